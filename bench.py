@@ -14,10 +14,17 @@ replicated, 8x8 image tiles are dealt to the ranks (tile t -> rank t % N, the re
 interleave, include/integrators.h:57-65,101), and the per-rank framebuffer slabs are gathered once
 per step with RCCL (one all_gather of equal padded slabs) and de-interleaved — no collective on
 the data path.  Scaling is STRONG: the frame stays 1800x800 at 512 spp, `value` is the rays of
-that frame over the slowest rank's time; rank 0 also times the whole frame alone once (untimed
-extra) so that the line carries t1_ms and efficiency = T1 / (N * T_N), and the weak-scaling figure
-rides along under "weak" (the frame grown with sqrt(N) per axis: every GPU keeps 1800x800 pixels).
+that frame over the slowest rank's time; with --full rank 0 also times the whole frame alone once
+(untimed extra) so that the line carries t1_ms and efficiency = T1 / (N * T_N), and the weak-scaling
+figure rides along under "weak" (the frame grown with sqrt(N) per axis: every GPU keeps 1800x800 pixels).
 `--weak` makes that frame the headline instead.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, count the rays
+of one frame (an untimed statistics launch after the timed ones), print the line.  `--full` adds
+the extras: the roofline, the CPU baseline legs (N == 1), and for N > 1 the whole-frame T1 with
+the efficiency and the weak-scaling figure.  `--dump-outputs DIR` writes the frame of the last
+timed step as DIR/frame.npy (float32 [H, W, 3]; above 64 MB a fixed, seeded sample of its pixels
+with their flat indices in DIR/frame_pixel_index.npy).
 
 Prints ONE JSON line on rank 0 (see the contract in the task statement).
 """
@@ -44,6 +51,8 @@ B_TRI = 4 + 48             # obj index + indices and vertices, per triangle test
 B_SPHERE = 4 + 16          # obj index + centre/radius, per sphere test
 B_MATERIAL = 72            # material record, per path vertex (one per next-event estimation)
 B_PIXEL = 12               # framebuffer, once per pixel
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
 
 
 def algorithmic_bytes(stats, pixels):
@@ -204,6 +213,22 @@ def cpu_baseline(spp):
     return out
 
 
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame a caller of the timed path receives, as DIR/frame.npy (float32).
+    A frame beyond DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its pixels (the same for
+    the same frame size), saved with their flat indices (float64, exact) beside it."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(frame, dtype=np.float32)
+    if img.nbytes > DUMP_LIMIT_BYTES:
+        pixels = img.reshape(-1, img.shape[-1])
+        keep = (DUMP_LIMIT_BYTES // 2) // pixels[0].nbytes
+        idx = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=keep, replace=False))
+        img = pixels[idx]
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "frame.npy"), img)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no rendezvous in the environment: start N fresh
     ranks as CHILD processes (never an exec: under rocprofv3 the GPU is initialised before this
@@ -251,6 +276,10 @@ def main():
                     help="rehearsal: every rank uses GPU 0 (needs --backend gloo)")
     ap.add_argument("--res", type=int, nargs=2, default=None, help="rehearsal: another frame size")
     ap.add_argument("--no-weak-leg", action="store_true", help="N>1: skip the weak-scaling figure that rides along")
+    ap.add_argument("--full", action="store_true",
+                    help="also the extras: roofline, CPU baseline legs (N=1), T1 / efficiency and the weak leg (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step as DIR/frame.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -283,9 +312,10 @@ def main():
     torch.cuda.set_stream(stream)
     red_dev = "cuda" if args.backend == "nccl" else "cpu"
 
-    def measure(res, steps, warmup):
+    def measure(res, steps, warmup, keep_frame=False):
         """W warm-up steps, then exactly `steps` steps of one frame of `res` between barriers;
-        returns the slowest rank's wall time and what was rendered."""
+        returns the slowest rank's wall time and what was rendered (`keep_frame`: also a host copy
+        of the last timed step's frame, taken before anything else writes the buffers)."""
         scene = load_scene(res)
         dev = hip.DeviceScene(scene)
         params = scene.default_params(samples=args.spp, tile_rank=rank, tile_world=n)
@@ -330,6 +360,7 @@ def main():
         elapsed = time.perf_counter() - t0
         dev.check()     # a frame the kernel's watchdog gave up is an error, not a measurement
         kernel_ms = sum(a.elapsed_time(b) for a, b in events) / steps
+        frame_host = frame.cpu().numpy() if keep_frame else None
         # event counts of one step (deterministic: same seeds every step); not timed, and AFTER the timed
         # launches: the statistics build uses scratch, and rocprofv3's dispatch records show a queue's
         # scratch on every later dispatch (the timed kernel's own record: Scratch_Size 0)
@@ -345,18 +376,22 @@ def main():
         return {"scene": scene, "dev": dev, "params": params, "frame": frame, "res": res,
                 "elapsed": float(t[0]), "kernel_ms": kernel_ms, "kernel_ms_max": float(t[1]),
                 "rays": float(counts[0]), "paths": float(counts[1]), "local_bytes": local_bytes, "local_rays": int(st.rays),
-                "kernel": dev.kernel_for(params)}
+                "kernel": dev.kernel_for(params), "frame_host": frame_host}
 
-    m = measure(res, args.steps, args.warmup)
+    m = measure(res, args.steps, args.warmup, keep_frame=bool(args.dump_outputs) and rank == 0)
     scene, dev, frame = m["scene"], m["dev"], m["frame"]
     W, H = res
     elapsed, kernel_ms, kernel_ms_max = m["elapsed"], m["kernel_ms"], m["kernel_ms_max"]
     total_rays, total_paths, local_bytes, kernel_name = m["rays"], m["paths"], m["local_bytes"], m["kernel"]
     local_rays = m["local_rays"]
 
-    # untimed extra on rank 0 (strong scaling): the whole frame alone, for T1 and --verify
+    # --dump-outputs: what the timed path computed in its last step
+    if m["frame_host"] is not None:
+        dump_outputs(args.dump_outputs, m["frame_host"])
+
+    # untimed extra on rank 0 (strong scaling, --full or --verify): the whole frame alone, for T1 and --verify
     t1_ms = None
-    if n > 1 and rank == 0 and not args.weak:
+    if n > 1 and rank == 0 and not args.weak and (args.full or args.verify):
         whole = scene.default_params(samples=args.spp)
         alone = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
         dev.render_async(whole, alone, stream=stream)           # warm-up of the whole-frame launch
@@ -371,10 +406,10 @@ def main():
             print("verify: assembled frame is bit-identical to the single-GPU frame", file=sys.stderr)
     if n > 1:
         dist.barrier()
-    # riding along for N > 1 (strong scaling is the headline): the same measurement on the frame grown
-    # with sqrt(N) per axis, where every GPU keeps 1800x800 pixels of work
+    # riding along for N > 1 with --full (strong scaling is the headline): the same measurement on the
+    # frame grown with sqrt(N) per axis, where every GPU keeps 1800x800 pixels of work
     weak = None
-    if n > 1 and not args.weak and not args.no_weak_leg:
+    if n > 1 and args.full and not args.weak and not args.no_weak_leg:
         try:
             mw = measure(grown, args.steps, 1)
             weak = {"resolution": list(grown), "ms_per_step": round(mw["elapsed"] / args.steps * 1e3, 3),
@@ -418,9 +453,10 @@ def main():
             out["t1_ms"] = round(t1_ms, 3)
             out["efficiency"] = round(t1_ms / (n * ms_per_step), 4)
             out["efficiency_kernels_only"] = round(t1_ms / (n * kernel_ms_max), 4)
-        roof = build_roofline(kernel_ms, local_bytes, local_rays, kernel_name, workload, library_fingerprint())
-        out["roofline"] = roof
-        if n == 1 and not args.no_cpu:
+        if args.full:
+            out["roofline"] = build_roofline(kernel_ms, local_bytes, local_rays, kernel_name, workload,
+                                             library_fingerprint())
+        if args.full and n == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.cpu_spp)
         print(json.dumps(out), flush=True)
     if n > 1:

@@ -1213,7 +1213,7 @@ def test_bench_self_launches_two_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--one-device", "--spp", "8", "--steps", "1", "--warmup", "0", "--no-cpu", "--verify",
+                        "--one-device", "--spp", "8", "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--verify",
                         "--res", "456", "200"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

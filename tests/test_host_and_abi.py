@@ -710,6 +710,28 @@ def test_bench_roofline_refuses_a_stale_pmc_pass(tmp_path):
     assert bench.library_fingerprint(str(tmp_path / "missing.so")) is None
 
 
+def test_bench_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: the frame as DIR/frame.npy (float32); beyond the size limit a
+    seeded sample of its pixels, the same on every run, with their flat indices beside it."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    frame = np.random.default_rng(1).random((20, 30, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    assert not (tmp_path / "whole" / "frame_pixel_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2400)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    pix, idx = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixel_index.npy")
+    assert pix.dtype == np.float32 and idx.dtype == np.float64 and pix.nbytes + idx.nbytes <= 2400
+    assert pix.shape == (100, 3) and np.array_equal(pix, frame.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_pixel_index.npy"))
+    assert np.array_equal(pix, np.load(tmp_path / "b" / "frame.npy"))
+
+
 def test_no_called_function_reads_the_kernel_argument_segment():
     """Guard of a fault that happened once (round 2, gpurun_out/s1/t.log: "Fatal Python error: Aborted" in
     render_to_host): under code object v5 a non-inlined device function gets no

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""From the PMC passes of tools/gpu_check.sh (bench.py --steps 1 --warmup 0 --spp 512: one stats
+"""From the PMC passes of tools/gpu_check.sh (bench.py --full --steps 1 --warmup 0 --spp 512: one stats
 launch, which runs the scheduler's DIAG build and is left out, + one timed launch) to the two
 small files bench.py reads: profiles/valu.json (VALU wave instructions and lane utilisation per
 launch) and profiles/traffic.json (HBM-side bytes per launch: FETCH_SIZE x 2 - the gfx950
