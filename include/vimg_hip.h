@@ -110,9 +110,36 @@ int64_t vimg_hip_shard_pixels(const VimgDeviceScene* scene, const VimgRenderPara
  * The call enqueues the kernels and waits for them (the reference call is blocking too).
  * Limit of one launch: the rings of a compute unit count the rays it queues in 32 bits - about 2^31 per
  * launch, i.e. the whole 1800x800 frame of disney_spheres up to ~60 000 samples per pixel (the reference's
- * scenes ask for 512-2048); beyond it the launch ends with VIMG_E_DEVICE and says so. */
+ * scenes ask for 512-2048); beyond it the launch ends with VIMG_E_DEVICE and says so.  More samples than
+ * that: render the frame progressively (below), where the limit holds per increment. */
 int vimg_hip_render(VimgDeviceScene* scene, const VimgRenderParams* params, void* d_out_rgb,
                     void* stream, VimgRenderStats* stats);
+
+/* Progressive rendering: one frame (or shard) of `scene` rendered a few samples at a time.  An accumulator
+ * is bound to one scene and one set of parameters: integrator, depth, tile_rank and tile_world are fixed
+ * for its life, params->samples is ignored.  It keeps a 32-byte record per pixel of the launch (the RNG
+ * state and the float sum, in the compact tile-major order of shards; twice, so that a failed increment
+ * leaves the last good state).
+ * Contract: increments n_1 .. n_k give, after each one, exactly the bits vimg_hip_render gives at
+ * samples = n_1 + .. + n_i - the same per-pixel PCG stream, the same jitter index, the same division -
+ * for every integrator, every shard and every scheduler configuration of this library.
+ *  _render  : adds `samples` samples to every pixel and writes the running mean in vimg_hip_render's
+ *             layout to d_out_rgb (DEVICE; NULL = advance only).  Blocks like vimg_hip_render and reads
+ *             the scene's error word; the accumulator advances only when the launch succeeded.  stats
+ *             (HOST, optional) = this increment's events.  VIMG_E_INVALID for samples == 0, a running
+ *             total beyond UINT32_MAX (the reference's sample count is 32-bit), another scene than the
+ *             accumulator's, NULL arguments.  The 2^31-ray limit of vimg_hip_render holds per increment.
+ *  _create  : VIMG_E_UNSUPPORTED for the development build's schedulers POOL, POOL4, POOL4G and STAGE.
+ *  _samples : samples per pixel so far (0 for NULL);  _reset: back to 0 (the next increment seeds again).
+ * Accumulators on the same scene are independent (each launch owns the scene's scratch while it runs);
+ * free them before their scene. */
+typedef struct VimgProgressive VimgProgressive;   /* opaque */
+int vimg_hip_progressive_create(VimgDeviceScene* scene, const VimgRenderParams* params, VimgProgressive** out);
+int vimg_hip_progressive_render(VimgDeviceScene* scene, VimgProgressive* acc, uint32_t samples,
+                                void* d_out_rgb, void* stream, VimgRenderStats* stats);
+uint64_t vimg_hip_progressive_samples(const VimgProgressive* acc);
+int vimg_hip_progressive_reset(VimgProgressive* acc);
+int vimg_hip_progressive_free(VimgProgressive* acc);
 
 /* Same as vimg_hip_render but only enqueues (no host wait, no stats); used by bench.py to time
  * back-to-back launches with HIP events on `stream`.  A scene renders one frame at a time: its

@@ -202,6 +202,11 @@ HIP_SYMBOLS = {
     "vimg_hip_shard_pixels": (i64, [C.c_void_p, PParams]),
     "vimg_hip_render": (C.c_int, [C.c_void_p, PParams, C.c_void_p, C.c_void_p, PStats]),
     "vimg_hip_render_async": (C.c_int, [C.c_void_p, PParams, C.c_void_p, C.c_void_p]),
+    "vimg_hip_progressive_create": (C.c_int, [C.c_void_p, PParams, C.POINTER(C.c_void_p)]),
+    "vimg_hip_progressive_render": (C.c_int, [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, PStats]),
+    "vimg_hip_progressive_samples": (C.c_uint64, [C.c_void_p]),
+    "vimg_hip_progressive_reset": (C.c_int, [C.c_void_p]),
+    "vimg_hip_progressive_free": (C.c_int, [C.c_void_p]),
     "vimg_hip_check": (C.c_int, [C.c_void_p]),
     "vimg_hip_render_to_host": (C.c_int, [C.c_void_p, PParams, Pf32, PStats]),
     "vimg_hip_trace_pixel": (C.c_int, [C.c_void_p, PParams, C.c_int, C.c_int, Pf32]),

@@ -3,9 +3,11 @@
 // on the GPU), -c tonemapper 0-3 (clamp, AgX, Reinhard, ACES; default AgX as main.cpp:97-114),
 // -d "x y" single-pixel trace, -b 0 binned / 1 sweep BVH (default 0 as main.cpp:183-187),
 // -m factor heatmap mode (BVH traversal cost, main.cpp:62-65,98-100,250-256), plus
-// -s spp override and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
+// -s spp override, -p step progressive rendering (increments of `step` samples, the PNG rewritten
+// after each; the last one is byte-identical to a plain run) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
 // here on the host (libvimg_host); the render and the post chain go through the C ABI of
 // libvimg_hip.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +27,7 @@ static double now_s() {
 int main(int argc, char** argv) {
   std::string scene_path, out_path = "v_img_amd.png";
   int tonemapper = 0, bvh_type = VIMG_BVH_BINNED, px = -1, py = -1;   // clamp, as src/main.cpp:46
-  long spp_override = -1;
+  long spp_override = -1, prog_step = 0;
   float heatmap_max = -1.f;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -39,6 +41,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "-b") bvh_type = std::atoi(next()) == 1 ? VIMG_BVH_SWEEP : VIMG_BVH_BINNED;
     else if (a == "-s") spp_override = std::atol(next());
+    else if (a == "-p") prog_step = std::atol(next());
     else if (a == "-m") heatmap_max = static_cast<float>(std::atof(next()));
     else if (a == "-o") out_path = next();
     else if (a == "-d") {
@@ -47,7 +50,7 @@ int main(int argc, char** argv) {
         return 2;
       }
     } else {
-      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-d \"x y\"] [-o out.png]\n");
+      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step] [-d \"x y\"] [-o out.png]\n");
       return 2;
     }
   }
@@ -120,6 +123,31 @@ int main(int argc, char** argv) {
       return 1;
     }
     std::printf("image rendering %.3f s\n", now_s() - t3);
+  } else if (prog_step > 0) {
+    // progressive: increments of prog_step samples (the last one may be shorter), each picture a valid preview
+    VimgProgressive* acc = nullptr;
+    if (vimg_hip_progressive_create(dev, &params, &acc) != VIMG_OK) {
+      std::fprintf(stderr, "progressive set-up failed: %s\n", vimg_hip_last_error());
+      return 1;
+    }
+    std::vector<uint8_t> rgb8(n * 3);
+    for (uint32_t done = 0; done < params.samples;) {
+      const uint32_t k = static_cast<uint32_t>(std::min<long>(prog_step, long(params.samples - done)));
+      if (vimg_hip_progressive_render(dev, acc, k, d_rgb, nullptr, nullptr) != VIMG_OK) {
+        std::fprintf(stderr, "render failed: %s\n", vimg_hip_last_error());
+        return 1;
+      }
+      done += k;
+      if (vimg_hip_post_rgb8(d_rgb, W, H, tonemapper, d_rgb8, nullptr) != VIMG_OK ||
+          hipMemcpy(rgb8.data(), d_rgb8, n * 3, hipMemcpyDeviceToHost) != hipSuccess ||
+          vimg_host_write_png(out_path.c_str(), rgb8.data(), W, H) != 0) {
+        std::fprintf(stderr, "preview write failed: %s %s\n", vimg_hip_last_error(), vimg_host_last_error());
+        return 1;
+      }
+      std::printf("samples %u / %u (%.3f s)\n", done, params.samples, now_s() - t3);
+      std::fflush(stdout);
+    }
+    vimg_hip_progressive_free(acc);
   } else {
     if (vimg_hip_render(dev, &params, d_rgb, nullptr, &st) != VIMG_OK) {
       std::fprintf(stderr, "render failed: %s\n", vimg_hip_last_error());

@@ -152,6 +152,13 @@ struct RenderArgs {
   uint32_t cu_magic_v, cu_shift_v;  // CU scheduler: n / pool_slots == mulhi(n, magic) >> shift (n < 2^31)
   uint32_t cu_magic_w, cu_shift_w;  // ... n / (2 * pool_slots)
   int32_t single_x, single_y;       // trace_pixel mode when >= 0
+  // progressive rendering (vimg_hip_progressive_render): the launch adds `samples` to pixels that already had
+  // `sample_base`; segment 0 of a pixel starts from its record in prog_in when sample_base > 0, and the pixel's
+  // last sample writes its record to prog_out.  Ordinary launches: 0, float(samples), nullptr, nullptr
+  uint32_t sample_base;             // samples per pixel before this launch (the R2 jitter index is absolute)
+  float spp_div;                    // static_cast<float>(sample_base + samples): the divisor of the mean
+  const VIMG_GLOBAL v4u* prog_in;   // per work item {rng lo, rng hi, -, -}{acc.xyz, -}, in the launch's item order
+  VIMG_GLOBAL v4u* prog_out;        // the same records after this launch (another buffer: a failed launch leaves prog_in as it was)
 };
 
 struct DeviceStats {

@@ -692,7 +692,11 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
       acc = acc + result;
       smp += 1;
       if (smp == A.samples) {
-        const f3 px_col = acc / static_cast<float>(A.samples);
+        const f3 px_col = acc / A.spp_div;
+        if (A.prog_out) {   // progressive launch: the pixel rests in its record until the next increment
+          A.prog_out[size_t(item) * 2u] = v4u{static_cast<uint32_t>(rng.s), static_cast<uint32_t>(rng.s >> 32), 0u, 0u};
+          A.prog_out[size_t(item) * 2u + 1u] = v4u{fu(acc.x), fu(acc.y), fu(acc.z), 0u};
+        }
         size_t o;
         if (single)
           o = 0;
@@ -770,10 +774,16 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
           if (!valid) {
             have_claim = false;   // off the image in every segment: draw another item
           } else if (seg == 0u) {
-            const uint64_t image_index = uint64_t(px) + uint64_t(H - 1 - py) * W;
-            pcg_seed(rng, image_index);
+            if (A.sample_base == 0u) {
+              const uint64_t image_index = uint64_t(px) + uint64_t(H - 1 - py) * W;
+              pcg_seed(rng, image_index);
+              acc = f3{0.f, 0.f, 0.f};
+            } else {   // a progressive launch after the first: the pixel goes on from its record
+              const v4u r0 = A.prog_in[size_t(item) * 2u], r1 = A.prog_in[size_t(item) * 2u + 1u];
+              rng.s = uint64_t(r0.x) | (uint64_t(r0.y) << 32);
+              acc = f3{uf(r1.x), uf(r1.y), uf(r1.z)};
+            }
             smp = 0;
-            acc = f3{0.f, 0.f, 0.f};
             need_pixel = false;
           } else {
             VIMG_GLOBAL uint32_t* st = reinterpret_cast<VIMG_GLOBAL uint32_t*>(A.pool_state + size_t(item) * 2u);
@@ -796,7 +806,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
     all_pending = (__ballot(pending) == __ballot(on));
     const bool regen = on && !retire && !pending && (finish || fresh);
     if (regen) {
-      const f2 off = random_x_y_r2(px + py + smp);
+      const f2 off = random_x_y_r2(px + py + A.sample_base + smp);   // (smp counts within the launch)
       // right-to-left argument evaluation of the reference's call
       const float rand2 = rand_float(rng);
       const float rand1 = rand_float(rng);

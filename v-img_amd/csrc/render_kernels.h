@@ -1659,10 +1659,16 @@ render_kernel(const DScene g, const RenderArgs A, float* __restrict__ out,
               valid = (tx < A.tiles_x) && (px < W) && (py < H);
             }
             if (valid) {
-              const uint64_t image_index = uint64_t(px) + uint64_t(H - 1 - py) * W;
-              pcg_seed(rng, image_index);
+              if (A.sample_base == 0u) {
+                const uint64_t image_index = uint64_t(px) + uint64_t(H - 1 - py) * W;
+                pcg_seed(rng, image_index);
+                acc = f3{0.f, 0.f, 0.f};
+              } else {   // a progressive launch after the first: the pixel goes on from its record
+                const v4u r0 = A.prog_in[size_t(item) * 2u], r1 = A.prog_in[size_t(item) * 2u + 1u];
+                rng.s = uint64_t(r0.x) | (uint64_t(r0.y) << 32);
+                acc = f3{__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z)};
+              }
               smp = 0;
-              acc = f3{0.f, 0.f, 0.f};
               new_path = true;
               need_pixel = false;
             }
@@ -1676,7 +1682,7 @@ render_kernel(const DScene g, const RenderArgs A, float* __restrict__ out,
 
     // ------------------------------------------------------------------ camera ray
     if (active && new_path) {
-      const f2 off = random_x_y_r2(px + py + smp);
+      const f2 off = random_x_y_r2(px + py + A.sample_base + smp);   // (smp counts within the launch)
       // the reference's call evaluates its two rand_float arguments right to left (g++):
       // rand2 receives the first draw
       const float rand2 = rand_float(rng);
@@ -1948,7 +1954,11 @@ render_kernel(const DScene g, const RenderArgs A, float* __restrict__ out,
       smp += 1;
       new_path = true;
       if (smp == A.samples) {
-        const f3 px_col = acc / static_cast<float>(A.samples);
+        const f3 px_col = acc / static_cast<float>(A.sample_base + A.samples);   // (= A.spp_div, one register fewer here)
+        if (A.prog_out) {   // progressive launch: the pixel rests in its record until the next increment
+          A.prog_out[size_t(item) * 2u] = v4u{static_cast<uint32_t>(rng.s), static_cast<uint32_t>(rng.s >> 32), 0u, 0u};
+          A.prog_out[size_t(item) * 2u + 1u] = v4u{__float_as_uint(acc.x), __float_as_uint(acc.y), __float_as_uint(acc.z), 0u};
+        }
         size_t o;
         if (single)
           o = 0;

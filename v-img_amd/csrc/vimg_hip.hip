@@ -85,6 +85,18 @@ struct VimgDeviceScene {
   size_t stage_slots_bytes = 0;
 };
 
+// A frame rendered in increments (vimg_hip_progressive_*): its scene, its parameters and the pixel records.
+struct VimgProgressive {
+  VimgDeviceScene* scene = nullptr;
+  VimgRenderParams params{};      // samples field unused
+  uint64_t items = 0;             // work items of a launch (64 per tile of the shard)
+  void* d_rec[2] = {nullptr, nullptr};   // 32 B per item each; d_rec[cur] holds the state after `samples`
+  int cur = 0;
+  uint32_t samples = 0;           // samples per pixel so far
+  void* d_scratch = nullptr;      // the means of increments asked for without an output buffer
+  size_t scratch_bytes = 0;
+};
+
 namespace {
 
 template <typename T>
@@ -346,6 +358,7 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   RenderArgs& a = c.args;
   a.integrator = p->integrator;
   a.samples = p->samples;
+  a.spp_div = static_cast<float>(p->samples);   // (a progressive launch sets the base and the divisor of its total)
   a.depth = p->depth;
   a.tile_rank = p->tile_rank;
   a.tile_world = p->tile_world;
@@ -508,6 +521,7 @@ LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int s
   RenderArgs& a = c.args;
   a.integrator = p->integrator;
   a.samples = p->samples;
+  a.spp_div = static_cast<float>(p->samples);   // (a progressive launch sets the base and the divisor of its total)
   a.depth = p->depth;
   a.tile_rank = p->tile_rank;
   a.tile_world = p->tile_world;
@@ -768,12 +782,30 @@ int ensure_stage(VimgDeviceScene* s, LaunchCfg& c, hipStream_t st) {
   return VIMG_OK;
 }
 
+// A progressive launch (vimg_hip_progressive_render): p->samples more samples for pixels that have had
+// `base`, their records read from `in` (when base > 0) and written to `out`.
+struct ProgLaunch {
+  uint32_t base;
+  const void* in;
+  void* out;
+};
+
 // Enqueues one render on `st` (counter / queue resets, then the kernel); ev0 / ev1, when given, are
 // recorded right before and right after the kernel itself.
 int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, hipStream_t st,
                    bool full_stats, bool want_stats, int sx, int sy, hipEvent_t ev0 = nullptr,
-                   hipEvent_t ev1 = nullptr) {
+                   hipEvent_t ev1 = nullptr, const ProgLaunch* prog = nullptr) {
   LaunchCfg c = make_launch(s, p, sx, sy);
+  if (prog) {
+    // only the two schedulers of the product library carry a pixel across launches
+    if (c.sched != VIMG_SCHED_CU && c.sched != VIMG_SCHED_LANE)
+      return fail(VIMG_E_UNSUPPORTED, "progressive rendering: the schedulers POOL, POOL4, POOL4G and STAGE of the "
+                                      "development build do not resume pixels across launches");
+    c.args.sample_base = prog->base;
+    c.args.spp_div = static_cast<float>(prog->base + p->samples);   // (the caller keeps the total <= UINT32_MAX)
+    c.args.prog_in = (const VIMG_GLOBAL v4u*)prog->in;
+    c.args.prog_out = (VIMG_GLOBAL v4u*)prog->out;
+  }
   if (int rc = ensure_pool(s, c)) return rc;
   c.args.full_stats = full_stats ? 1u : 0u;
   if (c.args.num_local_tiles == 0 && sx < 0) return VIMG_OK;
@@ -833,7 +865,8 @@ int check_kernel_error(VimgDeviceScene* s) {
     // bits of the launch's error word (render_cu_kernel.h: raise): 1 a wave found nothing to do for ten seconds
     // while slots were live, 2 a group lock timed out (development build), 4 a ring entry was reserved and never
     // written, 8 a compute unit queued more than 2^31 rays or slots in one launch
-    const std::string what = (words[1] & 8u) ? "a compute unit queued more than 2^31 rays in one launch: render fewer samples per launch"
+    const std::string what = (words[1] & 8u) ? "a compute unit queued more than 2^31 rays in one launch: render fewer samples per launch "
+                                               "(vimg_hip_progressive_render adds a frame's samples in increments)"
                                              : "a wave waited for work that never came";
     return fail(VIMG_E_DEVICE, "render kernel watchdog: " + what + " (the frame is incomplete), code " +
                                    std::to_string(words[1] | (stage_err << 8)));
@@ -1347,6 +1380,79 @@ int vimg_hip_render(VimgDeviceScene* s, const VimgRenderParams* p, void* d_out, 
   HIP_TRY(hipStreamSynchronize(st));
   if (int rc2 = check_kernel_error(s)) return rc2;
   if (stats) return fetch_stats(s, p, stats);
+  return VIMG_OK;
+}
+
+// ---- progressive rendering: a frame's samples in increments, bit for bit the one-shot render of their total.
+// Between increments a pixel rests in a 32-byte record {rng lo, rng hi, -, -}{acc.xyz, -} per work item (the
+// launch's compact tile-major order); a launch reads the records of the last good state and writes the other
+// buffer, so a launch that fails leaves the accumulator where it was.
+int vimg_hip_progressive_create(VimgDeviceScene* s, const VimgRenderParams* p, VimgProgressive** out) {
+  if (!out) return fail(VIMG_E_INVALID, "progressive: null output handle");
+  *out = nullptr;
+  if (!s || !p) return fail(VIMG_E_INVALID, "progressive: null scene or params");
+  VimgRenderParams q = *p;
+  q.samples = 1;   // (ignored: every increment says how many)
+  if (int rc = check_params(s, &q)) return rc;
+  if (s->opt.scheduler != VIMG_OPT_AUTO && s->opt.scheduler != VIMG_SCHED_LANE && s->opt.scheduler != VIMG_SCHED_CU)
+    return fail(VIMG_E_UNSUPPORTED, "progressive rendering: the schedulers POOL, POOL4, POOL4G and STAGE of the "
+                                    "development build do not resume pixels across launches");
+  VimgProgressive* a = new VimgProgressive{};
+  a->scene = s;
+  a->params = q;
+  a->items = uint64_t(local_tiles(s, &q)) * 64u;
+  const size_t bytes = std::max<size_t>(a->items, 1) * 32u;
+  for (int k = 0; k < 2; ++k) {
+    if (hipMalloc(&a->d_rec[k], bytes) != hipSuccess) {
+      vimg_hip_progressive_free(a);
+      return fail(VIMG_E_DEVICE, "progressive: hipMalloc of the pixel records failed");
+    }
+  }
+  *out = a;
+  return VIMG_OK;
+}
+
+int vimg_hip_progressive_render(VimgDeviceScene* s, VimgProgressive* a, uint32_t samples, void* d_out, void* stream,
+                                VimgRenderStats* stats) {
+  if (!s || !a) return fail(VIMG_E_INVALID, "progressive: null scene or accumulator");
+  if (a->scene != s) return fail(VIMG_E_INVALID, "progressive: the accumulator belongs to another scene");
+  if (samples == 0) return fail(VIMG_E_INVALID, "samples must be > 0");
+  if (uint64_t(a->samples) + samples > 0xffffffffull)
+    return fail(VIMG_E_INVALID, "progressive: more than 2^32 - 1 samples per pixel in all (the reference counts them in 32 bits)");
+  VimgRenderParams p = a->params;
+  p.samples = samples;
+  if (int rc = check_params(s, &p)) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  if (!d_out) {   // advance only: the means go to a buffer of the accumulator's
+    const size_t floats = (p.tile_world == 1 ? size_t(s->d.res_x) * s->d.res_y : size_t(a->items)) * 3u;
+    if (int rc = grow(&a->d_scratch, &a->scratch_bytes, std::max<size_t>(floats, 3) * sizeof(float))) return rc;
+    d_out = a->d_scratch;
+  }
+  const ProgLaunch pl{a->samples, a->d_rec[a->cur], a->d_rec[a->cur ^ 1]};
+  int rc = enqueue_render(s, &p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1, nullptr,
+                          nullptr, &pl);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc2 = check_kernel_error(s)) return rc2;
+  a->samples += samples;
+  a->cur ^= 1;
+  if (stats) return fetch_stats(s, &p, stats);
+  return VIMG_OK;
+}
+
+uint64_t vimg_hip_progressive_samples(const VimgProgressive* a) { return a ? a->samples : 0u; }
+
+int vimg_hip_progressive_reset(VimgProgressive* a) {
+  if (!a) return fail(VIMG_E_INVALID, "progressive: null accumulator");
+  a->samples = 0;   // the next increment seeds every pixel again
+  return VIMG_OK;
+}
+
+int vimg_hip_progressive_free(VimgProgressive* a) {
+  if (!a) return VIMG_OK;
+  for (void* q : {a->d_rec[0], a->d_rec[1], a->d_scratch})
+    if (q) (void)hipFree(q);
+  delete a;
   return VIMG_OK;
 }
 

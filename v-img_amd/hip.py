@@ -116,6 +116,12 @@ class DeviceScene:
                                              C.byref(st) if stats else None))
         return (out, st) if stats else out
 
+    def progressive(self, params):
+        """An accumulator for this frame (or shard) rendered a few samples at a time (vimg_hip_progressive_*):
+        after increments n_1 .. n_k the image is bit for bit ``render`` at n_1 + .. + n_k samples.
+        ``params.samples`` is ignored; the other fields are fixed for the accumulator's life."""
+        return Progressive(self, params)
+
     def render_async(self, params, out, stream=None):
         with _Ordered(stream) as sp:
             _check(self._lib.vimg_hip_render_async(self._h, C.byref(params),
@@ -200,6 +206,66 @@ class DeviceScene:
             pass
 
 
+class Progressive:
+    """A frame of one DeviceScene rendered in increments (DeviceScene.progressive).  Every call is ordered
+    on torch's stream the way DeviceScene.render is."""
+
+    def __init__(self, dev, params):
+        self._lib = dev._lib
+        self._dev = dev              # (keeps the scene alive while the accumulator is)
+        self.params = abi.RenderParams.from_buffer_copy(params)
+        h = C.c_void_p()
+        _check(self._lib.vimg_hip_progressive_create(dev._h, C.byref(self.params), C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if not self._h:
+            raise HipError("progressive accumulator used after close()")
+        return self._h
+
+    @property
+    def samples(self):
+        """Samples per pixel so far."""
+        return int(self._lib.vimg_hip_progressive_samples(self._handle()))
+
+    def render(self, samples, out=None, stats=False, stream=None):
+        """Adds `samples` samples per pixel and returns the running mean in ``DeviceScene.render``'s shapes
+        ([H, W, 3], or the shard's compact [shard_pixels, 3] when tile_world > 1), with this increment's
+        RenderStats when ``stats``.  ``out=False``: advance only, nothing is written or returned but the stats."""
+        import torch
+        h = self._handle()
+        w, ht = self._dev.resolution
+        if out is None:
+            if self.params.tile_world == 1:
+                out = torch.empty((ht, w, 3), dtype=torch.float32, device="cuda")
+            else:
+                out = torch.zeros((self._dev.shard_pixels(self.params), 3), dtype=torch.float32, device="cuda")
+        ptr = None if out is False else C.c_void_p(out.data_ptr())
+        st = abi.RenderStats()
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_progressive_render(self._dev._h, h, int(samples), ptr, sp,
+                                                         C.byref(st) if stats else None))
+        img = None if out is False else out
+        return (img, st) if stats else img
+
+    def reset(self, stream=None):
+        """Back to 0 samples: the next increment seeds every pixel again."""
+        h = self._handle()
+        with _Ordered(stream):
+            _check(self._lib.vimg_hip_progressive_reset(h))
+
+    def close(self):
+        if self._h:
+            self._lib.vimg_hip_progressive_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def post_rgb8(image, tonemapper=1, stream=None):
     """Tonemap + sRGB + 8-bit quantise a [H, W, 3] float32 CUDA tensor on the GPU
     (vimg_hip_post_rgb8); returns a [H, W, 3] uint8 CUDA tensor."""
@@ -212,7 +278,7 @@ def post_rgb8(image, tonemapper=1, stream=None):
     return out
 
 
-__all__ = ["DeviceScene", "post_rgb8", "HipError", "device_count", "init", "make_params"]
+__all__ = ["DeviceScene", "Progressive", "post_rgb8", "HipError", "device_count", "init", "make_params"]
 
 
 # ---- the pre-step of the path on the GPU (include/vimg_hip.h) ----------
