@@ -94,6 +94,32 @@ int vimg_hip_scene_upload(const VimgScene* scene, VimgDeviceScene** out);
 int vimg_hip_scene_upload_opts(const VimgScene* scene, const VimgHipOptions* opts, VimgDeviceScene** out);
 int vimg_hip_scene_free(VimgDeviceScene* scene);
 
+/* Changing a resident scene without a new upload: same topology, materials, textures,
+ * lights and resolution; new positions and a new camera.
+ *  _update_geometry : new positions, NULL = unchanged.  DEVICE pointers to float32, read on `stream`:
+ *      vertices num_vertices x 3 (the whole table, VimgScene order), normals num_vertices x 3 (rows of
+ *      meshes without normals are ignored), spheres num_spheres x 4 (centre xyz, radius; the material
+ *      stays).  Bakes again everything the upload derives from positions - triangle records, face
+ *      normals, area pdfs, leaf records and their degenerate flag, emitters - and refits the tree's boxes
+ *      bottom-up in its existing topology, all in kernels with the upload's float expressions and the host
+ *      builders' fold order; then blocks until the scene is consistent (the inputs may be reused at once).
+ *      A launch afterwards reads exactly what an upload of the host scene with the same positions and a
+ *      vimg_host_refit_bvh tree reads.  Values are taken as they come (no finiteness check).
+ *  _set_camera : the camera values the upload derives (pixel size, primary-ray cone, lens).  A different
+ *      res_x / res_y is VIMG_E_INVALID.
+ * Both change the scene's generation: a VimgProgressive whose records were made before refuses its next
+ * increment (VIMG_E_INVALID) until vimg_hip_progressive_reset.  Argument errors (NULL, struct_size too
+ * small) return VIMG_E_INVALID and leave the scene as it was.  Launches on the scene stay ordered on one
+ * stream, as for every launch of a scene. */
+typedef struct VimgGeometryUpdate {
+  uint32_t struct_size;     /* sizeof(VimgGeometryUpdate) */
+  const void* vertices;     /* num_vertices x 3, or NULL */
+  const void* normals;      /* num_vertices x 3, or NULL */
+  const void* spheres;      /* num_spheres x 4, or NULL */
+} VimgGeometryUpdate;
+int vimg_hip_scene_update_geometry(VimgDeviceScene* scene, const VimgGeometryUpdate* update, void* stream);
+int vimg_hip_scene_set_camera(VimgDeviceScene* scene, const VimgCamera* camera);
+
 /* Number of float triples a shard's compact framebuffer holds
  * (= 64 * number of 8x8 tiles owned by tile_rank). */
 int64_t vimg_hip_shard_pixels(const VimgDeviceScene* scene, const VimgRenderParams* params);

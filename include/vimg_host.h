@@ -33,6 +33,9 @@ void vimg_host_scene_free(VimgHostScene* s);
 void vimg_host_set_camera_lookat(VimgHostScene* s, const float from[3], const float at[3],
                                  const float up[3], float vfov_deg, int res_x, int res_y,
                                  float aperture_radius, float focal_dist);
+/* The VimgCamera that vimg_host_set_camera_lookat stores (for vimg_hip_scene_set_camera). */
+void vimg_host_camera_lookat(const float from[3], const float at[3], const float up[3], float vfov_deg,
+                             int res_x, int res_y, float aperture_radius, float focal_dist, VimgCamera* out);
 void vimg_host_set_render_defaults(VimgHostScene* s, uint32_t integrator, uint32_t samples,
                                    uint32_t depth);
 
@@ -92,6 +95,18 @@ typedef int (*vimg_bvh_builder_fn)(uint32_t n, const float* bounds6, uint32_t* n
                                    uint32_t* max_depth, VimgBVHNode* nodes, float* bb,
                                    uint32_t* obj_indices);
 int vimg_host_build_bvh_with(VimgHostScene* s, vimg_bvh_builder_fn builder);
+
+/* ---- new positions in the same topology: the host counterpart of vimg_hip_scene_update_geometry.
+ * A scene that is set and refit, then uploaded, is what a device scene updated with the same
+ * positions holds.  set_vertices: xyz = num_vertices x 3 (the whole table); normals num_vertices x 3
+ * or NULL (= keep), only rows of meshes with normals are taken.  set_spheres: num_spheres x 4
+ * (centre xyz, radius; the material stays).  Neither touches the tree: refit_bvh recomputes its boxes
+ * from the primitive bounds of vimg_host_build_bvh in the same topology - a leaf folded over its
+ * primitives in obj_indices order from the first, an internal node as the union of its children -
+ * and fails on a scene without a BVH. */
+int vimg_host_set_vertices(VimgHostScene* s, const float* xyz, const float* normals);
+int vimg_host_set_spheres(VimgHostScene* s, const float* centre_radius);
+int vimg_host_refit_bvh(VimgHostScene* s);
 
 /* View valid until the scene is modified or freed.  NULL before vimg_host_build_bvh. */
 const VimgScene* vimg_host_scene_view(const VimgHostScene* s);

@@ -123,6 +123,15 @@ class RenderStats(C.Structure):
         return int(self.closest_rays) + int(self.shadow_rays)
 
 
+class GeometryUpdate(C.Structure):
+    """VimgGeometryUpdate (include/vimg_hip.h): device pointers to float32 tables, NULL = unchanged."""
+    _fields_ = [("struct_size", u32), ("vertices", C.c_void_p), ("normals", C.c_void_p), ("spheres", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GeometryUpdate)
+
+
 OPT_AUTO = -1
 SCHED_LANE, SCHED_POOL, SCHED_STAGE, SCHED_POOL4, SCHED_POOL4G, SCHED_CU = 1, 2, 3, 4, 5, 6
 SCHEDULERS = {"lane": SCHED_LANE, "pool": SCHED_POOL, "stage": SCHED_STAGE, "pool4": SCHED_POOL4, "pool4g": SCHED_POOL4G, "cu": SCHED_CU}
@@ -165,6 +174,7 @@ HOST_SYMBOLS = {
     "vimg_host_scene_free": (None, [C.c_void_p]),
     "vimg_host_set_camera_lookat": (None, [C.c_void_p, Pf32, Pf32, Pf32, f32, C.c_int, C.c_int,
                                            f32, f32]),
+    "vimg_host_camera_lookat": (None, [Pf32, Pf32, Pf32, f32, C.c_int, C.c_int, f32, f32, C.POINTER(Camera)]),
     "vimg_host_set_render_defaults": (None, [C.c_void_p, u32, u32, u32]),
     "vimg_host_add_texture_const": (C.c_int, [C.c_void_p, Pf32]),
     "vimg_host_add_texture_checker": (C.c_int, [C.c_void_p, u32, u32, Pf32, Pf32]),
@@ -183,6 +193,9 @@ HOST_SYMBOLS = {
     "vimg_host_rgb8_to_normal": (None, [C.POINTER(C.c_uint8), C.c_uint64, f32, Pf32]),
     "vimg_host_build_bvh": (C.c_int, [C.c_void_p, C.c_int]),
     "vimg_host_build_bvh_with": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vimg_host_set_vertices": (C.c_int, [C.c_void_p, Pf32, Pf32]),
+    "vimg_host_set_spheres": (C.c_int, [C.c_void_p, Pf32]),
+    "vimg_host_refit_bvh": (C.c_int, [C.c_void_p]),
     "vimg_host_scene_view": (PScene, [C.c_void_p]),
     "vimg_host_default_params": (None, [C.c_void_p, PParams]),
     "vimg_host_tonemap_to_rgb8": (C.c_int, [Pf32, C.c_int, C.c_int, C.c_int,
@@ -199,6 +212,8 @@ HIP_SYMBOLS = {
     "vimg_hip_scene_upload": (C.c_int, [PScene, C.POINTER(C.c_void_p)]),
     "vimg_hip_scene_upload_opts": (C.c_int, [PScene, C.POINTER(HipOptions), C.POINTER(C.c_void_p)]),
     "vimg_hip_scene_free": (C.c_int, [C.c_void_p]),
+    "vimg_hip_scene_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]),
+    "vimg_hip_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     "vimg_hip_shard_pixels": (i64, [C.c_void_p, PParams]),
     "vimg_hip_render": (C.c_int, [C.c_void_p, PParams, C.c_void_p, C.c_void_p, PStats]),
     "vimg_hip_render_async": (C.c_int, [C.c_void_p, PParams, C.c_void_p, C.c_void_p]),

@@ -1,0 +1,198 @@
+// Geometry update of a resident scene (vimg_hip_scene_update_geometry): the records the
+// upload bakes from the positions are baked again from new ones, with the upload's float expressions,
+// and the tree keeps its topology while its boxes are recomputed bottom-up.
+//
+//   scene_update_tris     one thread per triangle: DTriShade positions, face normal n, tri_area_pdf
+//   scene_update_spheres  one thread per sphere: centre and radius of d.spheres (the material stays)
+//   scene_update_leaves   one thread per leaf slot: a, b, c0 and the degenerate flag of DLeafPrim
+//   scene_update_lights   one thread per emitter: the triangle / sphere fields of DLight
+//   scene_refit_chains    one thread per chain record (leaves over 127 primitives): the leaf's box twice
+//   scene_refit_level     one thread per internal node of one breadth-first level, deepest level first
+//   scene_refit_root      one thread: the root's box for DScene::root_min / root_max
+//
+// Boxes are folded with the host's selects (b < a ? b : a, a < b ? b : a; host/hmath.hpp) in the host
+// builders' order: a triangle's box is vmin(v0, vmin(v1, v2)), a leaf's the fold over its primitives in
+// obj_indices order from the first, an internal child's grow(left, right).  The levels need no
+// synchronisation between workgroups: a launch only reads records the launches before it wrote.
+#include <hip/hip_runtime.h>
+
+#include "device_math.h"
+#include "scene_update.h"
+
+namespace vimg {
+
+namespace {
+
+constexpr uint32_t kRefMask = (1u << 25) - 1u;
+
+// the scene's tables as plain (flat) pointers: records are copied whole, and written (off the hot path)
+template <typename T>
+VD T* flat(gptr<T> p) {
+  return (T*)p;
+}
+
+struct Box3 {
+  f3 lo, hi;
+};
+
+VD Box3 grow(Box3 a, Box3 b) {
+  return Box3{mk3(sel_min(a.lo.x, b.lo.x), sel_min(a.lo.y, b.lo.y), sel_min(a.lo.z, b.lo.z)),
+              mk3(sel_max(a.hi.x, b.hi.x), sel_max(a.hi.y, b.hi.y), sel_max(a.hi.z, b.hi.z))};
+}
+
+// prim_bounds (host/bvh_build.cpp) of one leaf slot
+VD Box3 slot_box(const DScene& d, uint32_t j) {
+  const DLeafPrim lp = flat(d.leaf_prims)[j];
+  if (lp.kind == 1u) {
+    const float r = lp.a.w;
+    return Box3{mk3(lp.a.x - r, lp.a.y - r, lp.a.z - r), mk3(lp.a.x + r, lp.a.y + r, lp.a.z + r)};
+  }
+  const f3 v0 = mk3(lp.a.x, lp.a.y, lp.a.z), v1 = mk3(lp.a.w, lp.b.x, lp.b.y), v2 = mk3(lp.b.z, lp.b.w, lp.c0);
+  const Box3 b12{mk3(sel_min(v1.x, v2.x), sel_min(v1.y, v2.y), sel_min(v1.z, v2.z)),
+                 mk3(sel_max(v1.x, v2.x), sel_max(v1.y, v2.y), sel_max(v1.z, v2.z))};
+  return Box3{mk3(sel_min(v0.x, b12.lo.x), sel_min(v0.y, b12.lo.y), sel_min(v0.z, b12.lo.z)),
+              mk3(sel_max(v0.x, b12.hi.x), sel_max(v0.y, b12.hi.y), sel_max(v0.z, b12.hi.z))};
+}
+
+VD Box3 leaf_box(const DScene& d, uint32_t first, uint32_t count) {
+  Box3 b = slot_box(d, first);
+  for (uint32_t i = 1; i < count; ++i) b = grow(b, slot_box(d, first + i));
+  return b;
+}
+
+// the box a child reference stands for: a leaf's fold, or the union of a node's two children (a chain
+// record carries its whole leaf on both sides, and grow(b, b) is b bit for bit)
+VD Box3 ref_box(const DScene& d, uint32_t ref) {
+  const uint32_t count = ref >> 25, idx = ref & kRefMask;
+  if (count) return leaf_box(d, idx, count);
+  const DNode n = flat(d.nodes)[idx];
+  const Box3 l{mk3(n.a.x, n.a.y, n.a.z), mk3(n.a.w, n.b.x, n.b.y)};
+  const Box3 r{mk3(n.b.z, n.b.w, n.c.x), mk3(n.c.y, n.c.z, n.c.w)};
+  return grow(l, r);
+}
+
+// the DNode layout of vimg_hip_scene_upload_opts: a = Lmin Lmax.x, b = Lmax.yz Rmin.xy, c = Rmin.z Rmax
+VD void store_boxes(const DScene& d, uint32_t i, Box3 l, Box3 r) {
+  DNode* n = flat(d.nodes) + i;
+  n->a = v4f{l.lo.x, l.lo.y, l.lo.z, l.hi.x};
+  n->b = v4f{l.hi.y, l.hi.z, r.lo.x, r.lo.y};
+  n->c = v4f{r.lo.z, r.hi.x, r.hi.y, r.hi.z};
+}
+
+}  // namespace
+
+__global__ void scene_update_tris(const DScene d, const float* vertices, uint32_t num_tris) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= num_tris) return;
+  DTriShade* ts = flat(d.tri_shade) + t;
+  const uint32_t ids[3] = {ts->i0, ts->i1, ts->i2};
+  float v[9];
+  for (int k = 0; k < 3; ++k)
+    for (int a = 0; a < 3; ++a) v[k * 3 + a] = vertices[size_t(ids[k]) * 3 + a];
+  // the upload's expressions (tri_normal and the area pdf, src/geometry/triangle.cpp:19-25,229-231)
+  const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+  const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+  const float c12[3] = {e1[1] * e2[2] - e2[1] * e1[2], e1[2] * e2[0] - e2[2] * e1[0],
+                        e1[0] * e2[1] - e2[0] * e1[1]};
+  const float inv_len = 1.0f / __builtin_sqrtf(c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2]);
+  const float c21[3] = {e2[1] * e1[2] - e1[1] * e2[2], e2[2] * e1[0] - e1[2] * e2[0],
+                        e2[0] * e1[1] - e1[0] * e2[1]};
+  const float area = __builtin_sqrtf(c21[0] * c21[0] + c21[1] * c21[1] + c21[2] * c21[2]) / 2.0f;
+  for (int k = 0; k < 9; ++k) ts->p[k] = v[k];
+  for (int a = 0; a < 3; ++a) ts->n[a] = c12[a] * inv_len;
+  flat(d.tri_area_pdf)[t] = 1.f / area;
+}
+
+__global__ void scene_update_spheres(const DScene d, const float* centre_radius, uint32_t num_spheres) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_spheres) return;
+  VimgSphere* sp = flat(d.spheres) + i;
+  for (int a = 0; a < 3; ++a) sp->center[a] = centre_radius[size_t(i) * 4 + a];
+  sp->radius = centre_radius[size_t(i) * 4 + 3];
+}
+
+__global__ void scene_update_leaves(const DScene d, uint32_t num_slots) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= num_slots) return;
+  DLeafPrim* lp = flat(d.leaf_prims) + j;
+  const VimgPrim p = flat(d.prims)[lp->prim];
+  if (p.type == VIMG_PRIM_TRIANGLE) {
+    const float* v = flat(d.tri_shade)[p.index].p;
+    lp->a = v4f{v[0], v[1], v[2], v[3]};
+    lp->b = v4f{v[4], v[5], v[6], v[7]};
+    lp->c0 = v[8];
+    // the degenerate-triangle reject (triangle.h:86-92) as the upload evaluates it
+    const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+    const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+    const float cx = e2[1] * e1[2] - e1[1] * e2[2];
+    const float cy = e2[2] * e1[0] - e1[2] * e2[0];
+    const float cz = e2[0] * e1[1] - e1[0] * e2[1];
+    const float l2 = cx * cx + cy * cy + cz * cz;
+    lp->kind = (l2 == 0.f) ? 2u : 0u;
+  } else {
+    const VimgSphere sp = flat(d.spheres)[p.index];
+    lp->a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
+  }
+}
+
+__global__ void scene_update_lights(const DScene d) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= d.num_lights) return;
+  const VimgLight l = flat(d.lights)[i];
+  if (l.type == VIMG_LIGHT_BACKGROUND) return;
+  const VimgPrim p = flat(d.prims)[l.prim];
+  DLight* L = flat(d.dlights) + i;
+  if (p.type == VIMG_PRIM_TRIANGLE) {
+    const DTriShade* ts = flat(d.tri_shade) + p.index;
+    L->a = v4f{ts->p[0], ts->p[1], ts->p[2], ts->p[3]};
+    L->b = v4f{ts->p[4], ts->p[5], ts->p[6], ts->p[7]};
+    L->c = v4f{ts->p[8], ts->n[0], ts->n[1], ts->n[2]};
+    L->d.w = flat(d.tri_area_pdf)[p.index];
+  } else {
+    const VimgSphere sp = flat(d.spheres)[p.index];
+    L->a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
+  }
+}
+
+__global__ void scene_refit_chains(const DScene d, const uint32_t* chain_leaf, uint32_t first_record, uint32_t n_chain) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_chain) return;
+  const Box3 b = leaf_box(d, chain_leaf[2 * k], chain_leaf[2 * k + 1]);
+  store_boxes(d, first_record + k, b, b);
+}
+
+__global__ void scene_refit_level(const DScene d, uint32_t begin, uint32_t end) {
+  const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= end) return;
+  const uint32_t lref = flat(d.nodes)[i].left_ref, rref = flat(d.nodes)[i].right_ref;
+  store_boxes(d, i, ref_box(d, lref), ref_box(d, rref));
+}
+
+__global__ void scene_refit_root(const DScene d, float* root_box) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const Box3 b = ref_box(d, d.root_ref);
+  root_box[0] = b.lo.x, root_box[1] = b.lo.y, root_box[2] = b.lo.z;
+  root_box[3] = b.hi.x, root_box[4] = b.hi.y, root_box[5] = b.hi.z;
+}
+
+hipError_t enqueue_scene_update(const DScene& d, const SceneUpdate& u, hipStream_t st) {
+  constexpr uint32_t kBlock = 256;
+  auto blocks = [](uint32_t n) { return dim3((n + kBlock - 1) / kBlock); };
+  if (u.vertices && u.num_tris)
+    hipLaunchKernelGGL(scene_update_tris, blocks(u.num_tris), dim3(kBlock), 0, st, d, u.vertices, u.num_tris);
+  if (u.spheres && u.num_spheres)
+    hipLaunchKernelGGL(scene_update_spheres, blocks(u.num_spheres), dim3(kBlock), 0, st, d, u.spheres, u.num_spheres);
+  // the slots read the triangle records and spheres written above, the lights too, the refit the slots
+  hipLaunchKernelGGL(scene_update_leaves, blocks(u.num_slots), dim3(kBlock), 0, st, d, u.num_slots);
+  if (d.num_lights) hipLaunchKernelGGL(scene_update_lights, blocks(d.num_lights), dim3(kBlock), 0, st, d);
+  if (u.n_chain)
+    hipLaunchKernelGGL(scene_refit_chains, blocks(u.n_chain), dim3(kBlock), 0, st, d, u.chain_leaf, u.n_internal, u.n_chain);
+  for (uint32_t k = u.num_levels; k-- > 0;) {
+    const uint32_t begin = u.level_begin[k], end = u.level_begin[k + 1];
+    hipLaunchKernelGGL(scene_refit_level, blocks(end - begin), dim3(kBlock), 0, st, d, begin, end);
+  }
+  hipLaunchKernelGGL(scene_refit_root, dim3(1), dim3(64), 0, st, d, u.root_box);
+  return hipGetLastError();
+}
+
+}  // namespace vimg

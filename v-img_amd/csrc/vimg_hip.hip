@@ -23,6 +23,7 @@
 #include "render_pool4_kernel.h"
 #include "render_cu_kernel.h"
 #include "heatmap_kernel.h"
+#include "scene_update.h"
 
 using namespace vimg;
 
@@ -83,6 +84,15 @@ struct VimgDeviceScene {
   size_t stage_pix_state_bytes = 0;
   void* d_stage_slots = nullptr;
   size_t stage_slots_bytes = 0;
+  // geometry updates (vimg_hip_scene_update_geometry): what the upload knew of the tables and the tree
+  uint64_t generation = 0;       // bumped by every change of the resident scene; accumulators remember theirs
+  uint32_t num_vertices = 0, num_tris = 0, num_spheres = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> normal_rows;   // (first vertex, count) of the meshes with normals, merged
+  uint32_t n_internal = 0;       // DNode records of the tree; the n_chain chain records follow them
+  uint32_t n_chain = 0;
+  const uint32_t* d_chain_leaf = nullptr;   // per chain record {first slot, count} of its whole leaf
+  std::vector<uint32_t> level_begin;        // breadth-first levels of the internal nodes: [level_begin[k], level_begin[k+1])
+  float* d_root_box = nullptr;              // 6 floats the refit leaves the root's box in
 };
 
 // A frame rendered in increments (vimg_hip_progressive_*): its scene, its parameters and the pixel records.
@@ -95,6 +105,7 @@ struct VimgProgressive {
   uint32_t samples = 0;           // samples per pixel so far
   void* d_scratch = nullptr;      // the means of increments asked for without an output buffer
   size_t scratch_bytes = 0;
+  uint64_t generation = 0;        // the scene's generation its records were made in
 };
 
 namespace {
@@ -959,6 +970,30 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
   return VIMG_OK;
 }
 
+// ---- camera: TLCam ctor (reference src/tl_camera.cpp:6-23) and the primary ray cone
+// (include/ray.h:44-48) are per-render constants, evaluated here with the expressions the
+// reference uses (tan is an unqualified call there: double).  The upload and
+// vimg_hip_scene_set_camera both bake through this.
+void bake_camera(const VimgCamera& cam, DScene& d) {
+  std::memcpy(d.cam_to_world, cam.cam_to_world, sizeof(d.cam_to_world));
+  {
+    float theta = (cam.vfov_deg * std::numbers::pi) / 180.0;
+    float ratio = static_cast<float>(cam.res_x) / cam.res_y;
+    float img_height = 2.0f * (::tan(static_cast<double>(theta / 2.0f)));
+    d.p_size0 = ratio * img_height;
+    d.p_size1 = img_height;
+    float vfov = (cam.vfov_deg * std::numbers::pi) / 180.f;
+    // std::atan / std::tan of floats, evaluated in double and rounded once (DESIGN.md Numerics)
+    float t = static_cast<float>(::tan(static_cast<double>(vfov / 2.f)));
+    d.cone_spread = static_cast<float>(
+        ::atan(static_cast<double>(2.f * t / static_cast<float>(static_cast<uint32_t>(cam.res_y)))));
+  }
+  d.aperture_radius = cam.aperture_radius;
+  d.focal_dist = cam.focal_dist;
+  d.res_x = cam.res_x;
+  d.res_y = cam.res_y;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1007,27 +1042,8 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
   };
   DScene& d = s->d;
 
-  // ---- camera: TLCam ctor (reference src/tl_camera.cpp:6-23) and the primary ray cone
-  // (include/ray.h:44-48) are per-render constants, evaluated here with the expressions the
-  // reference uses (tan is an unqualified call there: double)
   const VimgCamera& cam = sc->camera;
-  std::memcpy(d.cam_to_world, cam.cam_to_world, sizeof(d.cam_to_world));
-  {
-    float theta = (cam.vfov_deg * std::numbers::pi) / 180.0;
-    float ratio = static_cast<float>(cam.res_x) / cam.res_y;
-    float img_height = 2.0f * (::tan(static_cast<double>(theta / 2.0f)));
-    d.p_size0 = ratio * img_height;
-    d.p_size1 = img_height;
-    float vfov = (cam.vfov_deg * std::numbers::pi) / 180.f;
-    // std::atan / std::tan of floats, evaluated in double and rounded once (DESIGN.md Numerics)
-    float t = static_cast<float>(::tan(static_cast<double>(vfov / 2.f)));
-    d.cone_spread = static_cast<float>(
-        ::atan(static_cast<double>(2.f * t / static_cast<float>(static_cast<uint32_t>(cam.res_y)))));
-  }
-  d.aperture_radius = cam.aperture_radius;
-  d.focal_dist = cam.focal_dist;
-  d.res_x = cam.res_x;
-  d.res_y = cam.res_y;
+  bake_camera(cam, d);
 
   // ---- BVH: only internal nodes get a record; they are renumbered breadth-first (root = 0) so
   // that the lowest indices are the top of the tree — the part staged into LDS.  Traversal order
@@ -1042,6 +1058,7 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
   // reaches holds no hit the reference could have accepted (its entry distance exceeds maxT).
   // Images are identical; the event counts gain the chain's node visits.
   std::vector<DNode> extra;          // chain records, appended behind the tree's own
+  std::vector<uint32_t> extra_leaf;  // per chain record: first slot and count of its whole leaf (for a refit)
   uint32_t extra_depth = 0;
   size_t n_internal = 0;             // set below, before the first chain is made
   auto leaf_ref = [&](const VimgBVHNode& n, const float* bmin, const float* bmax, uint32_t& out) {
@@ -1066,6 +1083,8 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
       dn.left_ref = rest;
       dn.right_ref = (chunks[i].second << 25) | chunks[i].first;
       extra.push_back(dn);
+      extra_leaf.push_back(n.first_index);
+      extra_leaf.push_back(n.obj_count);
       rest = static_cast<uint32_t>(n_internal + extra.size() - 1);
       ++links;
     }
@@ -1075,16 +1094,22 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
   };
   std::vector<uint32_t> order;   // internal nodes: new index -> old index
   std::vector<uint32_t> new_of(b.num_nodes, 0);
-  if (b.nodes[0].obj_count == 0) order.push_back(0);
+  std::vector<uint32_t> level;   // internal nodes: new index -> depth below the root
+  if (b.nodes[0].obj_count == 0) order.push_back(0), level.push_back(0);
   for (size_t head = 0; head < order.size(); ++head) {
     const VimgBVHNode& n = b.nodes[order[head]];
     for (uint32_t c = n.first_index; c <= n.first_index + 1; ++c)
       if (b.nodes[c].obj_count == 0) {
         new_of[c] = static_cast<uint32_t>(order.size());
         order.push_back(c);
+        level.push_back(level[head] + 1);
       }
   }
   n_internal = order.size();
+  // breadth-first numbering makes every level one index range: a refit runs them deepest first
+  for (size_t i = 0; i < order.size(); ++i)
+    if (i == 0 || level[i] != level[i - 1]) s->level_begin.push_back(static_cast<uint32_t>(i));
+  s->level_begin.push_back(static_cast<uint32_t>(n_internal));
   std::vector<DNode> nodes(order.size());
   for (size_t i = 0; i < order.size(); ++i) {
     const VimgBVHNode& n = b.nodes[order[i]];
@@ -1119,6 +1144,8 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
     d.root_max[a] = b.bb_mins_maxes[2 * 3 + a];
   }
   d.num_nodes = static_cast<uint32_t>(nodes.size());
+  s->n_internal = static_cast<uint32_t>(n_internal);
+  s->n_chain = static_cast<uint32_t>(extra.size());
   if (b.max_depth + extra_depth + 2 > 96) return bail(fail(VIMG_E_INVALID, "BVH (with its leaf chains) deeper than the 94-level stack bound"));
   d.max_depth = b.max_depth + extra_depth;   // a chain link pushes one entry like any internal node
 
@@ -1262,6 +1289,26 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
   UP(dlights, dlights.data(), dlights.size());
   UP(cdf_pool, sc->cdf_pool, sc->num_cdf);
 #undef UP
+  if (!extra_leaf.empty()) {   // (refit bookkeeping: not counted in the scene's bytes)
+    void* p = nullptr;
+    if (hipMalloc(&p, extra_leaf.size() * sizeof(uint32_t)) != hipSuccess) return bail(fail(VIMG_E_DEVICE, "hipMalloc failed"));
+    s->allocs.push_back(p);
+    if (hipMemcpy(p, extra_leaf.data(), extra_leaf.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+      return bail(fail(VIMG_E_DEVICE, "hipMemcpy failed"));
+    s->d_chain_leaf = static_cast<const uint32_t*>(p);
+  }
+  s->num_vertices = sc->num_vertices;
+  s->num_tris = sc->num_tris;
+  s->num_spheres = sc->num_spheres;
+  for (uint32_t i = 0; i < sc->num_meshes; ++i) {
+    const VimgMesh& m = sc->meshes[i];
+    if (!m.has_normals || m.num_vertices == 0) continue;
+    auto& r = s->normal_rows;
+    if (!r.empty() && r.back().first + r.back().second == m.first_vertex)
+      r.back().second += m.num_vertices;
+    else
+      r.push_back({m.first_vertex, m.num_vertices});
+  }
   d.num_lights = sc->num_lights;
   d.background = sc->background;
   // Background::is_emissive (reference include/background.h:51-56,176)
@@ -1291,7 +1338,8 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
   if (hipGetDeviceProperties(&prop, g_device) != hipSuccess) return bail(fail(VIMG_E_DEVICE, "hipGetDeviceProperties failed"));
   s->num_cus = static_cast<uint32_t>(prop.multiProcessorCount);
   if (hipMalloc(reinterpret_cast<void**>(&s->d_stats), sizeof(DeviceStats)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->d_counter), 2 * sizeof(unsigned int)) != hipSuccess)
+      hipMalloc(reinterpret_cast<void**>(&s->d_counter), 2 * sizeof(unsigned int)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&s->d_root_box), 6 * sizeof(float)) != hipSuccess)
     return bail(fail(VIMG_E_DEVICE, "hipMalloc of scratch failed"));
   if (hipMemset(s->d_counter, 0, 2 * sizeof(unsigned int)) != hipSuccess) return bail(fail(VIMG_E_DEVICE, "hipMemset of scratch failed"));
   *out = s;
@@ -1303,6 +1351,7 @@ int vimg_hip_scene_free(VimgDeviceScene* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   if (s->d_stats) (void)hipFree(s->d_stats);
   if (s->d_counter) (void)hipFree(s->d_counter);
+  if (s->d_root_box) (void)hipFree(s->d_root_box);
   if (s->d_frame) (void)hipFree(s->d_frame);
   if (s->d_pool_cold) (void)hipFree(s->d_pool_cold);
   if (s->d_stack_ovf) (void)hipFree(s->d_stack_ovf);
@@ -1310,6 +1359,47 @@ int vimg_hip_scene_free(VimgDeviceScene* s) {
   for (void* q : {s->d_stage_ctl, s->d_stage_kargs, s->d_stage_rings, s->d_stage_pix_ring, s->d_stage_pix_state, s->d_stage_slots})
     if (q) (void)hipFree(q);
   delete s;
+  return VIMG_OK;
+}
+
+// ---- changes of a resident scene.  Argument errors are found before anything is enqueued, so
+// they leave the scene as it was; a change that passes them bumps the scene's generation, which a progressive
+// accumulator compares before its next increment.
+int vimg_hip_scene_update_geometry(VimgDeviceScene* s, const VimgGeometryUpdate* u, void* stream) {
+  if (!s || !u) return fail(VIMG_E_INVALID, "update_geometry: null scene or update");
+  if (u->struct_size < sizeof(VimgGeometryUpdate)) return fail(VIMG_E_INVALID, "update_geometry: struct_size too small");
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  ++s->generation;
+  if (u->normals)   // rows of meshes without normals keep what the upload gave them
+    for (const auto& r : s->normal_rows)
+      HIP_TRY(hipMemcpyAsync((float*)s->d.normals + size_t(r.first) * 3, static_cast<const float*>(u->normals) + size_t(r.first) * 3,
+                             size_t(r.second) * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  SceneUpdate up{};
+  up.vertices = static_cast<const float*>(u->vertices);
+  up.spheres = static_cast<const float*>(u->spheres);
+  up.num_tris = s->num_tris;
+  up.num_spheres = s->num_spheres;
+  up.num_slots = s->num_leaf_prims;
+  up.n_internal = s->n_internal;
+  up.n_chain = s->n_chain;
+  up.chain_leaf = s->d_chain_leaf;
+  up.level_begin = s->level_begin.data();
+  up.num_levels = static_cast<uint32_t>(s->level_begin.size() - 1);
+  up.root_box = s->d_root_box;
+  HIP_TRY(enqueue_scene_update(s->d, up, st));
+  float box[6];
+  HIP_TRY(hipMemcpyAsync(box, s->d_root_box, sizeof(box), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int a = 0; a < 3; ++a) s->d.root_min[a] = box[a], s->d.root_max[a] = box[3 + a];
+  return VIMG_OK;
+}
+
+int vimg_hip_scene_set_camera(VimgDeviceScene* s, const VimgCamera* cam) {
+  if (!s || !cam) return fail(VIMG_E_INVALID, "set_camera: null scene or camera");
+  if (cam->res_x != s->d.res_x || cam->res_y != s->d.res_y)
+    return fail(VIMG_E_INVALID, "set_camera: the resolution is fixed at upload");
+  bake_camera(*cam, s->d);
+  ++s->generation;
   return VIMG_OK;
 }
 
@@ -1399,6 +1489,7 @@ int vimg_hip_progressive_create(VimgDeviceScene* s, const VimgRenderParams* p, V
                                     "development build do not resume pixels across launches");
   VimgProgressive* a = new VimgProgressive{};
   a->scene = s;
+  a->generation = s->generation;
   a->params = q;
   a->items = uint64_t(local_tiles(s, &q)) * 64u;
   const size_t bytes = std::max<size_t>(a->items, 1) * 32u;
@@ -1416,6 +1507,9 @@ int vimg_hip_progressive_render(VimgDeviceScene* s, VimgProgressive* a, uint32_t
                                 VimgRenderStats* stats) {
   if (!s || !a) return fail(VIMG_E_INVALID, "progressive: null scene or accumulator");
   if (a->scene != s) return fail(VIMG_E_INVALID, "progressive: the accumulator belongs to another scene");
+  if (a->generation != s->generation)
+    return fail(VIMG_E_INVALID, "progressive: the scene changed (geometry or camera) since the accumulator's records "
+                                "were made; reset it");
   if (samples == 0) return fail(VIMG_E_INVALID, "samples must be > 0");
   if (uint64_t(a->samples) + samples > 0xffffffffull)
     return fail(VIMG_E_INVALID, "progressive: more than 2^32 - 1 samples per pixel in all (the reference counts them in 32 bits)");
@@ -1445,6 +1539,7 @@ uint64_t vimg_hip_progressive_samples(const VimgProgressive* a) { return a ? a->
 int vimg_hip_progressive_reset(VimgProgressive* a) {
   if (!a) return fail(VIMG_E_INVALID, "progressive: null accumulator");
   a->samples = 0;   // the next increment seeds every pixel again
+  a->generation = a->scene->generation;
   return VIMG_OK;
 }
 

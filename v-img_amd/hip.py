@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as abi
-from .host import HostScene, make_params
+from .host import HostScene, camera_lookat, make_params
 
 
 class HipError(RuntimeError):
@@ -81,6 +81,8 @@ class DeviceScene:
                                                     C.byref(h)))
         self._h = h
         self.resolution = host_scene.resolution
+        v = host_scene.view.contents
+        self.num_vertices, self.num_spheres = int(v.num_vertices), int(v.num_spheres)
 
     @property
     def bytes(self):
@@ -115,6 +117,54 @@ class DeviceScene:
             _check(self._lib.vimg_hip_render(self._h, C.byref(params), C.c_void_p(out.data_ptr()), sp,
                                              C.byref(st) if stats else None))
         return (out, st) if stats else out
+
+    def _device_table(self, a, rows, cols, what, keep):
+        """A float32 [rows, cols] table on this process's GPU: a CUDA tensor as it is, a numpy array copied up."""
+        import torch
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda or a.device.index != torch.cuda.current_device():
+                raise ValueError(f"{what}: the tensor must be on the current CUDA device, not {a.device}")
+            if a.dtype != torch.float32:
+                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
+            if not a.is_contiguous():
+                raise ValueError(f"{what}: the tensor must be contiguous")
+            t = a
+        elif isinstance(a, np.ndarray):
+            if a.dtype != np.float32:
+                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
+            t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda")   # (a blocking copy: done before the update reads it)
+        else:
+            raise ValueError(f"{what}: expected a torch CUDA tensor or a numpy array, not {type(a).__name__}")
+        if tuple(t.shape) != (rows, cols):
+            raise ValueError(f"{what}: shape must be ({rows}, {cols}), not {tuple(t.shape)}")
+        keep.append(t)
+        return C.c_void_p(t.data_ptr()) if t.numel() else None
+
+    def update_geometry(self, vertices=None, normals=None, spheres=None, stream=None):
+        """New positions for the resident scene (vimg_hip_scene_update_geometry): vertices and normals
+        [num_vertices, 3], spheres [num_spheres, 4] (centre, radius), float32; None = unchanged.  The records
+        baked from positions and the tree's boxes are rebuilt on the GPU; the call returns when the scene is
+        consistent.  Progressive accumulators of the scene must be reset afterwards."""
+        keep = []          # (the tensors stay alive until the blocking call returns)
+        upd = abi.GeometryUpdate()
+        if vertices is not None:
+            upd.vertices = self._device_table(vertices, self.num_vertices, 3, "vertices", keep)
+        if normals is not None:
+            upd.normals = self._device_table(normals, self.num_vertices, 3, "normals", keep)
+        if spheres is not None:
+            upd.spheres = self._device_table(spheres, self.num_spheres, 4, "spheres", keep)
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
+
+    def set_camera(self, look_from, look_at=None, up=None, vfov_deg=None, aperture_radius=0.0, focal_dist=1.0):
+        """A new camera at the scene's resolution (vimg_hip_scene_set_camera): look-at arguments as
+        HostScene.set_camera without the resolution, or an abi.Camera.  Progressive accumulators of the scene
+        must be reset afterwards."""
+        if isinstance(look_from, abi.Camera):
+            cam = look_from
+        else:
+            cam = camera_lookat(look_from, look_at, up, vfov_deg, self.resolution, aperture_radius, focal_dist)
+        _check(self._lib.vimg_hip_scene_set_camera(self._h, C.byref(cam)))
 
     def progressive(self, params):
         """An accumulator for this frame (or shard) rendered a few samples at a time (vimg_hip_progressive_*):

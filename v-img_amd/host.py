@@ -142,6 +142,42 @@ class HostScene:
     def build_bvh(self, kind=abi.BVH_SWEEP):
         self._check(self._lib.vimg_host_build_bvh(self._h, kind))
 
+    # ---- new positions in the same topology (DeviceScene.update_geometry on the host) -----------
+    def _table(self, a, rows, cols, what):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size != rows * cols:
+            raise HostError(f"{what}: expected {rows} x {cols} floats, got shape {a.shape}")
+        return a
+
+    def set_vertices(self, xyz, normals=None):
+        """The whole vertex table (num_vertices x 3, VimgScene order) and optionally the normals (the same
+        shape; only rows of meshes with normals are taken).  The tree keeps its boxes until refit_bvh()."""
+        n = self.view.contents.num_vertices
+        v = self._table(xyz, n, 3, "set_vertices")
+        nr = self._table(normals, n, 3, "set_vertices normals") if normals is not None else None
+        self._check(self._lib.vimg_host_set_vertices(self._h, _fp(v), _fp(nr) if nr is not None else None))
+
+    def set_spheres(self, centre_radius):
+        """num_spheres x 4: centre xyz, radius (materials stay)."""
+        n = self.view.contents.num_spheres
+        sp = self._table(centre_radius, n, 4, "set_spheres")
+        self._check(self._lib.vimg_host_set_spheres(self._h, _fp(sp)))
+
+    def refit_bvh(self):
+        """The tree's boxes recomputed from the current positions, topology unchanged."""
+        self._check(self._lib.vimg_host_refit_bvh(self._h))
+        return self
+
+    def geometry(self):
+        """Copies of (vertices [V, 3], normals [V, 3], spheres [S, 4] = centre, radius)."""
+        v = self.view.contents
+        nv, ns = v.num_vertices, v.num_spheres
+        verts = np.ctypeslib.as_array(v.vertices, (nv, 3)).copy() if nv else np.zeros((0, 3), np.float32)
+        nrm = np.ctypeslib.as_array(v.normals, (nv, 3)).copy() if nv else np.zeros((0, 3), np.float32)
+        sph = np.array([list(v.spheres[i].center) + [v.spheres[i].radius] for i in range(ns)],
+                       dtype=np.float32).reshape(ns, 4)
+        return verts, nrm, sph
+
     def build_bvh_with(self, builder_fn_ptr):
         """Build the BVH with a caller-supplied builder (a C function pointer with the
         vimg_bvh_builder_fn signature, e.g. vimg_amd.hip.lbvh_builder())."""
@@ -184,6 +220,15 @@ class HostScene:
             self.close()
         except Exception:
             pass
+
+
+def camera_lookat(look_from, look_at, up, vfov_deg, res, aperture_radius=0.0, focal_dist=1.0):
+    """The abi.Camera HostScene.set_camera stores for the same arguments."""
+    f, a, u = _f32(look_from), _f32(look_at), _f32(up)
+    cam = abi.Camera()
+    abi.host_lib().vimg_host_camera_lookat(_fp(f), _fp(a), _fp(u), vfov_deg, int(res[0]), int(res[1]),
+                                           aperture_radius, focal_dist, C.byref(cam))
+    return cam
 
 
 def make_params(base=None, integrator=None, samples=None, depth=None, tile_rank=None,

@@ -395,3 +395,33 @@ HostBVH build_bin_bvh(const std::vector<PrimBounds>& bboxes, const std::vector<V
   bvh.bb.resize((ctx.next_node * 2 + 3) * 3);
   return bvh;
 }
+
+// Same topology, new boxes: the primitive bounds of prim_bounds, folded as the builders fold them - a
+// leaf over its primitives in obj_indices order from the first, an internal node as grow(left, right) -
+// children before parents (reverse breadth-first order, whatever the numbering).  Triple 1 of bb (no
+// node's box) is left alone.
+void refit_bvh(const std::vector<PrimBounds>& bboxes, HostBVH& bvh) {
+  const size_t n = bvh.nodes.size();
+  std::vector<Box> box(n);
+  std::vector<uint32_t> order{0};
+  for (size_t head = 0; head < order.size(); ++head) {
+    const VimgBVHNode& node = bvh.nodes[order[head]];
+    if (node.obj_count == 0) order.push_back(node.first_index), order.push_back(node.first_index + 1);
+  }
+  for (size_t k = order.size(); k-- > 0;) {
+    const uint32_t i = order[k];
+    const VimgBVHNode& node = bvh.nodes[i];
+    if (node.obj_count) {
+      box[i] = box_of(bboxes[bvh.obj_indices[node.first_index]]);
+      for (uint32_t j = 1; j < node.obj_count; ++j) box[i].grow(bboxes[bvh.obj_indices[node.first_index + j]]);
+    } else {
+      box[i] = box[node.first_index];
+      box[i].grow(box[node.first_index + 1]);
+      store_child_boxes(bvh, node.first_index, box[node.first_index], box[node.first_index + 1]);
+    }
+  }
+  for (int a = 0; a < 3; ++a) {
+    bvh.bb[0 * 3 + a] = box[0].lo[a];
+    bvh.bb[2 * 3 + a] = box[0].hi[a];
+  }
+}

@@ -476,17 +476,23 @@ VimgHostScene* vimg_host_scene_new(void) {
 
 void vimg_host_scene_free(VimgHostScene* s) { delete s; }
 
+void vimg_host_camera_lookat(const float from[3], const float at[3], const float up[3], float vfov_deg,
+                             int res_x, int res_y, float aperture_radius, float focal_dist, VimgCamera* out) {
+  mat_to_array(hm::cam_to_world(V3{from[0], from[1], from[2]}, V3{at[0], at[1], at[2]},
+                                V3{up[0], up[1], up[2]}),
+               out->cam_to_world);
+  out->vfov_deg = vfov_deg;
+  out->res_x = res_x;
+  out->res_y = res_y;
+  out->aperture_radius = aperture_radius;
+  out->focal_dist = focal_dist;
+}
+
 void vimg_host_set_camera_lookat(VimgHostScene* s, const float from[3], const float at[3],
                                  const float up[3], float vfov_deg, int res_x, int res_y,
                                  float aperture_radius, float focal_dist) {
-  mat_to_array(hm::cam_to_world(V3{from[0], from[1], from[2]}, V3{at[0], at[1], at[2]},
-                                V3{up[0], up[1], up[2]}),
-               s->camera.cam_to_world);
-  s->camera.vfov_deg = vfov_deg;
-  s->camera.res_x = res_x;
-  s->camera.res_y = res_y;
-  s->camera.aperture_radius = aperture_radius;
-  s->camera.focal_dist = focal_dist;
+  vimg_host_camera_lookat(from, at, up, vfov_deg, res_x, res_y, aperture_radius, focal_dist, &s->camera);
+  s->view.camera = s->camera;
 }
 
 void vimg_host_set_render_defaults(VimgHostScene* s, uint32_t integrator, uint32_t samples,
@@ -664,6 +670,45 @@ int vimg_host_build_bvh_with(VimgHostScene* s, vimg_bvh_builder_fn builder) {
   s->bvh = std::move(bvh);
   s->bvh_built = true;
   s->refresh_view();
+  return 0;
+}
+
+// ---- new positions in the same topology (the host counterpart of vimg_hip_scene_update_geometry)
+int vimg_host_set_vertices(VimgHostScene* s, const float* xyz, const float* normals) {
+  if (!s || !xyz) {
+    host_set_error("set_vertices: null scene or vertices");
+    return -1;
+  }
+  std::memcpy(s->vertices.data(), xyz, s->vertices.size() * sizeof(float));
+  if (normals)   // only meshes with normals have rows that are read
+    for (const VimgMesh& m : s->meshes)
+      if (m.has_normals)
+        std::memcpy(s->normals.data() + size_t(m.first_vertex) * 3, normals + size_t(m.first_vertex) * 3,
+                    size_t(m.num_vertices) * 3 * sizeof(float));
+  return 0;
+}
+
+int vimg_host_set_spheres(VimgHostScene* s, const float* centre_radius) {
+  if (!s || !centre_radius) {
+    host_set_error("set_spheres: null scene or spheres");
+    return -1;
+  }
+  for (size_t i = 0; i < s->spheres.size(); ++i) {
+    for (int a = 0; a < 3; ++a) s->spheres[i].center[a] = centre_radius[i * 4 + a];
+    s->spheres[i].radius = centre_radius[i * 4 + 3];
+  }
+  return 0;
+}
+
+int vimg_host_refit_bvh(VimgHostScene* s) {
+  if (!s || !s->bvh_built) {
+    host_set_error("refit_bvh: the scene has no BVH to refit");
+    return -1;
+  }
+  std::vector<PrimBounds> bounds;
+  std::vector<V3> centers;
+  prim_bounds(*s, bounds, centers);
+  refit_bvh(bounds, s->bvh);
   return 0;
 }
 

@@ -48,6 +48,7 @@ HostBVH build_sweep_bvh(const std::vector<PrimBounds>& bboxes, const std::vector
                         uint32_t max_node_prims);
 HostBVH build_bin_bvh(const std::vector<PrimBounds>& bboxes, const std::vector<hm::V3>& centers,
                       size_t num_bins);
+void refit_bvh(const std::vector<PrimBounds>& bboxes, HostBVH& bvh);
 
 // texture_build.cpp
 bool build_mip_chain(uint32_t w, uint32_t h, const float* level0, uint32_t wrap_u, uint32_t wrap_v,
