@@ -120,6 +120,35 @@ typedef struct VimgGeometryUpdate {
 int vimg_hip_scene_update_geometry(VimgDeviceScene* scene, const VimgGeometryUpdate* update, void* stream);
 int vimg_hip_scene_set_camera(VimgDeviceScene* scene, const VimgCamera* camera);
 
+/* Ray queries on a resident scene: the render's own walk on rays the caller gives.
+ *  _trace_rays  : closest hit, exactly what the render's walk (traverse<false>: the same slab, triangle and
+ *      sphere expressions, the same tie rule) computes for a ray with that [t_min, t_max].  d_hits: n VimgRayHit
+ *      - t the hit distance, prim an index into VimgScene.prims, b1 b2 the weights of a triangle's 2nd and 3rd
+ *      vertex (e1 * inv_det, e2 * inv_det as tri_hit_info forms them; 0 for spheres).  A miss writes t = +inf,
+ *      prim = VIMG_NO_HIT, b1 = b2 = 0.  d_info (may be NULL): n VimgHitInfo, the hit's full record
+ *      (make_hit_info<true>, what the parity probe returns): position, shading and geometric normal, uv,
+ *      material; zeros for a miss.
+ *  _occluded    : the render's shadow test (traverse<true>) over [t_min, t_max]: d_flags[i] = 1 when anything
+ *      is hit, else 0.
+ *  _camera_rays : the camera's generate_ray (as the render and the image use it; the one _set_camera sets) for
+ *      n samples {x, y, lens_u, lens_v} of float32 (pixel coordinates, lens samples in [0, 1)): n VimgRay with
+ *      t_min = 0.0001f, t_max = +inf.  Picking = _camera_rays, then _trace_rays.
+ * All three only enqueue on `stream` (NULL = the library's stream): no allocation, no host wait.  They read the
+ * scene and nothing else (none of its render scratch), so they may sit between renders and progressive
+ * increments without changing those results or the scene's generation; a call after _update_geometry returns
+ * sees the new geometry.  Buffers are DEVICE pointers, 16-byte aligned (d_flags: any alignment).  n == 0 does
+ * nothing; n >= 2^32, a NULL scene, a NULL buffer with n > 0 or a misaligned buffer are VIMG_E_INVALID, found
+ * before anything is enqueued (also without a GPU).  A ray with t_min > t_max or a NaN in its range is a miss,
+ * not an error. */
+typedef struct VimgRay { float org[3]; float t_min; float dir[3]; float t_max; } VimgRay;             /* 32 B */
+typedef struct VimgRayHit { float t; uint32_t prim; float b1, b2; } VimgRayHit;                       /* 16 B */
+typedef struct VimgHitInfo { float p[3]; float ns[3]; float ng[3]; float uv[2]; uint32_t mat; } VimgHitInfo;   /* 48 B */
+#define VIMG_NO_HIT 0xffffffffu
+int vimg_hip_trace_rays(VimgDeviceScene* scene, const void* d_rays, uint64_t n, void* d_hits, void* d_info,
+                        void* stream);
+int vimg_hip_occluded(VimgDeviceScene* scene, const void* d_rays, uint64_t n, uint8_t* d_flags, void* stream);
+int vimg_hip_camera_rays(VimgDeviceScene* scene, const void* d_samples, uint64_t n, void* d_rays, void* stream);
+
 /* Number of float triples a shard's compact framebuffer holds
  * (= 64 * number of 8x8 tiles owned by tile_rank). */
 int64_t vimg_hip_shard_pixels(const VimgDeviceScene* scene, const VimgRenderParams* params);

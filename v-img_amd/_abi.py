@@ -132,6 +132,23 @@ class GeometryUpdate(C.Structure):
         self.struct_size = C.sizeof(GeometryUpdate)
 
 
+class Ray(C.Structure):
+    """VimgRay (include/vimg_hip.h): one query ray, 32 B."""
+    _fields_ = [("org", f32 * 3), ("t_min", f32), ("dir", f32 * 3), ("t_max", f32)]
+
+
+class RayHit(C.Structure):
+    """VimgRayHit: closest hit of one ray, 16 B; prim == NO_HIT for a miss."""
+    _fields_ = [("t", f32), ("prim", u32), ("b1", f32), ("b2", f32)]
+
+
+class HitInfo(C.Structure):
+    """VimgHitInfo: the hit's record, 48 B."""
+    _fields_ = [("p", f32 * 3), ("ns", f32 * 3), ("ng", f32 * 3), ("uv", f32 * 2), ("mat", u32)]
+
+
+NO_HIT = 0xFFFFFFFF
+
 OPT_AUTO = -1
 SCHED_LANE, SCHED_POOL, SCHED_STAGE, SCHED_POOL4, SCHED_POOL4G, SCHED_CU = 1, 2, 3, 4, 5, 6
 SCHEDULERS = {"lane": SCHED_LANE, "pool": SCHED_POOL, "stage": SCHED_STAGE, "pool4": SCHED_POOL4, "pool4g": SCHED_POOL4G, "cu": SCHED_CU}
@@ -214,6 +231,9 @@ HIP_SYMBOLS = {
     "vimg_hip_scene_free": (C.c_int, [C.c_void_p]),
     "vimg_hip_scene_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]),
     "vimg_hip_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
+    "vimg_hip_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_hip_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "vimg_hip_camera_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vimg_hip_shard_pixels": (i64, [C.c_void_p, PParams]),
     "vimg_hip_render": (C.c_int, [C.c_void_p, PParams, C.c_void_p, C.c_void_p, PStats]),
     "vimg_hip_render_async": (C.c_int, [C.c_void_p, PParams, C.c_void_p, C.c_void_p]),

@@ -166,6 +166,122 @@ class DeviceScene:
             cam = camera_lookat(look_from, look_at, up, vfov_deg, self.resolution, aperture_radius, focal_dist)
         _check(self._lib.vimg_hip_scene_set_camera(self._h, C.byref(cam)))
 
+    # ---- ray queries (vimg_hip_trace_rays, _occluded, _camera_rays) ----------------------------------
+    def _query_input(self, a, cols, what):
+        """(device tensor [N, cols] float32, came from numpy): a CUDA tensor on the current device as it is, a numpy
+        array copied up; both 16-byte aligned."""
+        import torch
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda or a.device.index != torch.cuda.current_device():
+                raise ValueError(f"{what}: the tensor must be on the current CUDA device, not {a.device}")
+            if a.dtype != torch.float32:
+                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
+            if not a.is_contiguous():
+                raise ValueError(f"{what}: the tensor must be contiguous")
+            t, host = a, False
+        elif isinstance(a, np.ndarray):
+            if a.dtype != np.float32:
+                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
+            t, host = torch.from_numpy(np.ascontiguousarray(a)).to("cuda"), True
+        else:
+            raise ValueError(f"{what}: expected a torch CUDA tensor or a numpy array, not {type(a).__name__}")
+        if t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError(f"{what}: shape must be (N, {cols}), not {tuple(t.shape)}")
+        if t.numel() and t.data_ptr() % 16:
+            raise ValueError(f"{what}: the tensor's data must be 16-byte aligned")
+        return t, host
+
+    @staticmethod
+    def _query_output(out, n, cols, dtype, what):
+        import torch
+        if out is None:
+            return torch.empty((n, cols) if cols else (n,), dtype=dtype, device="cuda")
+        shape = (n, cols) if cols else (n,)
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != torch.cuda.current_device()
+                or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"{what}: out must be a contiguous {dtype} CUDA tensor of shape {shape} on the current device")
+        if n and cols and out.data_ptr() % 16:
+            raise ValueError(f"{what}: out must be 16-byte aligned")
+        return out
+
+    @staticmethod
+    def _query_stream(stream):
+        """The _Ordered of a query launch.  Its outputs, and the copies of numpy inputs, were made on torch's current
+        stream: a launch on another stream first waits for the current one, so that it neither reads a copy not yet
+        made nor writes memory the caching allocator handed out while current-stream work on it is still pending."""
+        import torch
+        ordered = _Ordered(stream)
+        cur = torch.cuda.current_stream()
+        if ordered.side is None and ordered.cur.cuda_stream != cur.cuda_stream:
+            ordered.cur.wait_stream(cur)
+        return ordered
+
+    @staticmethod
+    def _after_query(ordered, tensors, host):
+        """A launch on another stream than torch's current one reads and writes its tensors asynchronously: the
+        caching allocator must not hand their memory out again before that stream has passed the launch.  Results
+        that go back to numpy wait for the launch first."""
+        import torch
+        used = ordered.side if ordered.side is not None else ordered.cur
+        if used.cuda_stream != torch.cuda.current_stream().cuda_stream:
+            for t in tensors:
+                if t is not None and t.numel():
+                    t.record_stream(used)
+            if host:
+                torch.cuda.current_stream().wait_stream(used)
+
+    def trace_rays(self, rays, info=False, out=None, stream=None):
+        """Closest hits of ``rays`` ([N, 8] float32 laid out as VimgRay: org xyz, t_min, dir xyz, t_max) against the
+        resident scene (vimg_hip_trace_rays): a RayHits with t [N] (+inf for a miss), prim [N] int32 (-1 for a
+        miss), bary [N, 2] (weights of a triangle's 2nd and 3rd vertex), and with ``info`` also p, ns, ng [N, 3],
+        uv [N, 2], mat [N] int32.  A CUDA tensor is used as it is and the results are views of device buffers,
+        ordered on ``stream`` (torch's current one by default); a numpy array is copied up and numpy arrays come
+        back.  ``out``: the [N, 4] float32 hit buffer, or (hits, [N, 12] info buffer) with ``info``."""
+        import torch
+        r, host = self._query_input(rays, 8, "rays")
+        n = r.shape[0]
+        hits_out, info_out = (out if info and out is not None else (out, None))
+        hits = self._query_output(hits_out, n, 4, torch.float32, "trace_rays")
+        rec = self._query_output(info_out, n, 12, torch.float32, "trace_rays info") if info else None
+        ordered = self._query_stream(stream)
+        with ordered as sp:
+            _check(self._lib.vimg_hip_trace_rays(self._h, C.c_void_p(r.data_ptr()) if n else None, n,
+                                                 C.c_void_p(hits.data_ptr()) if n else None,
+                                                 C.c_void_p(rec.data_ptr()) if rec is not None and n else None, sp))
+        self._after_query(ordered, (r, hits, rec), host)
+        return RayHits.of(hits, rec, host)
+
+    def occluded(self, rays, out=None, stream=None):
+        """The render's shadow test on ``rays`` ([N, 8] float32, VimgRay; vimg_hip_occluded): bool [N], True when
+        anything lies in [t_min, t_max].  CUDA tensor in, CUDA tensor out (a view of ``out``, [N] uint8, when
+        given); numpy in, numpy out."""
+        import torch
+        r, host = self._query_input(rays, 8, "rays")
+        n = r.shape[0]
+        flags = self._query_output(out, n, 0, torch.uint8, "occluded")
+        ordered = self._query_stream(stream)
+        with ordered as sp:
+            _check(self._lib.vimg_hip_occluded(self._h, C.c_void_p(r.data_ptr()) if n else None, n,
+                                               C.c_void_p(flags.data_ptr()) if n else None, sp))
+        self._after_query(ordered, (r, flags), host)
+        res = flags.view(torch.bool)
+        return res.cpu().numpy() if host else res
+
+    def camera_rays(self, samples, out=None, stream=None):
+        """The camera's rays (vimg_hip_camera_rays) for ``samples`` [N, 4] float32 {x, y, lens_u, lens_v} (pixel
+        coordinates, lens samples): [N, 8] float32 VimgRay records with t_min 1e-4 and t_max +inf - the input of
+        trace_rays for picking.  CUDA tensor in, CUDA tensor out; numpy in, numpy out."""
+        import torch
+        smp, host = self._query_input(samples, 4, "samples")
+        n = smp.shape[0]
+        rays = self._query_output(out, n, 8, torch.float32, "camera_rays")
+        ordered = self._query_stream(stream)
+        with ordered as sp:
+            _check(self._lib.vimg_hip_camera_rays(self._h, C.c_void_p(smp.data_ptr()) if n else None, n,
+                                                  C.c_void_p(rays.data_ptr()) if n else None, sp))
+        self._after_query(ordered, (smp, rays), host)
+        return rays.cpu().numpy() if host else rays
+
     def progressive(self, params):
         """An accumulator for this frame (or shard) rendered a few samples at a time (vimg_hip_progressive_*):
         after increments n_1 .. n_k the image is bit for bit ``render`` at n_1 + .. + n_k samples.
@@ -256,6 +372,33 @@ class DeviceScene:
             pass
 
 
+class RayHits:
+    """Result of DeviceScene.trace_rays: t [N], prim [N] int32 (-1 = miss), bary [N, 2]; with info also p, ns, ng
+    [N, 3], uv [N, 2], mat [N] int32 (zeros for a miss).  Views of the device buffers (torch) or numpy arrays."""
+    FIELDS = ("t", "prim", "bary", "p", "ns", "ng", "uv", "mat")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    @classmethod
+    def of(cls, hits, info, host):
+        import torch
+        if host:
+            hits = hits.cpu().numpy()
+            info = None if info is None else info.cpu().numpy()
+            as_i32 = lambda a: a.view(np.int32)
+        else:
+            as_i32 = lambda a: a.view(torch.int32)
+        f = dict(t=hits[:, 0], prim=as_i32(hits)[:, 1], bary=hits[:, 2:4])
+        if info is not None:
+            f.update(p=info[:, 0:3], ns=info[:, 3:6], ng=info[:, 6:9], uv=info[:, 9:11], mat=as_i32(info)[:, 11])
+        return cls(**f)
+
+    def __repr__(self):
+        return f"RayHits(n={len(self.t)}, info={self.p is not None})"
+
+
 class Progressive:
     """A frame of one DeviceScene rendered in increments (DeviceScene.progressive).  Every call is ordered
     on torch's stream the way DeviceScene.render is."""
@@ -328,7 +471,7 @@ def post_rgb8(image, tonemapper=1, stream=None):
     return out
 
 
-__all__ = ["DeviceScene", "Progressive", "post_rgb8", "HipError", "device_count", "init", "make_params"]
+__all__ = ["DeviceScene", "Progressive", "RayHits", "post_rgb8", "HipError", "device_count", "init", "make_params"]
 
 
 # ---- the pre-step of the path on the GPU (include/vimg_hip.h) ----------
