@@ -32,8 +32,8 @@ $(LIBDIR)/libvimg_host.so: $(HOSTSRC) $(HOSTHDR) Makefile
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(HOSTFLAGS) $(HOSTSRC) -o $@
 
-# one object per translation unit (make -j compiles them side by side): the ABI unit, one unit per
-# render kernel family, the BVH builders
+# one object per translation unit (make -j compiles them side by side): the host units of the ABI, one
+# unit per render kernel family, the BVH builders
 HIPCFLAGS := $(filter-out -shared,$(HIPFLAGS)) -c
 OBJDIR    := build/hip
 HIPOBJ    := $(patsubst v-img_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
@@ -49,14 +49,12 @@ $(LIBDIR)/libvimg_hip.so: $(HIPOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIPOBJ) -o $@
 
-# development build: the product's kernels plus the two retired schedulers (round 1's pooled kernel,
-# the staged kernel) the GPU tests cross-check against; selected with VIMG_HIP_LIB
+# development build: the product's objects, with the units of the retired schedulers (their kernels and
+# their host side) compiled for real; the GPU tests cross-check against it, selected with VIMG_HIP_LIB
 DEVOBJDIR := build/hip_dev
 DEVOBJ    := $(patsubst v-img_amd/csrc/%.hip,$(DEVOBJDIR)/%.o,$(HIPSRC))
-$(DEVOBJDIR)/k_dev.o: v-img_amd/csrc/k_dev.hip $(HIPHDR) Makefile
-	@mkdir -p $(DEVOBJDIR)
-	$(HIPCC) $(HIPCFLAGS) -DVIMG_DEV_SCHEDULERS=1 $< -o $@
-$(DEVOBJDIR)/k_pool4.o: v-img_amd/csrc/k_pool4.hip $(HIPHDR) Makefile
+DEVUNITS  := k_dev k_pool4 launch_dev
+$(DEVUNITS:%=$(DEVOBJDIR)/%.o): $(DEVOBJDIR)/%.o: v-img_amd/csrc/%.hip $(HIPHDR) Makefile
 	@mkdir -p $(DEVOBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -DVIMG_DEV_SCHEDULERS=1 $< -o $@
 $(DEVOBJDIR)/%.o: $(OBJDIR)/%.o

@@ -1128,7 +1128,7 @@ def test_leaves_of_more_than_127_primitives(leaf_cap):
 
 
 def test_launch_policy_picks_the_builds_design_md_names():
-    """vimg_hip.hip:make_launch: every launch - a full frame, its shards down to an
+    """launch_policy.hip:make_launch: every launch - a full frame, its shards down to an
     eighth, a frame of test size, trace_pixel - gets the CU scheduler, in the build for trees that sit
     in LDS or the one for trees in global memory; the lane-bound kernel by name.  (What each of them
     renders is the business of the parity tests above.)"""

@@ -11,7 +11,7 @@ with two ray sets:
                  normal, t_max = the scene's diagonal
 at N = 2^20 and 2^24.  Each row runs under both launch shapes, interleaved: the persistent grid
 (VIMG_HIP_QUERY_BLOCKS=1) and one workgroup per 256 rays (=0), each read at upload by a DeviceScene of its own; the
-library's policy picks one of them per scene (vimg_hip.hip:launch_query).  Times are device events
+library's policy picks one of them per scene (ray_query.hip:launch_query).  Times are device events
 around back-to-back calls of the C ABI (max(2, 2^25 / N) of them) on a non-default stream, per call, best of `reps`
 after a warm-up.  Prints a table to stderr and one JSON line.
 Per-kernel times: run it under `rocprofv3 --kernel-trace --stats` (kernels ray_query_kernel<0|1|2>)."""

@@ -1,0 +1,137 @@
+// What the host units of libvimg_hip.so share (none of it is exported: include/vimg_hip.h is the ABI).
+//   vimg_hip.hip       init / options / last_error, the render entry points, enqueue_render
+//   scene_upload.hip   validation, baking and upload of a scene, its changes, its release
+//   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel
+//   launch_dev.hip     the retired schedulers POOL / POOL4 / POOL4G / STAGE (development build; stubs otherwise)
+//   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/vimg_hip.h"
+#include "device_scene.h"
+#include "kernel_tus.h"
+
+struct DevSchedState;   // launch_dev.hip
+
+struct VimgDeviceScene {
+  vimg::DScene d{};
+  std::vector<void*> allocs;
+  size_t total_bytes = 0;
+  bool textured = false;       // needs the TEX=true kernels (cones, image textures, env map)
+  VimgHipOptions opt{};        // the caller's options (VIMG_OPT_AUTO where the policy decides)
+  int waves_per_simd = 2;      // LANE register budget by policy (scene size)
+  bool too_wide = false;       // resolution beyond the 16-bit pixel coordinates of the slot records
+  uint32_t num_cus = 0;
+  uint32_t num_leaf_prims = 0;   // records in d.leaf_prims (= primitives of the scene)
+  // scratch owned by the scene: stats, work counter, host-render framebuffer
+  vimg::DeviceStats* d_stats = nullptr;
+  unsigned int* d_counter = nullptr;
+  float* d_frame = nullptr;
+  void* d_pool_cold = nullptr;   // pooled kernel: cold slot records of every resident wave
+  size_t pool_cold_bytes = 0;
+  void* d_stack_ovf = nullptr;   // pool4, deep trees: the stack entries beyond the LDS part, per resident wave
+  size_t stack_ovf_bytes = 0;
+  void* d_pool_state = nullptr;  // pooled kernel: per-pixel record between sample segments
+  size_t pool_state_bytes = 0;
+  uint32_t pool_epoch = 0;       // bumped per launch: tags of earlier launches never match
+  size_t frame_floats = 0;
+  DevSchedState* dev = nullptr;  // buffers of the retired schedulers (development build; null until one of them launches)
+  // geometry updates (vimg_hip_scene_update_geometry): what the upload knew of the tables and the tree
+  uint64_t generation = 0;       // bumped by every change of the resident scene; accumulators remember theirs
+  uint32_t num_vertices = 0, num_tris = 0, num_spheres = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> normal_rows;   // (first vertex, count) of the meshes with normals, merged
+  uint32_t n_internal = 0;       // DNode records of the tree; the n_chain chain records follow them
+  uint32_t n_chain = 0;
+  const uint32_t* d_chain_leaf = nullptr;   // per chain record {first slot, count} of its whole leaf
+  std::vector<uint32_t> level_begin;        // breadth-first levels of the internal nodes: [level_begin[k], level_begin[k+1])
+  float* d_root_box = nullptr;              // 6 floats the refit leaves the root's box in
+  // ray queries (vimg_hip_trace_rays, _occluded): the LDS layout and the blocks per CU of each query build, worked
+  // out at the first query (the tree's shape and the options never change after upload)
+  int query_launch = -1;        // VIMG_HIP_QUERY_BLOCKS (tools/ only): 0 = one workgroup per 256 rays (the probe's launch),
+                                // 1 = the persistent grid, unset = the policy of launch_query
+  bool query_ready = false;
+  vimg::RenderArgs query_args{};
+  uint32_t query_lds = 0;
+  uint32_t query_per_cu[3] = {0, 0, 0};
+};
+
+// A frame rendered in increments (vimg_hip_progressive_*): its scene, its parameters and the pixel records.
+struct VimgProgressive {
+  VimgDeviceScene* scene = nullptr;
+  VimgRenderParams params{};      // samples field unused
+  uint64_t items = 0;             // work items of a launch (64 per tile of the shard)
+  void* d_rec[2] = {nullptr, nullptr};   // 32 B per item each; d_rec[cur] holds the state after `samples`
+  int cur = 0;
+  uint32_t samples = 0;           // samples per pixel so far
+  void* d_scratch = nullptr;      // the means of increments asked for without an output buffer
+  size_t scratch_bytes = 0;
+  uint64_t generation = 0;        // the scene's generation its records were made in
+};
+
+#pragma GCC visibility push(hidden)
+namespace vimg {
+
+extern hipStream_t g_stream;   // vimg_hip.hip (vimg_hip_init)
+extern int g_device;
+
+int fail(int code, const std::string& msg);   // sets vimg_hip_last_error of this thread; returns code
+#define HIP_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return fail(VIMG_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
+  } while (0)
+
+int grow(void** p, size_t* have, size_t need);   // a device buffer of at least `need` bytes (contents lost when it grows)
+
+inline uint32_t tiles_of(int n) { return (static_cast<uint32_t>(n) + 7u) / 8u; }
+uint32_t local_tiles(const VimgDeviceScene* s, const VimgRenderParams* p);
+inline uint32_t opt_or(int32_t v, uint32_t dflt) { return v == VIMG_OPT_AUTO ? dflt : static_cast<uint32_t>(v); }
+
+struct LaunchCfg {
+  RenderArgs args;
+  uint32_t grid, lds_bytes;
+  int sched;     // VIMG_SCHED_* of this launch
+  bool pooled;   // render_pool_kernel for this launch
+  int wps;       // register-budget build (waves per SIMD of __launch_bounds__)
+  int rays;      // pool4: rays a lane walks at the same time (1; two measured slower and are not built)
+  bool group;    // pool4: one pool and one set of queues per workgroup (VIMG_SCHED_POOL4G) instead of per wave
+  bool deep;     // pooled / staged kernel: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)
+  int cu_waves;  // CU scheduler: waves per workgroup (16 or 8)
+  size_t cold_bytes;   // scene-owned scratch of the launch: cold slot records of every resident wave (0: none) ...
+  size_t ovf_bytes;    // ... and the stack entries beyond stack_lds (0: the stacks fit)
+};
+
+// ---- launch_policy.hip
+LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
+// the lane-bound kernel's launch; also the LDS layout (stacks, then the top of the tree) of probes, the heatmap and queries
+LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
+RenderArgs base_args(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
+// Splits a pixel's samples into segments handed out as separate work items (sets pool_segments, pool_seg_len;
+// returns the length): about `per_gen` segments per pool generation of the frame, at most `most`
+uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint64_t items, uint64_t in_flight,
+                      double per_gen, double most, RenderArgs* a);
+// the kernel the policy sizes a launch for, and the build of it that runs (render_cu_kernel: the statistics
+// build for `stats`, the early-ray build for cu_flex bit 5)
+const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c);
+const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
+
+// ---- launch_dev.hip: the schedulers POOL, POOL4, POOL4G and STAGE.  Without -DVIMG_DEV_SCHEDULERS the
+// upload refuses them (kNoDevSchedulers) and these are stubs that answer the same.
+inline constexpr const char* kNoDevSchedulers =
+    "options: the schedulers POOL, POOL4, POOL4G and STAGE are reference implementations "
+    "of the development build (make dev), not part of this library";
+LaunchCfg dev_make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
+const void* dev_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, const char** name);
+// enqueues the launch (its queue resets, argument block and kernel) on `st`; ev0 is recorded right before the kernel
+int dev_enqueue(VimgDeviceScene* s, const LaunchCfg& c, float* d_out, DeviceStats* stats, hipStream_t st, hipEvent_t ev0);
+int dev_error_word(const VimgDeviceScene* s, unsigned int* word);   // the staged kernel's own error word (0 without one)
+void dev_free(VimgDeviceScene* s);
+
+}  // namespace vimg
+#pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // render_cu_kernel, the build whose vertex stages queue their rays as soon as they are known (EARLY): frames
-// short of pixels and trees in global memory (vimg_hip.hip:make_launch_cu)
+// short of pixels and trees in global memory (launch_policy.hip:make_launch_cu)
 #include "kernel_tus.h"
 #include "render_cu_kernel.h"
 

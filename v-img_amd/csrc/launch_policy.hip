@@ -1,0 +1,280 @@
+// The launch policy of the product: which kernel a launch runs and with what grid, LDS layout and scheduler
+// parameters.  Policy (AUTO): the CU-wide scheduler (render_cu_kernel) for every launch - whole frames, thin
+// shards, trace_pixel.  The lane-bound kernel runs when asked for by name and for frames wider than the 16-bit
+// pixel coordinates of the slot records; the schedulers of rounds 1 and 2 by name, in the development build
+// (launch_dev.hip).
+#include <cmath>
+
+#include "hip_internal.h"
+#include "render_cu_kernel.h"
+
+namespace vimg {
+
+uint32_t local_tiles(const VimgDeviceScene* s, const VimgRenderParams* p) {
+  const uint32_t total = tiles_of(s->d.res_x) * tiles_of(s->d.res_y);
+  if (p->tile_rank >= total) return 0;
+  return (total - p->tile_rank + p->tile_world - 1) / p->tile_world;
+}
+
+// what every launch builder fills the same way
+RenderArgs base_args(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  const VimgHipOptions& o = s->opt;
+  RenderArgs a{};
+  a.integrator = p->integrator;
+  a.samples = p->samples;
+  a.spp_div = static_cast<float>(p->samples);   // (a progressive launch sets the base and the divisor of its total)
+  a.depth = p->depth;
+  a.tile_rank = p->tile_rank;
+  a.tile_world = p->tile_world;
+  a.tiles_x = tiles_of(s->d.res_x);
+  a.tiles_y = tiles_of(s->d.res_y);
+  a.num_local_tiles = local_tiles(s, p);
+  a.full_stats = 0;
+  a.single_x = sx;
+  a.single_y = sy;
+  a.stack_entries = s->d.max_depth + 2;
+  a.stack_ovf = nullptr;
+  a.pool_refill = 16u;
+  a.pool_vbatch = std::min(64u, std::max(1u, opt_or(o.pool_vbatch, 64u)));
+  a.pool_boxmin = std::min(64u, opt_or(o.pool_boxmin, 16u));
+  a.pool_segments = 1;
+  a.pool_seg_len = p->samples;
+  return a;
+}
+
+uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint64_t items, uint64_t in_flight,
+                      double per_gen, double most, RenderArgs* a) {
+  const double gens = double(items) / double(in_flight);
+  uint32_t k = gens >= 10.0 ? 1u : uint32_t(std::min(most, std::max(1.0, std::floor(per_gen / gens + 0.5))));
+  k = std::min<uint32_t>(k, std::max<uint32_t>(p->samples / 4u, 1u));
+  if (items * 2u < in_flight * 3u) k = 1u;
+  if (s->opt.pool_segments != VIMG_OPT_AUTO) k = uint32_t(std::max(1, s->opt.pool_segments));
+  k = std::min<uint32_t>(k, 4096u);
+  while (k > 1u && items * k >= 0xfff00000ull) --k;   // (segment, pixel) items must fit the 32-bit counter
+  const uint32_t len = std::max<uint32_t>((p->samples + k - 1) / k, 1u);
+  a->pool_seg_len = len;
+  a->pool_segments = std::max<uint32_t>((p->samples + len - 1) / len, 1u);
+  return len;
+}
+
+namespace {
+
+CuKernel pick_cu_kernel(const VimgDeviceScene* s, bool deep, int nw, bool diag = false, bool early = false) {
+  return diag ? vimg_cu_kernel_diag(s->textured, deep, nw)
+              : (early ? vimg_cu_kernel_early(s->textured, deep, nw) : vimg_cu_kernel(s->textured, deep, nw));
+}
+
+// n / d == mulhi(n, magic) >> shift for every n < 2^31 (Granlund & Montgomery, "Division by invariant
+// integers using multiplication", fig. 4.1 with N = 31): the ring index of render_cu_kernel's tickets
+void magic_div(uint32_t d, uint32_t* magic, uint32_t* shift) {
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;   // ceil(log2 d), d >= 2
+  *magic = static_cast<uint32_t>((1ull << (31u + l)) / d + 1ull);
+  *shift = l - 1u;
+}
+
+// The launch of the CU-wide scheduler (render_cu_kernel.h): one workgroup of 16 waves per compute unit
+// (or two of 8), a pool of as many slots as the CU's LDS holds behind the top of the tree, the
+// walking waves' stacks and the rings - never more than the launch has pixels per workgroup.
+LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  LaunchCfg c{};
+  const VimgHipOptions& o = s->opt;
+  const uint64_t items = (sx >= 0) ? 1 : uint64_t(local_tiles(s, p)) * 64u;
+  c.sched = VIMG_SCHED_CU;
+  c.pooled = true;
+  c.group = false;
+  c.rays = 1;
+  c.wps = 4;
+  c.cu_waves = 16;   // (a build with two 8-wave workgroups per CU halves the pool a batch draws from; not built)
+  const uint32_t nw = uint32_t(c.cu_waves);
+  RenderArgs& a = c.args = base_args(s, p, sx, sy);
+  a.stack_lds = std::min(a.stack_entries, std::max(1u, opt_or(o.lds_stack, 32u)));
+  // walking waves: five of eight by policy (config 2: the walk is 60 % of the wave cycles); when every
+  // wave walks, every wave must be allowed to shade too
+  a.cu_walkers = 0;   // (set below, once the tree's place is known)
+  a.cu_flex = opt_or(o.cu_flex, 1u);   // (bit 1 / 2: shading / walking at wave priority 1; bit 4: no split batches; bit 5: early rays, by policy below)
+  a.cu_lowwater = std::max(1u, opt_or(o.cu_lowwater, 64u));
+  a.cu_patience = opt_or(o.cu_patience, 4u);
+  a.cu_join = std::max(1u, opt_or(o.cu_join, 1u));
+  a.cu_sleep = std::min(127u, std::max(1u, opt_or(o.cu_sleep, 4u)));
+  a.pool_starve = std::min(64u, std::max(1u, opt_or(o.pool_starve, 16u)));   // smallest partial batch worth a wave at once
+  a.pool_classes = std::min(3u, std::max(1u, opt_or(o.pool_classes, 3u)));
+  a.pool_gbreak = 0;
+  // LDS of the workgroup: the whole CU's (16 waves) or half of it, minus a margin
+  const uint32_t share = (160u * 1024u) / (16u / nw) - 1024u;
+  uint32_t node_budget = 4608u;
+  if (o.lds_budget_kb != VIMG_OPT_AUTO) node_budget = uint32_t(std::max(1, o.lds_budget_kb)) * 1024u;
+  a.lds_nodes = std::min(node_budget / 56u, s->d.num_nodes);
+  const uint32_t node_bytes = (a.lds_nodes * 56u + 255u) & ~255u;
+  // the build with the overflow path and the global node fetch serves both trees beyond the LDS
+  // node cache and stacks deeper than their LDS rows
+  c.deep = a.lds_nodes < s->d.num_nodes || a.stack_lds < a.stack_entries;
+  // walking waves (profiles/r3_cu/sweeps.txt): trees in LDS 9 of 16 (config 2 at 512 spp: 8 waves 307,
+  // 9: 304, 10: 325, 11: 337 ms), trees in global memory 10 (stand-ins of configs 4 / 5 at 32 spp:
+  // 8 waves 2 650 / 3 436, 10: 2 796 / 4 019, 12: 2 649 / 3 762 Mrays/s); when every wave walks, every
+  // wave must be allowed to shade too
+  a.cu_walkers = std::min(nw, std::max(1u, opt_or(o.cu_walkers, c.deep ? 10u : 9u)));
+  // finished rays that send a walking wave to its rings (hand-over, then refill): 16 on trees in LDS; on
+  // trees in global memory, where a pass waits for memory and a finished ray would wait with it, 2
+  // (stand-ins of configs 4 / 5: an eighth of the frame at 128 spp 82.8 / 77.9 against 93.3 / 82.3 ms,
+  // a quarter 87.7 against 92.2, a half 101.9 against 107.8, the whole frame unchanged)
+  a.pool_refill = std::max(1u, opt_or(o.pool_refill, c.deep ? 2u : 16u));
+  const uint32_t stack_rows = pool4_stack_rows_of(a.stack_entries, a.stack_lds);
+  uint32_t leaf_bytes = 0;
+  a.lds_leaf = 0;
+  if (s->num_leaf_prims * 48u <= 4096u && o.lds_leaf != 0) {
+    a.lds_leaf = s->num_leaf_prims;
+    leaf_bytes = a.lds_leaf * 48u;
+  }
+  auto slots_with = [&](uint32_t walkers) {
+    const uint32_t fixed = node_bytes + walkers * stack_rows * 256u + cu_pool_bytes(0, nw) + leaf_bytes + 64u;
+    uint32_t n = share > fixed ? (share - fixed) / CU_LDS_BYTES : 0u;
+    n = std::min(n, 4096u);
+    // (trees in LDS: the rate is flat from 1 152 slots on - config 2 at 512 spp: 896 slots 323, 1 024: 305,
+    // 1 152: 297.7, 1 280: 297.7, 1 408: 298.4, all 1 490 the LDS holds: 300.2 ms; smaller cold regions stay in L2)
+    if (!c.deep && o.pool_slots == VIMG_OPT_AUTO) n = std::min(n, 1280u);
+    if (o.pool_slots != VIMG_OPT_AUTO) n = std::min(n, uint32_t(std::max(0, o.pool_slots)));
+    return n;
+  };
+  // never more slots than the launch has pixels per workgroup (a thin shard's pixels each own a slot
+  // from the first sample to the last)
+  const uint32_t groups = s->num_cus * (16u / nw);
+  const uint64_t per_group = (items + groups - 1) / groups;
+  // a launch whose pixels all own a slot, on a tree in LDS: every wave walks AND shades (a quarter of
+  // config 2: 135.0 against 142.4 ms; an eighth and a third: no difference)
+  if (o.cu_walkers == VIMG_OPT_AUTO && !c.deep && o.pool_slots == VIMG_OPT_AUTO && per_group + 8u <= slots_with(nw)) a.cu_walkers = nw;
+  if (a.cu_walkers == nw) a.cu_flex |= 1u;
+  const uint32_t stack_bytes = a.cu_walkers * stack_rows * 256u;
+  uint32_t slots = slots_with(a.cu_walkers);
+  // ... and when the pixels are more than the slots but fewer than 2.7 pools' worth (half a frame of
+  // config 2), a pool of pixels / 2.7: the segments of a pixel are handed from slot to slot, and a
+  // slot that draws a segment whose predecessor is still running can only wait - with 1.65
+  // generations of slots per pixel half of config 2 took 253 ms, with 2.7 (1 040 slots) 176, with 3.5 180
+  if (o.pool_slots == VIMG_OPT_AUTO && per_group > slots && per_group * 10u < uint64_t(slots) * 27u)
+    slots = static_cast<uint32_t>(per_group * 10u / 27u);
+  slots = static_cast<uint32_t>(std::min<uint64_t>(slots, per_group + 8u));
+  slots = std::max(slots & ~7u, 8u);
+  // EARLY rays (cu_flex bit 5: a vertex stage queues each ray as soon as it is known and finishes beside
+  // the walk) wherever a slot's hop latency is on the frame's critical path: launches of fewer than three
+  // pools' worth of pixels, and trees in global memory (whose walks are long).  Config 2: an eighth 110.4 ->
+  // 99.9 ms, a quarter 132.5 -> 118.3, a half 170.6 -> 164.5, the whole frame 300.4 -> 309.7 (it only pays the
+  // two extra ring operations per vertex: off there); stand-ins of configs 4 / 5: whole frame 121.4 -> 118.4 /
+  // 127.0 -> 124.1, an eighth 81.3 -> 79.4 / 76.8 -> 69.9
+  if (o.cu_flex == VIMG_OPT_AUTO && (c.deep || per_group * 10u <= uint64_t(slots) * 30u)) a.cu_flex |= 32u;
+  // a tree in global memory on a launch whose pixels all own a slot: the box loop yields to waiting leaves
+  // below 8 descending lanes instead of 16 (stand-ins of configs 4 / 5, a quarter at 128 spp: 79.3 / 69.9
+  // against 80.8 / 72.7 ms, an eighth 76.7 / 65.5 against 76.9 / 70.1; halves and whole frames want 16)
+  if (c.deep && o.pool_boxmin == VIMG_OPT_AUTO && per_group + 8u >= slots && per_group <= slots) a.pool_boxmin = 8u;
+  a.pool_slots = slots;
+  magic_div(slots, &a.cu_magic_v, &a.cu_shift_v);
+  magic_div(2u * slots, &a.cu_magic_w, &a.cu_shift_w);
+  c.lds_bytes = node_bytes + stack_bytes + cu_pool_bytes(slots, nw) + leaf_bytes;
+  int per_cu = 0;
+  hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of(s, c), int(nw * 64u), c.lds_bytes);
+  if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+  per_cu = std::min<int>(per_cu, int(16u / nw));
+  const uint64_t need_blocks = (items + slots - 1) / slots;
+  c.grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(need_blocks, uint64_t(s->num_cus) * per_cu)));
+  // segments: as the group build of render_pool4_kernel (the tail of a frame is one segment long)
+  a.cu_watchdog = static_cast<uint32_t>(1000000000ull >> 20);
+  if (sx < 0) {
+    const uint32_t len = segments_for(s, p, items, uint64_t(c.grid) * slots, 176.0, 64.0, &a);
+    a.cu_watchdog = static_cast<uint32_t>(std::min<uint64_t>((1000000000ull + 5000000ull * len) >> 20, 0x7fffffffull));   // 10 s + 50 ms per sample of a segment
+  }
+  return c;
+}
+
+// the scene-owned scratch of a CU launch: one cold region per workgroup, one overflow stack per walking wave
+void cu_scratch(const VimgDeviceScene* s, LaunchCfg& c) {
+  const RenderArgs& a = c.args;
+  c.cold_bytes = size_t(c.grid) * pool4_cold_records(s->textured) * a.pool_slots * 16u;
+  if (a.stack_lds < a.stack_entries)
+    c.ovf_bytes = size_t(c.grid) * a.cu_walkers * uint32_t(c.rays) * (a.stack_entries - a.stack_lds) * 256u;
+}
+
+}  // namespace
+
+const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
+  if (c.sched == VIMG_SCHED_CU) return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves));
+  if (c.sched == VIMG_SCHED_LANE) return reinterpret_cast<const void*>(vimg_lane_kernel(s->textured, c.wps));
+  return dev_kernel_of(s, c, nullptr);
+}
+
+const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
+  if (c.sched != VIMG_SCHED_CU) return kernel_of(s, c);
+  return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves, stats, (c.args.cu_flex & 32u) != 0u));
+}
+
+LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  LaunchCfg c{};
+  const VimgHipOptions& o = s->opt;
+  const uint64_t items = (sx >= 0) ? 1 : uint64_t(local_tiles(s, p)) * 64u;
+  c.sched = VIMG_SCHED_LANE;
+  // register budget: the lane-bound kernel wants 3 waves per SIMD on scenes beyond the on-chip
+  // caches (latency-bound) and 2 on small ones (VALU-bound, fewest spills)
+  c.wps = s->waves_per_simd;
+  if (o.waves_per_simd != VIMG_OPT_AUTO) c.wps = o.waves_per_simd >= 3 ? 3 : 2;
+  c.rays = 1;
+  RenderArgs& a = c.args = base_args(s, p, sx, sy);
+  a.stack_lds = a.stack_entries;
+  // LDS budget per 256-thread workgroup: stacks first, then as much of the top of the tree as
+  // fits in 40 KiB total (keeps >= 4 workgroups per CU inside the 160 KiB)
+  const uint32_t stack_bytes = 4u * a.stack_entries * 64u * 4u;
+  uint32_t budget = 40u * 1024u;
+  if (o.lds_budget_kb != VIMG_OPT_AUTO) budget = uint32_t(std::max(1, o.lds_budget_kb)) * 1024u;
+  uint32_t nodes = 0;
+  if (stack_bytes + 512 < budget) nodes = (budget - stack_bytes - 256) / 56u;
+  a.lds_nodes = std::min(nodes, s->d.num_nodes);
+  c.lds_bytes = ((a.lds_nodes * 56u + 255u) & ~255u) + stack_bytes;
+  // (queue parameters of the pooled kernels: the lane-bound kernel reads none of them)
+  a.pool_gbreak = std::min(64u, opt_or(o.pool_gbreak, 32u));
+  a.pool_classes = std::min(3u, std::max(1u, opt_or(o.pool_classes, 3u)));
+  a.pool_starve = std::min(64u, std::max(1u, opt_or(o.pool_starve, 24u)));
+  // persistent grid: as many 4-wave workgroups as the kernel's registers and LDS let a CU hold
+  // (asked of the runtime), never more than the work
+  int per_cu = 0;
+  hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of(s, c), 256, c.lds_bytes);
+  if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+  const uint64_t need_blocks = (items + 255) / 256;
+  c.grid = static_cast<uint32_t>(
+      std::max<uint64_t>(1, std::min<uint64_t>(need_blocks, uint64_t(s->num_cus) * per_cu)));
+  return c;
+}
+
+LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  const int sched = s->opt.scheduler;
+  if (s->too_wide || sched == VIMG_SCHED_LANE) return make_launch_lane(s, p, sx, sy);   // slots pack pixel coordinates in 16 bits
+  if (sched != VIMG_OPT_AUTO && sched != VIMG_SCHED_CU) return dev_make_launch(s, p, sx, sy);
+  LaunchCfg c = make_launch_cu(s, p, sx, sy);
+  cu_scratch(s, c);
+  return c;
+}
+
+}  // namespace vimg
+
+using namespace vimg;
+
+extern "C" {
+
+const char* vimg_hip_launch_kernel(const VimgDeviceScene* s, const VimgRenderParams* p) {
+  if (!s || !p) return "";
+  static const char* lane_names[2][2] = {{"render_kernel<false,2>", "render_kernel<false,3>"},
+                                         {"render_kernel<true,2>", "render_kernel<true,3>"}};
+  static const char* cu_names[2][2] = {{"render_cu_kernel<false>", "render_cu_kernel<false,deep>"},
+                                       {"render_cu_kernel<true>", "render_cu_kernel<true,deep>"}};
+  if (p->tile_world == 0 || p->tile_rank >= p->tile_world) return "";
+  const LaunchCfg c = make_launch(s, p, -1, -1);
+  if (c.sched == VIMG_SCHED_CU) return cu_names[s->textured ? 1 : 0][c.deep ? 1 : 0];
+  if (c.sched == VIMG_SCHED_LANE) return lane_names[s->textured ? 1 : 0][c.wps >= 3 ? 1 : 0];
+  const char* name = "";
+  (void)dev_kernel_of(s, c, &name);
+  return name;
+}
+
+const char* vimg_hip_scene_kernel(const VimgDeviceScene* s) {
+  // the scheduler is chosen per launch: report the one of a whole frame
+  const VimgRenderParams whole{VIMG_INTEGRATOR_MIS, 64, 1, 0, 1};
+  return vimg_hip_launch_kernel(s, &whole);
+}
+
+}  // extern "C"

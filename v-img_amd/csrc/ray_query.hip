@@ -8,13 +8,14 @@
 //
 // The query kernels call traverse / make_hit_info of render_kernels.h unchanged, so a ray's answer is the
 // render's bits.  Launch shape: a persistent grid (as many 256-thread workgroups as the CU holds at the LDS
-// size of make_launch(..., for_render = false)); each workgroup stages the top of the tree into LDS once and
+// size of make_launch_lane); each workgroup stages the top of the tree into LDS once and
 // its waves then take whole 64-ray chunks, chunk = global wave + k * waves of the grid.  A lane loads its
 // ray as two 16-byte loads and stores its hit as one (plus three for the record).  The same kernel on a
-// grid of one workgroup per 256 rays is the probe's launch; which of the two runs is the ABI unit's policy
-// (vimg_hip.hip:launch_query; VIMG_HIP_QUERY_BLOCKS=0 / 1 forces one, tools only).
+// grid of one workgroup per 256 rays is the probe's launch; which of the two runs is the policy of
+// launch_query below (VIMG_HIP_QUERY_BLOCKS=0 / 1 forces one, tools only).
 #include <hip/hip_runtime.h>
 
+#include "hip_internal.h"
 #include "ray_query.h"
 #include "render_kernels.h"
 
@@ -111,3 +112,90 @@ hipError_t enqueue_camera_rays(const DScene& d, const void* samples, uint32_t n,
 }
 
 }  // namespace vimg
+
+// ---- the entry points.  The argument checks never read the scene, so they answer
+// the same on a machine without a GPU; the calls then only enqueue, and read nothing of the scene's render scratch.
+using namespace vimg;
+
+namespace {
+
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+int check_query(const char* what, const VimgDeviceScene* s, uint64_t n, const void* in, const char* in_name,
+                const void* out, const char* out_name, bool out_aligned) {
+  const std::string w(what);
+  if (!s) return fail(VIMG_E_INVALID, w + ": null scene");
+  if (n >= (1ull << 32)) return fail(VIMG_E_INVALID, w + ": n must be below 2^32");
+  if (n == 0) return VIMG_OK;
+  if (!in) return fail(VIMG_E_INVALID, w + ": null " + in_name);
+  if (!out) return fail(VIMG_E_INVALID, w + ": null " + out_name);
+  if (misaligned16(in)) return fail(VIMG_E_INVALID, w + ": " + in_name + " is not 16-byte aligned");
+  if (out_aligned && misaligned16(out)) return fail(VIMG_E_INVALID, w + ": " + out_name + " is not 16-byte aligned");
+  return VIMG_OK;
+}
+
+// The probe's LDS layout (stacks for max_depth + 2 entries, then the top of the tree) and, per query build, the
+// workgroups a CU holds at that size.
+int ensure_query(VimgDeviceScene* s) {
+  if (s->query_ready) return VIMG_OK;
+  VimgRenderParams p{VIMG_INTEGRATOR_MIS, 1, 1, 0, 1};
+  const LaunchCfg c = make_launch_lane(s, &p, -1, -1);
+  s->query_args = c.args;
+  s->query_lds = c.lds_bytes;
+  for (int k = QUERY_CLOSEST; k <= QUERY_OCCLUDED; ++k) {
+    if (c.lds_bytes > 48u * 1024u)
+      HIP_TRY(hipFuncSetAttribute(ray_query_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(c.lds_bytes)));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ray_query_kernel(k), 256, c.lds_bytes) != hipSuccess || per_cu < 1)
+      per_cu = 1;
+    s->query_per_cu[k] = uint32_t(per_cu);
+  }
+  s->query_ready = true;
+  return VIMG_OK;
+}
+
+int launch_query(VimgDeviceScene* s, int kind, const void* rays, uint32_t n, void* hits, void* info, uint8_t* flags,
+                 void* stream) {
+  if (int rc = ensure_query(s)) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  const uint64_t chunks = (uint64_t(n) + 63u) / 64u;
+  uint64_t grid = (chunks + 3u) / 4u;   // one workgroup per 256 rays
+  // Policy: the persistent grid when the top of the tree is staged and the rest read from global memory (config 5
+  // stand-in, 16 M rays: 1.03-1.34x); one workgroup per 256 rays when the whole tree sits in LDS or none of it does
+  // (config 2: the persistent grid 0.85-0.98x on 11 of 12 rows, the caterpillar's stacks-only layout 0.92-0.96x at
+  // 16 M rays) - there
+  // the dispatcher's refill of finished workgroups balances chunks of unequal cost better than the persistent grid's
+  // fixed share per wave, and the re-staging is cheap
+  const bool persistent = s->query_launch == 1 ||
+                          (s->query_launch == -1 && s->query_args.lds_nodes > 0 && s->query_args.lds_nodes < s->d.num_nodes);
+  if (persistent) grid = std::min<uint64_t>(grid, uint64_t(s->num_cus) * s->query_per_cu[kind]);
+  HIP_TRY(enqueue_ray_query(s->d, s->query_args, kind, uint32_t(grid), s->query_lds, rays, n, hits, info, flags, st));
+  return VIMG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vimg_hip_trace_rays(VimgDeviceScene* s, const void* d_rays, uint64_t n, void* d_hits, void* d_info, void* stream) {
+  if (int rc = check_query("trace_rays", s, n, d_rays, "rays", d_hits, "hits", true)) return rc;
+  if (n == 0) return VIMG_OK;
+  if (d_info && misaligned16(d_info)) return fail(VIMG_E_INVALID, "trace_rays: info is not 16-byte aligned");
+  return launch_query(s, d_info ? QUERY_CLOSEST_INFO : QUERY_CLOSEST, d_rays, uint32_t(n), d_hits, d_info, nullptr, stream);
+}
+
+int vimg_hip_occluded(VimgDeviceScene* s, const void* d_rays, uint64_t n, uint8_t* d_flags, void* stream) {
+  if (int rc = check_query("occluded", s, n, d_rays, "rays", d_flags, "flags", false)) return rc;
+  if (n == 0) return VIMG_OK;
+  return launch_query(s, QUERY_OCCLUDED, d_rays, uint32_t(n), nullptr, nullptr, d_flags, stream);
+}
+
+int vimg_hip_camera_rays(VimgDeviceScene* s, const void* d_samples, uint64_t n, void* d_rays, void* stream) {
+  if (int rc = check_query("camera_rays", s, n, d_samples, "samples", d_rays, "rays", true)) return rc;
+  if (n == 0) return VIMG_OK;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  HIP_TRY(enqueue_camera_rays(s->d, d_samples, uint32_t(n), d_rays, st));
+  return VIMG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,73 @@
+// The records the upload bakes from positions, stated once: vimg_hip_scene_upload_opts (host) and the
+// scene_update_* kernels (device) both call these, so a geometry update gives bit for bit what a fresh
+// upload gives.  Plain float expressions, evaluated with IEEE +, -, *, / and no contraction on both
+// sides (-ffp-contract=off).  Square root is spelled __builtin_sqrtf everywhere: sqrtss on the host,
+// the correctly rounded v_sqrt_f32 expansion on gfx950 (hipcc's default for float sqrt).
+#pragma once
+#include "device_scene.h"
+
+namespace vimg {
+
+#define VHD static __host__ __device__ __forceinline__
+
+// cross(p2 - p0, p1 - p0) of the triangle v = p0 p1 p2 (nine floats)
+VHD void tri_cross21(const float* v, float c21[3]) {
+  const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+  const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+  c21[0] = e2[1] * e1[2] - e1[1] * e2[2];
+  c21[1] = e2[2] * e1[0] - e1[2] * e2[0];
+  c21[2] = e2[0] * e1[1] - e1[0] * e2[1];
+}
+
+// tri_normal and the area pdf with the reference's float expressions
+// (src/geometry/triangle.cpp:19-25,229-231; glm cross / normalize as in device_math.h)
+VHD void bake_tri_normal_pdf(const float* v, float n[3], float* area_pdf) {
+  const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+  const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+  const float c12[3] = {e1[1] * e2[2] - e2[1] * e1[2], e1[2] * e2[0] - e2[2] * e1[0],
+                        e1[0] * e2[1] - e2[0] * e1[1]};
+  const float inv_len = 1.0f / __builtin_sqrtf(c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2]);
+  for (int a = 0; a < 3; ++a) n[a] = c12[a] * inv_len;
+  float c21[3];
+  tri_cross21(v, c21);
+  const float area = __builtin_sqrtf(c21[0] * c21[0] + c21[1] * c21[1] + c21[2] * c21[2]) / 2.0f;
+  *area_pdf = 1.f / area;
+}
+
+// DLeafPrim of a triangle: positions and kind.  The degenerate-triangle reject of the reference
+// (triangle.h:86-92) depends on the vertices only: evaluated once, with the same float expression
+VHD void bake_leaf_tri(const float* v, DLeafPrim& lp) {
+  lp.a = v4f{v[0], v[1], v[2], v[3]};
+  lp.b = v4f{v[4], v[5], v[6], v[7]};
+  lp.c0 = v[8];
+  float c[3];
+  tri_cross21(v, c);
+  const float l2 = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+  lp.kind = (l2 == 0.f) ? 2u : 0u;
+}
+// ... of a sphere: centre and radius (its kind, 1, never changes)
+VHD void bake_leaf_sphere(const VimgSphere& sp, DLeafPrim& lp) {
+  lp.a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
+}
+
+// the geometric fields of a DLight: a triangle's positions, face normal and area pdf, a sphere's centre and radius
+VHD void bake_light_tri(const DTriShade& ts, float area_pdf, DLight& L) {
+  L.a = v4f{ts.p[0], ts.p[1], ts.p[2], ts.p[3]};
+  L.b = v4f{ts.p[4], ts.p[5], ts.p[6], ts.p[7]};
+  L.c = v4f{ts.p[8], ts.n[0], ts.n[1], ts.n[2]};
+  L.d.w = area_pdf;
+}
+VHD void bake_light_sphere(const VimgSphere& sp, DLight& L) {
+  L.a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
+}
+
+// the boxes of a DNode's two children: a = Lmin Lmax.x, b = Lmax.yz Rmin.xy, c = Rmin.z Rmax
+VHD void pack_boxes(DNode& n, const float* lmin, const float* lmax, const float* rmin, const float* rmax) {
+  n.a = v4f{lmin[0], lmin[1], lmin[2], lmax[0]};
+  n.b = v4f{lmax[1], lmax[2], rmin[0], rmin[1]};
+  n.c = v4f{rmin[2], rmax[0], rmax[1], rmax[2]};
+}
+
+#undef VHD
+
+}  // namespace vimg

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
+#include "scene_bake.h"
 #include "scene_update.h"
 
 namespace vimg {
@@ -71,12 +72,10 @@ VD Box3 ref_box(const DScene& d, uint32_t ref) {
   return grow(l, r);
 }
 
-// the DNode layout of vimg_hip_scene_upload_opts: a = Lmin Lmax.x, b = Lmax.yz Rmin.xy, c = Rmin.z Rmax
 VD void store_boxes(const DScene& d, uint32_t i, Box3 l, Box3 r) {
-  DNode* n = flat(d.nodes) + i;
-  n->a = v4f{l.lo.x, l.lo.y, l.lo.z, l.hi.x};
-  n->b = v4f{l.hi.y, l.hi.z, r.lo.x, r.lo.y};
-  n->c = v4f{r.lo.z, r.hi.x, r.hi.y, r.hi.z};
+  const float lmin[3] = {l.lo.x, l.lo.y, l.lo.z}, lmax[3] = {l.hi.x, l.hi.y, l.hi.z};
+  const float rmin[3] = {r.lo.x, r.lo.y, r.lo.z}, rmax[3] = {r.hi.x, r.hi.y, r.hi.z};
+  pack_boxes(flat(d.nodes)[i], lmin, lmax, rmin, rmax);
 }
 
 }  // namespace
@@ -89,18 +88,11 @@ __global__ void scene_update_tris(const DScene d, const float* vertices, uint32_
   float v[9];
   for (int k = 0; k < 3; ++k)
     for (int a = 0; a < 3; ++a) v[k * 3 + a] = vertices[size_t(ids[k]) * 3 + a];
-  // the upload's expressions (tri_normal and the area pdf, src/geometry/triangle.cpp:19-25,229-231)
-  const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
-  const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
-  const float c12[3] = {e1[1] * e2[2] - e2[1] * e1[2], e1[2] * e2[0] - e2[2] * e1[0],
-                        e1[0] * e2[1] - e2[0] * e1[1]};
-  const float inv_len = 1.0f / __builtin_sqrtf(c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2]);
-  const float c21[3] = {e2[1] * e1[2] - e1[1] * e2[2], e2[2] * e1[0] - e1[2] * e2[0],
-                        e2[0] * e1[1] - e1[0] * e2[1]};
-  const float area = __builtin_sqrtf(c21[0] * c21[0] + c21[1] * c21[1] + c21[2] * c21[2]) / 2.0f;
+  float n[3], area_pdf;
+  bake_tri_normal_pdf(v, n, &area_pdf);
   for (int k = 0; k < 9; ++k) ts->p[k] = v[k];
-  for (int a = 0; a < 3; ++a) ts->n[a] = c12[a] * inv_len;
-  flat(d.tri_area_pdf)[t] = 1.f / area;
+  for (int a = 0; a < 3; ++a) ts->n[a] = n[a];
+  flat(d.tri_area_pdf)[t] = area_pdf;
 }
 
 __global__ void scene_update_spheres(const DScene d, const float* centre_radius, uint32_t num_spheres) {
@@ -117,21 +109,9 @@ __global__ void scene_update_leaves(const DScene d, uint32_t num_slots) {
   DLeafPrim* lp = flat(d.leaf_prims) + j;
   const VimgPrim p = flat(d.prims)[lp->prim];
   if (p.type == VIMG_PRIM_TRIANGLE) {
-    const float* v = flat(d.tri_shade)[p.index].p;
-    lp->a = v4f{v[0], v[1], v[2], v[3]};
-    lp->b = v4f{v[4], v[5], v[6], v[7]};
-    lp->c0 = v[8];
-    // the degenerate-triangle reject (triangle.h:86-92) as the upload evaluates it
-    const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
-    const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
-    const float cx = e2[1] * e1[2] - e1[1] * e2[2];
-    const float cy = e2[2] * e1[0] - e1[2] * e2[0];
-    const float cz = e2[0] * e1[1] - e1[0] * e2[1];
-    const float l2 = cx * cx + cy * cy + cz * cz;
-    lp->kind = (l2 == 0.f) ? 2u : 0u;
+    bake_leaf_tri(flat(d.tri_shade)[p.index].p, *lp);
   } else {
-    const VimgSphere sp = flat(d.spheres)[p.index];
-    lp->a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
+    bake_leaf_sphere(flat(d.spheres)[p.index], *lp);
   }
 }
 
@@ -143,14 +123,9 @@ __global__ void scene_update_lights(const DScene d) {
   const VimgPrim p = flat(d.prims)[l.prim];
   DLight* L = flat(d.dlights) + i;
   if (p.type == VIMG_PRIM_TRIANGLE) {
-    const DTriShade* ts = flat(d.tri_shade) + p.index;
-    L->a = v4f{ts->p[0], ts->p[1], ts->p[2], ts->p[3]};
-    L->b = v4f{ts->p[4], ts->p[5], ts->p[6], ts->p[7]};
-    L->c = v4f{ts->p[8], ts->n[0], ts->n[1], ts->n[2]};
-    L->d.w = flat(d.tri_area_pdf)[p.index];
+    bake_light_tri(flat(d.tri_shade)[p.index], flat(d.tri_area_pdf)[p.index], *L);
   } else {
-    const VimgSphere sp = flat(d.spheres)[p.index];
-    L->a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
+    bake_light_sphere(flat(d.spheres)[p.index], *L);
   }
 }
 
