@@ -94,8 +94,8 @@ int vimg_hip_scene_upload(const VimgScene* scene, VimgDeviceScene** out);
 int vimg_hip_scene_upload_opts(const VimgScene* scene, const VimgHipOptions* opts, VimgDeviceScene** out);
 int vimg_hip_scene_free(VimgDeviceScene* scene);
 
-/* Changing a resident scene without a new upload: same topology, materials, textures,
- * lights and resolution; new positions and a new camera.
+/* Changing a resident scene without a new upload: same primitives, materials, textures,
+ * lights and resolution; new positions and a new camera (and, below, a new tree over them).
  *  _update_geometry : new positions, NULL = unchanged.  DEVICE pointers to float32, read on `stream`:
  *      vertices num_vertices x 3 (the whole table, VimgScene order), normals num_vertices x 3 (rows of
  *      meshes without normals are ignored), spheres num_spheres x 4 (centre xyz, radius; the material
@@ -119,6 +119,33 @@ typedef struct VimgGeometryUpdate {
 } VimgGeometryUpdate;
 int vimg_hip_scene_update_geometry(VimgDeviceScene* scene, const VimgGeometryUpdate* update, void* stream);
 int vimg_hip_scene_set_camera(VimgDeviceScene* scene, const VimgCamera* camera);
+
+/* A new tree for a resident scene: what a refit cannot give after a large deformation.
+ *  _rebuild_bvh : builds a BVH over the scene's primitives as they now stand (after any _update_geometry) with
+ *      the PLOC builder (opts NULL, or builder VIMG_BUILDER_PLOC) or the LBVH, and bakes the device layout from
+ *      it, all in kernels on resident data: primitive bounds from the triangle records and spheres, the builder's
+ *      core, node records, leaf slots in the new order.  The host only reads the builders' per-round / per-level
+ *      counters.  Afterwards a launch reads exactly the bytes vimg_hip_scene_upload gives for the host scene with
+ *      the same positions whose tree vimg_host_build_bvh_with(vimg_hip_build_ploc) (resp. _lbvh) built: image,
+ *      event counts, heatmap, trace_pixel and ray queries are that upload's, and so is vimg_hip_scene_bytes.
+ *      Blocking; ordered after the work already on `stream` (NULL = the library's).  Changes the scene's
+ *      generation like _update_geometry.  The tree is built beside the old one and swapped in when every step
+ *      has succeeded: a failed call (VIMG_E_DEVICE, a tree beyond the 94-level stack bound, VIMG_E_UNSUPPORTED
+ *      for a leaf over 127 primitives - the builders end theirs at 8) leaves the scene as it was, generation
+ *      included.  A NULL scene, a struct_size below sizeof(VimgRebuildOptions) or an unknown builder are
+ *      VIMG_E_INVALID, found before anything is enqueued.
+ *  _bvh_cost : the surface-area cost of the scene's tree under the reference's model (include/bvh.h:17-20:
+ *      traversal 0.5, intersection 1): the sum over nodes of area x (0.5 for a node with children, its primitive
+ *      count for a leaf) over the root's area, area = dx dy + dx dz + dy dz of the float32 extents, summed in
+ *      float64 in a fixed order (the same scene gives the same bits).  It rises when a refit stretches a tree
+ *      over moved geometry and falls back with a rebuild.  Blocking; reads only the tree. */
+enum { VIMG_BUILDER_PLOC = 0, VIMG_BUILDER_LBVH = 1 };
+typedef struct VimgRebuildOptions {
+  uint32_t struct_size;     /* sizeof(VimgRebuildOptions) */
+  uint32_t builder;         /* VIMG_BUILDER_* */
+} VimgRebuildOptions;
+int vimg_hip_scene_rebuild_bvh(VimgDeviceScene* scene, const VimgRebuildOptions* opts, void* stream);
+int vimg_hip_scene_bvh_cost(VimgDeviceScene* scene, void* stream, double* cost);
 
 /* Ray queries on a resident scene: the render's own walk on rays the caller gives.
  *  _trace_rays  : closest hit, exactly what the render's walk (traverse<false>: the same slab, triangle and

@@ -132,6 +132,19 @@ class GeometryUpdate(C.Structure):
         self.struct_size = C.sizeof(GeometryUpdate)
 
 
+BUILDER_PLOC, BUILDER_LBVH = 0, 1
+BUILDERS = {"ploc": BUILDER_PLOC, "lbvh": BUILDER_LBVH}
+
+
+class RebuildOptions(C.Structure):
+    """VimgRebuildOptions (include/vimg_hip.h): the builder of vimg_hip_scene_rebuild_bvh."""
+    _fields_ = [("struct_size", u32), ("builder", u32)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(RebuildOptions)
+
+
 class Ray(C.Structure):
     """VimgRay (include/vimg_hip.h): one query ray, 32 B."""
     _fields_ = [("org", f32 * 3), ("t_min", f32), ("dir", f32 * 3), ("t_max", f32)]
@@ -231,6 +244,8 @@ HIP_SYMBOLS = {
     "vimg_hip_scene_free": (C.c_int, [C.c_void_p]),
     "vimg_hip_scene_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]),
     "vimg_hip_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
+    "vimg_hip_scene_rebuild_bvh": (C.c_int, [C.c_void_p, C.POINTER(RebuildOptions), C.c_void_p]),
+    "vimg_hip_scene_bvh_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "vimg_hip_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vimg_hip_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vimg_hip_camera_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

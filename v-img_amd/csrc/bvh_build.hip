@@ -20,8 +20,10 @@
 // Both end with
 //   6. the reference's layout, a level of the tree per step: breadth-first numbering with siblings
 //      adjacent, the sibling-pair box table, obj_indices, the depth.
-// Everything runs in kernels; the host launches, reads a counter per round / level, and copies the
-// finished arrays out.
+// Everything runs in kernels; the host launches and reads a counter per round / level.  The cores
+// (lbvh_core, ploc_core: vimg::build_tree_device) take the primitive bounds on the device and leave the
+// layout's arrays there - what vimg_hip_scene_rebuild_bvh builds a resident scene's new tree from; the two
+// exported builders copy the bounds up, run their core and copy the arrays out.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,7 +37,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "../../include/vimg_hip.h"
+#include "hip_internal.h"
 
 namespace {
 
@@ -235,10 +237,12 @@ emit_write(EmitTree t, const uint2* __restrict__ level, uint32_t size, const uns
   }
 }
 
-int emit_reference_layout(const EmitTree& t, uint32_t root_id, uint32_t* num_nodes, uint32_t* max_depth, VimgBVHNode* nodes, float* bb,
-                          uint32_t* obj_indices) {
+// The arrays stay on the device, in `out` (which owns them); out->level_internal gets the nodes with children
+// of every level that has some (the per-level totals the loop reads anyway).
+int emit_reference_layout(const EmitTree& t, uint32_t root_id, vimg::DeviceTree* out) {
   const uint32_t n = t.n, threads = 256;
   const size_t max_nodes = size_t(2) * n - 1, bb_rows = 2 * max_nodes + 3;
+  out->level_internal.clear();
   Buf d_level[2], d_packed, d_scanned, d_totals, d_nodes, d_bb, d_obj, d_scan;
   for (auto& b : d_level) LB_TRY(hipMalloc(&b.p, size_t(n) * sizeof(uint2)));
   LB_TRY(hipMalloc(&d_packed.p, size_t(n) * 8));
@@ -271,17 +275,37 @@ int emit_reference_layout(const EmitTree& t, uint32_t root_id, uint32_t* num_nod
     child_base += 2u * with_children, prim_base += static_cast<uint32_t>(totals & 0xffffffffull);
     if (child_base > max_nodes || prim_base > n) return VIMG_E_DEVICE;
     size = 2u * with_children;
+    if (with_children) out->level_internal.push_back(with_children);
     cur ^= 1;
   }
   LB_TRY(hipGetLastError());
   if (prim_base != n) return VIMG_E_DEVICE;   // every primitive sits in exactly one leaf
-  *num_nodes = child_base;
-  *max_depth = depth;
-  LB_TRY(hipMemcpy(nodes, d_nodes.p, size_t(child_base) * sizeof(VimgBVHNode), hipMemcpyDeviceToHost));
-  LB_TRY(hipMemcpy(bb, d_bb.p, (size_t(2) * child_base + 2) * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  LB_TRY(hipMemcpy(obj_indices, d_obj.p, size_t(n) * 4, hipMemcpyDeviceToHost));
+  out->num_nodes = child_base;
+  out->max_depth = depth;
+  out->nodes = d_nodes.as<VimgBVHNode>(), out->bb = d_bb.as<float>(), out->obj_indices = d_obj.as<uint32_t>();
+  d_nodes.p = d_bb.p = d_obj.p = nullptr;   // (out owns them now)
   return VIMG_OK;
 }
+
+// the finished arrays, copied out for the exported builders
+int download_tree(const vimg::DeviceTree& t, uint32_t n, uint32_t* num_nodes, uint32_t* max_depth, VimgBVHNode* nodes, float* bb,
+                  uint32_t* obj_indices) {
+  *num_nodes = t.num_nodes;
+  *max_depth = t.max_depth;
+  LB_TRY(hipMemcpy(nodes, t.nodes, size_t(t.num_nodes) * sizeof(VimgBVHNode), hipMemcpyDeviceToHost));
+  LB_TRY(hipMemcpy(bb, t.bb, (size_t(2) * t.num_nodes + 2) * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  LB_TRY(hipMemcpy(obj_indices, t.obj_indices, size_t(n) * 4, hipMemcpyDeviceToHost));
+  return VIMG_OK;
+}
+
+struct HostBounds {   // the primitive bounds of an exported builder's caller, copied up
+  Buf d;
+  int upload(uint32_t n, const float* bounds6) {
+    LB_TRY(hipMalloc(&d.p, size_t(n) * 6 * sizeof(float)));
+    LB_TRY(hipMemcpy(d.p, bounds6, size_t(n) * 6 * sizeof(float), hipMemcpyHostToDevice));
+    return VIMG_OK;
+  }
+};
 
 // ---- PLOC (parallel locally-ordered clustering, Meister & Bittner 2018): bottom-up agglomeration
 // over the Morton-sorted clusters.  Per round: every cluster looks at its 2 * R neighbours in the
@@ -578,17 +602,10 @@ top_level(const TopItem* __restrict__ in, TopItem* __restrict__ out, const TopJo
   }
 }
 
-}  // namespace
-
-extern "C" int vimg_hip_build_lbvh(uint32_t n, const float* bounds6, uint32_t* num_nodes,
-                                   uint32_t* max_depth, VimgBVHNode* nodes, float* bb,
-                                   uint32_t* obj_indices) {
-  if (!bounds6 || !num_nodes || !max_depth || !nodes || !bb || !obj_indices || n == 0 || n > (1u << 25))
-    return VIMG_E_INVALID;
-  if (vimg_hip_device_count() <= 0) return VIMG_E_DEVICE;
+// the LBVH over `n` primitive bounds on the device
+int lbvh_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
   const uint32_t threads = 256, blocks = (n + threads - 1) / threads;
-  Buf d_bounds, d_mm, d_keys, d_keys2, d_left, d_right, d_pi, d_pl, d_box, d_visits, d_tmp;
-  LB_TRY(hipMalloc(&d_bounds.p, size_t(n) * 6 * sizeof(float)));
+  Buf d_mm, d_keys, d_keys2, d_left, d_right, d_pi, d_pl, d_box, d_visits, d_tmp;
   LB_TRY(hipMalloc(&d_mm.p, 6 * sizeof(uint32_t)));
   LB_TRY(hipMalloc(&d_keys.p, size_t(n) * 8));
   LB_TRY(hipMalloc(&d_keys2.p, size_t(n) * 8));
@@ -598,14 +615,13 @@ extern "C" int vimg_hip_build_lbvh(uint32_t n, const float* bounds6, uint32_t* n
   LB_TRY(hipMalloc(&d_pl.p, size_t(n) * 4));
   LB_TRY(hipMalloc(&d_box.p, size_t(2) * n * 6 * sizeof(float)));   // the leaves' boxes, then the nodes'
   LB_TRY(hipMalloc(&d_visits.p, size_t(n) * 4));
-  LB_TRY(hipMemcpy(d_bounds.p, bounds6, size_t(n) * 6 * sizeof(float), hipMemcpyHostToDevice));
   const uint32_t mm_init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
   LB_TRY(hipMemcpy(d_mm.p, mm_init, sizeof(mm_init), hipMemcpyHostToDevice));
   LB_TRY(hipMemset(d_visits.p, 0, size_t(n) * 4));
 
-  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, d_bounds.as<float>(), n,
+  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, bounds, n,
                      d_mm.as<uint32_t>());
-  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, d_bounds.as<float>(), n,
+  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, bounds, n,
                      d_mm.as<uint32_t>(), d_keys.as<unsigned long long>());
   size_t tmp_bytes = 0;
   LB_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys.as<unsigned long long>(),
@@ -617,34 +633,26 @@ extern "C" int vimg_hip_build_lbvh(uint32_t n, const float* bounds6, uint32_t* n
     hipLaunchKernelGGL(lb_radix_tree, dim3(blocks), dim3(threads), 0, 0, d_keys2.as<unsigned long long>(), int(n),
                        d_left.as<uint32_t>(), d_right.as<uint32_t>(), d_pi.as<uint32_t>(), d_pl.as<uint32_t>());
   hipLaunchKernelGGL(lb_boxes, dim3(blocks), dim3(threads), 0, 0, d_keys2.as<unsigned long long>(),
-                     d_bounds.as<float>(), int(n), d_left.as<uint32_t>(), d_right.as<uint32_t>(),
+                     bounds, int(n), d_left.as<uint32_t>(), d_right.as<uint32_t>(),
                      d_pi.as<uint32_t>(), d_pl.as<uint32_t>(), d_box.as<float>(), d_box.as<float>() + size_t(n) * 6,
                      d_visits.as<uint32_t>());
   LB_TRY(hipGetLastError());
   // (one primitive per leaf: no subtree ends as a leaf; the root is internal node 0, or the only leaf)
   const EmitTree tree{d_left.as<uint32_t>(), d_right.as<uint32_t>(), d_box.as<float>(), nullptr, nullptr, d_keys2.as<unsigned long long>(), n, 1u};
-  return emit_reference_layout(tree, n == 1 ? 0u : n, num_nodes, max_depth, nodes, bb, obj_indices);
+  return emit_reference_layout(tree, n == 1 ? 0u : n, out);
 }
 
-
-// PLOC builder: same signature and output layout as vimg_hip_build_lbvh; leaves collapsed by the
-// SAH as the reference's builders end theirs (up to 8 primitives), the top rebuilt by binned SAH.  The
-// tree and its layout are made on the GPU.
-extern "C" int vimg_hip_build_ploc(uint32_t n, const float* bounds6, uint32_t* num_nodes,
-                                   uint32_t* max_depth, VimgBVHNode* nodes, float* bb,
-                                   uint32_t* obj_indices) {
-  if (!bounds6 || !num_nodes || !max_depth || !nodes || !bb || !obj_indices || n == 0 || n > (1u << 25))
-    return VIMG_E_INVALID;
-  if (vimg_hip_device_count() <= 0) return VIMG_E_DEVICE;
+// PLOC over `n` primitive bounds on the device: leaves collapsed by the SAH as the reference's builders end
+// theirs (up to 8 primitives), the top rebuilt by binned SAH.  The tree and its layout are made on the GPU.
+int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
   const bool diag = getenv("VIMG_HIP_DIAG") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
   const uint32_t threads = 256, blocks = (n + threads - 1) / threads;
   // ids: [0, n) the sorted leaves, [n, 2n - 1) the nodes of the agglomeration, from 2n - 1 the nodes of the new top
   // (at most one per subtree of the cut, and the cut has at most n subtrees)
   const size_t ids = size_t(3) * n;
-  Buf d_bounds, d_mm, d_keys, d_keys2, d_tmp, d_box, d_cl[2], d_nn, d_merged, d_keep, d_pos, d_left, d_right, d_counter, d_scan;
+  Buf d_mm, d_keys, d_keys2, d_tmp, d_box, d_cl[2], d_nn, d_merged, d_keep, d_pos, d_left, d_right, d_counter, d_scan;
   Buf d_nprims, d_cost, d_as_leaf, d_parent, d_firstpos, d_key, d_sorted, d_sort_tmp, d_at, d_items[2], d_jobs[2], d_counts;
-  LB_TRY(hipMalloc(&d_bounds.p, size_t(n) * 6 * sizeof(float)));
   LB_TRY(hipMalloc(&d_mm.p, 6 * sizeof(uint32_t)));
   LB_TRY(hipMalloc(&d_keys.p, size_t(n) * 8));
   LB_TRY(hipMalloc(&d_keys2.p, size_t(n) * 8));
@@ -670,13 +678,12 @@ extern "C" int vimg_hip_build_ploc(uint32_t n, const float* bounds6, uint32_t* n
   LB_TRY(hipEventCreate(&e0.e));
   LB_TRY(hipEventCreate(&e1.e));
   const hipEvent_t ev0 = e0.e, ev1 = e1.e;
-  LB_TRY(hipMemcpy(d_bounds.p, bounds6, size_t(n) * 6 * sizeof(float), hipMemcpyHostToDevice));
   const uint32_t mm_init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
   LB_TRY(hipMemcpy(d_mm.p, mm_init, sizeof(mm_init), hipMemcpyHostToDevice));
   LB_TRY(hipMemset(d_counter.p, 0, 4));
   LB_TRY(hipEventRecord(ev0, 0));
-  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, d_bounds.as<float>(), n, d_mm.as<uint32_t>());
-  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, d_bounds.as<float>(), n, d_mm.as<uint32_t>(),
+  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, bounds, n, d_mm.as<uint32_t>());
+  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, bounds, n, d_mm.as<uint32_t>(),
                      d_keys.as<unsigned long long>());
   size_t tmp_bytes = 0, scan_bytes = 0;
   LB_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(), n, 0, 62));
@@ -685,7 +692,7 @@ extern "C" int vimg_hip_build_ploc(uint32_t n, const float* bounds6, uint32_t* n
   LB_TRY(hipMalloc(&d_scan.p, std::max<size_t>(scan_bytes, 16)));
   LB_TRY(rocprim::radix_sort_keys(d_tmp.p, tmp_bytes, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(), n, 0, 62));
   hipLaunchKernelGGL(ploc_leaf_boxes, dim3(blocks), dim3(threads), 0, 0, d_keys2.as<unsigned long long>(),
-                     d_bounds.as<float>(), n, d_box.as<float>(), d_cl[0].as<uint32_t>(), rec);
+                     bounds, n, d_box.as<float>(), d_cl[0].as<uint32_t>(), rec);
   uint32_t c = n, radius = PLOC_R;
   if (const char* e = getenv("VIMG_PLOC_R")) radius = uint32_t(std::max(1, atoi(e)));
   int cur = 0, rounds = 0;
@@ -773,14 +780,64 @@ extern "C" int vimg_hip_build_ploc(uint32_t n, const float* bounds6, uint32_t* n
   const auto t_gpu = std::chrono::steady_clock::now();
   const EmitTree tree{d_left.as<uint32_t>(), d_right.as<uint32_t>(), d_box.as<float>(), d_nprims.as<uint32_t>(), d_as_leaf.as<uint32_t>(),
                       d_keys2.as<unsigned long long>(), n, 0u};
-  const int er = emit_reference_layout(tree, root_id, num_nodes, max_depth, nodes, bb, obj_indices);
+  const int er = emit_reference_layout(tree, root_id, out);
   if (er != VIMG_OK) return er;
   if (diag) {
     const auto t_end = std::chrono::steady_clock::now();
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     fprintf(stderr, "[vimg build] ploc: %u primitives, %d rounds, cut of %u subtrees, %u top levels launched; first kernel to last %.2f ms "
-                    "(%.2f ms with the allocations and the upload before), the reference's layout (levels on the GPU) and its download %.2f ms\n",
+                    "(%.2f ms with the allocations before), the reference's layout (levels on the GPU, arrays left there) %.2f ms\n",
             n, rounds, top_items_n, top_levels, gpu_ms, ms(t_begin, t_gpu), ms(t_gpu, t_end));
   }
   return VIMG_OK;
+}
+
+int build_exported(uint32_t builder, uint32_t n, const float* bounds6, uint32_t* num_nodes, uint32_t* max_depth, VimgBVHNode* nodes,
+                   float* bb, uint32_t* obj_indices) {
+  if (!bounds6 || !num_nodes || !max_depth || !nodes || !bb || !obj_indices || n == 0 || n > (1u << 25))
+    return VIMG_E_INVALID;
+  if (vimg_hip_device_count() <= 0) return VIMG_E_DEVICE;
+  const auto t_begin = std::chrono::steady_clock::now();
+  HostBounds up;
+  if (int rc = up.upload(n, bounds6)) return rc;
+  const auto t_up = std::chrono::steady_clock::now();
+  vimg::DeviceTree tree;
+  if (int rc = vimg::build_tree_device(builder, n, up.d.as<float>(), &tree)) return rc;
+  const auto t_built = std::chrono::steady_clock::now();
+  if (int rc = download_tree(tree, n, num_nodes, max_depth, nodes, bb, obj_indices)) return rc;
+  if (getenv("VIMG_HIP_DIAG")) {
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    fprintf(stderr, "[vimg build] %u primitives: upload of the bounds %.2f ms, download of the layout %.2f ms\n", n, ms(t_begin, t_up),
+            ms(t_built, std::chrono::steady_clock::now()));
+  }
+  return VIMG_OK;
+}
+
+}  // namespace
+
+namespace vimg {
+
+DeviceTree::~DeviceTree() {
+  for (void* p : {(void*)nodes, (void*)bb, (void*)obj_indices})
+    if (p) (void)hipFree(p);
+}
+
+int build_tree_device(uint32_t builder, uint32_t n, const float* d_bounds6, DeviceTree* out) {
+  if (!d_bounds6 || !out || n == 0 || n > (1u << 25)) return VIMG_E_INVALID;
+  if (builder == VIMG_BUILDER_PLOC) return ploc_core(n, d_bounds6, out);
+  if (builder == VIMG_BUILDER_LBVH) return lbvh_core(n, d_bounds6, out);
+  return VIMG_E_INVALID;
+}
+
+}  // namespace vimg
+
+extern "C" int vimg_hip_build_lbvh(uint32_t n, const float* bounds6, uint32_t* num_nodes, uint32_t* max_depth, VimgBVHNode* nodes,
+                                   float* bb, uint32_t* obj_indices) {
+  return build_exported(VIMG_BUILDER_LBVH, n, bounds6, num_nodes, max_depth, nodes, bb, obj_indices);
+}
+
+// PLOC builder: same signature and output layout as vimg_hip_build_lbvh.
+extern "C" int vimg_hip_build_ploc(uint32_t n, const float* bounds6, uint32_t* num_nodes, uint32_t* max_depth, VimgBVHNode* nodes,
+                                   float* bb, uint32_t* obj_indices) {
+  return build_exported(VIMG_BUILDER_PLOC, n, bounds6, num_nodes, max_depth, nodes, bb, obj_indices);
 }

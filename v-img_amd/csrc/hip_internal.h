@@ -4,6 +4,7 @@
 //   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel
 //   launch_dev.hip     the retired schedulers POOL / POOL4 / POOL4G / STAGE (development build; stubs otherwise)
 //   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
+//   scene_rebuild.hip  a new tree for a resident scene, its cost       bvh_build.hip    the GPU builders and their cores
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,7 +52,8 @@ struct VimgDeviceScene {
   std::vector<uint32_t> level_begin;        // breadth-first levels of the internal nodes: [level_begin[k], level_begin[k+1])
   float* d_root_box = nullptr;              // 6 floats the refit leaves the root's box in
   // ray queries (vimg_hip_trace_rays, _occluded): the LDS layout and the blocks per CU of each query build, worked
-  // out at the first query (the tree's shape and the options never change after upload)
+  // out at the first query and again after vimg_hip_scene_rebuild_bvh (which resets query_ready: both depend on
+  // max_depth and num_nodes; nothing else changes the tree's shape, and the options never change after upload)
   int query_launch = -1;        // VIMG_HIP_QUERY_BLOCKS (tools/ only): 0 = one workgroup per 256 rays (the probe's launch),
                                 // 1 = the persistent grid, unset = the policy of launch_query
   bool query_ready = false;
@@ -106,6 +108,23 @@ struct LaunchCfg {
   size_t cold_bytes;   // scene-owned scratch of the launch: cold slot records of every resident wave (0: none) ...
   size_t ovf_bytes;    // ... and the stack entries beyond stack_lds (0: the stacks fit)
 };
+
+// ---- bvh_build.hip: the cores of vimg_hip_build_ploc / _lbvh.  They take the primitive bounds (n x {min.xyz,
+// max.xyz}) on the device and leave the tree in the reference's layout (include/bvh.h:22-57) there too: nodes
+// [num_nodes], bb [(2 num_nodes + 2) x 3], obj_indices [n].  Blocking, on the null stream; VIMG_PLOC_* and
+// VIMG_HIP_DIAG as for the exported builders.
+struct DeviceTree {
+  VimgBVHNode* nodes = nullptr;
+  float* bb = nullptr;
+  uint32_t* obj_indices = nullptr;
+  uint32_t num_nodes = 0, max_depth = 0;
+  std::vector<uint32_t> level_internal;   // nodes with children on every level that has some, root level first
+  DeviceTree() = default;
+  DeviceTree(const DeviceTree&) = delete;
+  DeviceTree& operator=(const DeviceTree&) = delete;
+  ~DeviceTree();   // frees the three arrays
+};
+int build_tree_device(uint32_t builder /* VIMG_BUILDER_* */, uint32_t n, const float* d_bounds6, DeviceTree* out);
 
 // ---- launch_policy.hip
 LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);

@@ -18,6 +18,7 @@
 
 #include "device_math.h"
 #include "scene_bake.h"
+#include "scene_boxes.h"
 #include "scene_update.h"
 
 namespace vimg {
@@ -32,27 +33,11 @@ VD T* flat(gptr<T> p) {
   return (T*)p;
 }
 
-struct Box3 {
-  f3 lo, hi;
-};
-
-VD Box3 grow(Box3 a, Box3 b) {
-  return Box3{mk3(sel_min(a.lo.x, b.lo.x), sel_min(a.lo.y, b.lo.y), sel_min(a.lo.z, b.lo.z)),
-              mk3(sel_max(a.hi.x, b.hi.x), sel_max(a.hi.y, b.hi.y), sel_max(a.hi.z, b.hi.z))};
-}
-
 // prim_bounds (host/bvh_build.cpp) of one leaf slot
 VD Box3 slot_box(const DScene& d, uint32_t j) {
   const DLeafPrim lp = flat(d.leaf_prims)[j];
-  if (lp.kind == 1u) {
-    const float r = lp.a.w;
-    return Box3{mk3(lp.a.x - r, lp.a.y - r, lp.a.z - r), mk3(lp.a.x + r, lp.a.y + r, lp.a.z + r)};
-  }
-  const f3 v0 = mk3(lp.a.x, lp.a.y, lp.a.z), v1 = mk3(lp.a.w, lp.b.x, lp.b.y), v2 = mk3(lp.b.z, lp.b.w, lp.c0);
-  const Box3 b12{mk3(sel_min(v1.x, v2.x), sel_min(v1.y, v2.y), sel_min(v1.z, v2.z)),
-                 mk3(sel_max(v1.x, v2.x), sel_max(v1.y, v2.y), sel_max(v1.z, v2.z))};
-  return Box3{mk3(sel_min(v0.x, b12.lo.x), sel_min(v0.y, b12.lo.y), sel_min(v0.z, b12.lo.z)),
-              mk3(sel_max(v0.x, b12.hi.x), sel_max(v0.y, b12.hi.y), sel_max(v0.z, b12.hi.z))};
+  if (lp.kind == 1u) return sphere_box(mk3(lp.a.x, lp.a.y, lp.a.z), lp.a.w);
+  return tri_box(mk3(lp.a.x, lp.a.y, lp.a.z), mk3(lp.a.w, lp.b.x, lp.b.y), mk3(lp.b.z, lp.b.w, lp.c0));
 }
 
 VD Box3 leaf_box(const DScene& d, uint32_t first, uint32_t count) {

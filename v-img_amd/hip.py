@@ -156,6 +156,25 @@ class DeviceScene:
         with _Ordered(stream) as sp:
             _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
 
+    def rebuild_bvh(self, builder="ploc", stream=None):
+        """A new tree over the scene's primitives as they now stand (vimg_hip_scene_rebuild_bvh): built by the GPU
+        builder ``builder`` ("ploc" or "lbvh") from the resident positions and baked into the device layout by
+        kernels.  Afterwards the scene is the upload of the same host scene after build_bvh_with(ploc_builder())
+        (or lbvh_builder()).  Blocking; progressive accumulators of the scene must be reset afterwards."""
+        if builder not in abi.BUILDERS:
+            raise ValueError(f"builder: expected one of {sorted(abi.BUILDERS)}, not {builder!r}")
+        opts = abi.RebuildOptions(builder=abi.BUILDERS[builder])
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_scene_rebuild_bvh(self._h, C.byref(opts), sp))
+
+    def bvh_cost(self, stream=None):
+        """Surface-area cost of the scene's tree under the reference's model (vimg_hip_scene_bvh_cost): it rises
+        when update_geometry stretches the tree over moved geometry; rebuild_bvh brings it back."""
+        cost = C.c_double()
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_scene_bvh_cost(self._h, sp, C.byref(cost)))
+        return float(cost.value)
+
     def set_camera(self, look_from, look_at=None, up=None, vfov_deg=None, aperture_radius=0.0, focal_dist=1.0):
         """A new camera at the scene's resolution (vimg_hip_scene_set_camera): look-at arguments as
         HostScene.set_camera without the resolution, or an abi.Camera.  Progressive accumulators of the scene
