@@ -22,7 +22,7 @@ ORAFLAGS  := -std=c++20 -O3 -march=x86-64-v3 -fPIC -shared -ffp-contract=off -pt
 HIPFLAGS  := --offload-arch=$(ARCH) -std=c++20 -O3 -fPIC -shared -ffp-contract=off -fno-slp-vectorize \
              -fno-fast-math -Iinclude -Wall -Wno-unused-function
 
-all: host hip dev oracle oracle-avx2 cli
+all: host hip oracle oracle-avx2 cli
 host: $(LIBDIR)/libvimg_host.so
 hip: $(LIBDIR)/libvimg_hip.so
 oracle: oracle/liboracle.so
@@ -49,22 +49,6 @@ $(LIBDIR)/libvimg_hip.so: $(HIPOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIPOBJ) -o $@
 
-# development build: the product's objects, with the units of the retired schedulers (their kernels and
-# their host side) compiled for real; the GPU tests cross-check against it, selected with VIMG_HIP_LIB
-DEVOBJDIR := build/hip_dev
-DEVOBJ    := $(patsubst v-img_amd/csrc/%.hip,$(DEVOBJDIR)/%.o,$(HIPSRC))
-DEVUNITS  := k_dev k_pool4 launch_dev
-$(DEVUNITS:%=$(DEVOBJDIR)/%.o): $(DEVOBJDIR)/%.o: v-img_amd/csrc/%.hip $(HIPHDR) Makefile
-	@mkdir -p $(DEVOBJDIR)
-	$(HIPCC) $(HIPCFLAGS) -DVIMG_DEV_SCHEDULERS=1 $< -o $@
-$(DEVOBJDIR)/%.o: $(OBJDIR)/%.o
-	@mkdir -p $(DEVOBJDIR)
-	cp $< $@
-dev: v-img_amd/lib/dev/libvimg_hip.so
-v-img_amd/lib/dev/libvimg_hip.so: $(DEVOBJ)
-	@mkdir -p v-img_amd/lib/dev
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(DEVOBJ) -o $@
-
 # C++ host program (the counterpart of the reference's main): links both libraries by rpath
 v-img_amd/bin/vimg-amd: v-img_amd/cli/main.cpp $(LIBDIR)/libvimg_host.so $(LIBDIR)/libvimg_hip.so Makefile
 	@mkdir -p v-img_amd/bin
@@ -88,6 +72,6 @@ oracle/liboracle_avx2.so: $(ORASRC) $(ORAHDR) Makefile
 	$(CXX) -std=c++20 -O3 -march=x86-64-v3 -fPIC -shared -pthread -Wall -Iinclude -DORACLE_AVX2_TIMING=1 $(ORASRC) -o $@
 
 clean:
-	rm -rf $(LIBDIR)/*.so $(LIBDIR)/dev oracle/*.so build/hip build/hip_dev
+	rm -rf $(LIBDIR)/*.so oracle/*.so build/hip
 
-.PHONY: all host hip dev oracle oracle-avx2 cli clean
+.PHONY: all host hip oracle oracle-avx2 cli clean

@@ -41,39 +41,39 @@ int vimg_hip_device_count(void);
  * the same bits.  The reference has no counterpart (its scheduler is the tile loop of
  * include/integrators.h:57-101); these are the knobs of OUR replacement of that loop, at the
  * boundary instead of in the environment.  (For tools/ only, VIMG_HIP_* environment variables
- * still override single fields at upload: scheduler VIMG_HIP_SCHED=cu|lane (pool|stage|pool4|pool4g in the
- * development build), the others as named in vimg_hip.hip:options_from_env.) */
+ * still override single fields at upload: scheduler VIMG_HIP_SCHED=cu|lane, the others as named in
+ * scene_upload.hip:options_from_env.) */
 #define VIMG_OPT_AUTO (-1)
 enum {
   VIMG_SCHED_LANE = 1,   /* render_kernel: one path per lane, persistent waves */
-  /* 2-5: the schedulers of rounds 1 and 2, reference implementations that only the development build of the
-   * library contains (make dev, v-img_amd/lib/dev/libvimg_hip.so); the product library answers VIMG_E_UNSUPPORTED */
-  VIMG_SCHED_POOL = 2,   /* render_pool_kernel: ~240 path slots per wave in LDS, walk + vertex stages in one wave */
-  VIMG_SCHED_STAGE = 3,  /* render_stage_kernel: path state in HBM slots, stages coupled by global queues, 4 waves/SIMD */
-  VIMG_SCHED_POOL4 = 4,  /* render_pool4_kernel: the pooled scheduler with the vertex stage as calls */
-  VIMG_SCHED_POOL4G = 5, /* the same with ONE pool and one set of queues per workgroup (four waves share them under a lock in LDS) */
+  /* 2-5: retired.  The schedulers of rounds 1 and 2 were removed from the library; the values keep their
+   * places for older callers, and an upload that names one answers VIMG_E_UNSUPPORTED */
+  VIMG_SCHED_POOL = 2,
+  VIMG_SCHED_STAGE = 3,
+  VIMG_SCHED_POOL4 = 4,
+  VIMG_SCHED_POOL4G = 5,
   VIMG_SCHED_CU = 6      /* render_cu_kernel: one pool per compute unit, walking and shading waves, lock-free rings in LDS, both rays of a vertex walked at once */
 };
 typedef struct VimgHipOptions {
   uint32_t struct_size;       /* sizeof(VimgHipOptions): lets the library accept older callers */
-  int32_t scheduler;          /* AUTO (vimg_hip.hip:make_launch_cu): CU for every launch; LANE for frames wider than 65 535 pixels */
-  int32_t waves_per_simd;     /* register budget: LANE / POOL 2 or 3 (AUTO: LANE 3 for scenes > 32 MiB else 2; POOL 2), POOL4 / POOL4G 3 or 4 (AUTO: 4 for full frames on trees that fit in LDS, else 3) */
-  int32_t lds_budget_kb;      /* LDS per workgroup for BVH top + stacks.  AUTO: 40 (LANE), stacks + 4.5 (POOL / STAGE) */
-  int32_t pool_slots;         /* CU: path slots per compute unit.  AUTO: what the CU's LDS holds, <= 1280 on trees in LDS, pixels / 2.7 on launches of 1 to 2.7 pools' worth of pixels, never more than pixels per CU + 8.  (POOL..: per wave, <= 256) */
-  int32_t pool_segments;      /* POOL: segments a pixel's samples are cut into.  AUTO: ~56 / pool generations, <= 16 (POOL4G at four waves: ~176 / generations, <= 64) */
-  int32_t pool_refill;        /* walk: finished rays of a wave that trigger hand-over and refill.  AUTO 16; CU on trees in global memory 2 */
-  int32_t pool_vbatch;        /* POOL: queued slots of one class that start a vertex batch.  AUTO 64 */
-  int32_t pool_classes;       /* POOL: vertex queues by material, 1..3.  AUTO 3; per-wave POOL4 on trees beyond LDS: 1 */
-  int32_t pool_starve;        /* CU: smallest partial vertex batch a wave takes at once.  AUTO 16.  (POOL..: idle walk lanes that force a partial batch, AUTO 24 / 32) */
-  int32_t pool_boxmin;        /* POOL / STAGE, deep trees: leave the box loop below this many descending lanes.  AUTO 16 */
-  int32_t lds_leaf;           /* POOL / STAGE: 0 = never copy the leaf records to LDS.  AUTO: when they fit 4 KiB */
-  int32_t stage_slots;        /* STAGE: path slots in flight.  AUTO: 2 x resident lanes, <= pixels of the launch */
-  int32_t stage_seg_len;      /* STAGE: samples a pixel stays bound to a slot.  AUTO 4 */
-  int32_t stage_wchunk;       /* STAGE: slot ids a walking wave stages in LDS, 128..256.  AUTO 128 */
-  int32_t stage_walk_quota;   /* STAGE: rays a wave walks before it looks at the queues again.  AUTO 2048 */
-  int32_t pool4_rays;         /* reserved (two rays per lane in the walk measured slower; 1 is what runs) */
-  int32_t lds_stack;          /* POOL4, trees beyond LDS: entries of a lane's traversal stack kept in LDS, the rest in global memory.  AUTO 32 */
-  int32_t pool_gbreak;        /* POOL4G: a wave leaves the walk for a full vertex batch only with this many rays or fewer in its lanes.  AUTO 32 */
+  int32_t scheduler;          /* AUTO (launch_policy.hip:make_launch): CU for every launch; LANE for frames wider than 65 535 pixels */
+  int32_t waves_per_simd;     /* LANE: register budget, 2 or 3.  AUTO: 3 for scenes > 32 MiB else 2.  (CU is built for 4) */
+  int32_t lds_budget_kb;      /* LANE: LDS per workgroup for the top of the tree and the stacks, AUTO 40.  CU: LDS for the top of the tree alone, AUTO 4.5 */
+  int32_t pool_slots;         /* CU: path slots per compute unit.  AUTO: what the CU's LDS holds, <= 1280 on trees in LDS, pixels / 2.7 on launches of 1 to 2.7 pools' worth of pixels, never more than pixels per CU + 8 */
+  int32_t pool_segments;      /* CU: segments a pixel's samples are cut into.  AUTO: ~176 / pool generations of the launch, <= 64 and <= samples / 4; 1 on launches of ten generations or more */
+  int32_t pool_refill;        /* CU: finished rays of a walking wave that trigger hand-over and refill.  AUTO 16; on trees in global memory 2 */
+  int32_t pool_vbatch;        /* CU: queued slots of one class that start a vertex batch, 1..64.  AUTO 64 */
+  int32_t pool_classes;       /* CU: vertex queues by material, 1..3.  AUTO 3 */
+  int32_t pool_starve;        /* CU: smallest partial vertex batch a wave takes at once.  AUTO 16 */
+  int32_t pool_boxmin;        /* CU, trees in global memory: leave the box loop below this many descending lanes.  AUTO 16; 8 on launches whose pixels all own a slot */
+  int32_t lds_leaf;           /* CU: 0 = never copy the leaf records to LDS.  AUTO: when they fit 4 KiB */
+  int32_t stage_slots;        /* accepted and ignored (read by a retired scheduler only) */
+  int32_t stage_seg_len;      /* accepted and ignored */
+  int32_t stage_wchunk;       /* accepted and ignored */
+  int32_t stage_walk_quota;   /* accepted and ignored */
+  int32_t pool4_rays;         /* accepted and ignored */
+  int32_t lds_stack;          /* CU: entries of a lane's traversal stack kept in LDS, the rest in global memory.  AUTO 32 */
+  int32_t pool_gbreak;        /* accepted and ignored */
   int32_t cu_waves;           /* CU: reserved; one 16-wave workgroup is a whole compute unit (12 waves at 168 registers measured slower) */
   int32_t cu_walkers;         /* CU: waves of the 16 that walk (the rest only shade).  AUTO: 9 on trees in LDS, 10 on trees in global memory, all 16 when every pixel of the launch owns a slot (tree in LDS) */
   int32_t cu_flex;            /* CU: bit 0: a walking wave that holds no ray may run a vertex batch; bit 4 (16): no split batches (the two BSDF evaluations of a vertex on the two halves of the wave when a batch has <= 32 slots); bit 5 (32): EARLY rays - a vertex stage queues its shadow ray right after the light sample and its path ray right after the BSDF sample and finishes (evaluations, stores) beside their walks; bits 1, 2: shading / walking at wave priority 1 (measurements).  AUTO 1, + 32 on launches of fewer than three pools' worth of pixels and on trees in global memory */
@@ -211,7 +211,6 @@ int vimg_hip_render(VimgDeviceScene* scene, const VimgRenderParams* params, void
  *             (HOST, optional) = this increment's events.  VIMG_E_INVALID for samples == 0, a running
  *             total beyond UINT32_MAX (the reference's sample count is 32-bit), another scene than the
  *             accumulator's, NULL arguments.  The 2^31-ray limit of vimg_hip_render holds per increment.
- *  _create  : VIMG_E_UNSUPPORTED for the development build's schedulers POOL, POOL4, POOL4G and STAGE.
  *  _samples : samples per pixel so far (0 for NULL);  _reset: back to 0 (the next increment seeds again).
  * Accumulators on the same scene are independent (each launch owns the scene's scratch while it runs);
  * free them before their scene. */

@@ -113,9 +113,8 @@ def _dev_opts(scene, **opts):
     return hip.DeviceScene(scene, **opts)
 
 
-# scheduler configurations (VimgHipOptions) of the PRODUCT library: every one must give the lane-bound
-# kernel's bits.  (The schedulers of rounds 1 and 2 - pool, pool4, pool4g, stage - live in the
-# development build and are cross-checked there: test_dev_build_schedulers_give_the_same_bits.)
+# scheduler configurations (VimgHipOptions) of the library: every one must give the lane-bound
+# kernel's bits.
 SCHEDULES = {
     "lane": dict(scheduler="lane"),
     # the CU-wide scheduler as the policy configures it
@@ -149,25 +148,7 @@ SCHEDULES = {
     # the top of the tree outside LDS too (one kilobyte of node cache), no leaf copy in LDS
     "cu/nolds": dict(scheduler="cu", lds_budget_kb=1, lds_leaf=0),
 }
-# the same for the development build (tests/dev_schedulers.py)
-DEV_SCHEDULES = {
-    "pool": dict(scheduler="pool"),
-    "pool/5": dict(scheduler="pool", pool_segments=5),
-    "pool/64": dict(scheduler="pool", pool_segments=64),
-    "pool4": dict(scheduler="pool4"),
-    "pool4/5": dict(scheduler="pool4", pool_segments=5),
-    "pool4/4": dict(scheduler="pool4", waves_per_simd=4, pool_segments=3),
-    "pool4g": dict(scheduler="pool4g"),
-    "pool4g/5": dict(scheduler="pool4g", pool_segments=5),
-    "pool4g/few": dict(scheduler="pool4g", pool_slots=24, pool_segments=2),
-    "pool4/stack1": dict(scheduler="pool4", lds_stack=1),
-    "pool4/stack3": dict(scheduler="pool4", lds_stack=3, pool_segments=2),
-    "stage": dict(scheduler="stage"),
-    "stage/few": dict(scheduler="stage", stage_slots=300, stage_seg_len=1),
-    "stage/whole": dict(scheduler="stage", stage_slots=1000, stage_seg_len=1 << 20, stage_walk_quota=128),
-}
-KERNEL_OF = {"lane": "render_kernel", "cu": "render_cu_kernel", "pool": "render_pool_kernel", "pool4": "render_pool4_kernel",
-             "pool4g": "render_pool4_kernel", "stage": "render_stage_kernel"}
+KERNEL_OF = {"lane": "render_kernel", "cu": "render_cu_kernel"}
 
 
 def scheduler_scene(scene_name):
@@ -187,7 +168,7 @@ def check_schedules_against_lane(s, p, schedules, what, twice=True):
     for name, opts in schedules.items():
         d = _dev_opts(s, **opts)
         assert d.kernel.startswith(KERNEL_OF[opts["scheduler"]]), (name, d.kernel)
-        assert ("group" in d.kernel) == (opts["scheduler"] == "pool4g"), (name, d.kernel)
+        assert "group" not in d.kernel, (name, d.kernel)
         img, st = d.render_to_host(p)
         assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), (what, name, d.kernel)
         assert st.as_dict() == rst.as_dict(), (what, name)
@@ -245,31 +226,13 @@ def test_cu_scheduler_on_every_feature(case):
     check_schedules_against_lane(s, p, {k: SCHEDULES[k] for k in pick}, case, twice=False)
 
 
-def test_dev_build_schedulers_give_the_same_bits():
-    """The schedulers of rounds 1 and 2 (render_pool_kernel, render_pool4_kernel per wave and per
-    workgroup, render_stage_kernel) are kept as reference implementations in the development build
-    of the library (make dev): ONE child process loads that build (VIMG_HIP_LIB) and checks every
-    configuration of DEV_SCHEDULES against the lane-bound kernel and the CU scheduler on the three
-    scheduler scenes and the ten feature cases (tests/dev_schedulers.py)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dev = os.path.join(root, "v-img_amd", "lib", "dev", "libvimg_hip.so")
-    assert os.path.exists(dev), "make dev"
-    env = dict(os.environ, VIMG_HIP_LIB=dev)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "dev_schedulers.py")], env=env, capture_output=True,
-                       text=True, timeout=900)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
-    assert "DEV_SCHEDULERS OK" in r.stdout
-
-
 def test_product_library_refuses_the_retired_schedulers():
     from vimg_amd import hip
     s = scenes.json_scene("disney_spheres.json", res=(32, 16))
     for name in ("pool", "pool4", "pool4g", "stage"):
-        with pytest.raises(hip.HipError, match="development build"):
+        with pytest.raises(hip.HipError, match="retired") as e:
             _dev_opts(s, scheduler=name)
+        assert "[-3]" in str(e.value), str(e.value)      # VIMG_E_UNSUPPORTED
 
 
 @pytest.mark.parametrize("integrator", ["s_normal", "g_normal"])

@@ -693,7 +693,7 @@ def test_bench_roofline_refuses_a_stale_pmc_pass(tmp_path):
     # an eighth of the frame: an eighth of the instructions and of the traffic
     shard = bench.build_roofline(100.0, 2.5e11, 5.0e8, kern, wl, sha, profiles_dir=str(tmp_path))
     assert shard["pmc"] == "fresh" and abs(shard["valu"]["wave_insts_per_launch"] - 2.5e10) < 1 and shard["traffic"] == int(5.0e10)
-    for other in (dict(lib_sha256="cd" * 32), dict(kernel_name="render_pool4_kernel<false,group>"), dict(workload=wl.replace("512", "64"))):
+    for other in (dict(lib_sha256="cd" * 32), dict(kernel_name="render_cu_kernel<false,deep>"), dict(workload=wl.replace("512", "64"))):
         args = dict(kernel_name=kern, workload=wl, lib_sha256=sha)
         args.update(other)
         stale = bench.build_roofline(300.0, 2.0e12, 4.0e9, args["kernel_name"], args["workload"], args["lib_sha256"],
@@ -736,22 +736,27 @@ def test_no_called_function_reads_the_kernel_argument_segment():
     """Guard of a fault that happened once (round 2, gpurun_out/s1/t.log: "Fatal Python error: Aborted" in
     render_to_host): under code object v5 a non-inlined device function gets no
     kernel-argument pointer - __builtin_amdgcn_kernarg_segment_ptr() folds to null there and the first
-    scene access faults.  Rules held by the sources: the builtin appears in ONE place (cu_kargs of
-    render_cu_kernel.h); everything that calls cu_kargs is force-inlined into the kernel (VD) or is the
-    kernel; that header defines no __noinline__ function; and the __noinline__ vertex stage of the
-    development build's render_pool4_kernel takes the address of its argument block as (k_lo, k_hi)."""
+    scene access faults.  Rules held by every file of the directory: the builtin appears in ONE place
+    (cu_kargs of render_cu_kernel.h); everything that calls cu_kargs is force-inlined into the kernel (VD)
+    or is the kernel; and the only function that is not inlined is the texture fetch col_at_uv_mipmap of
+    render_kernels.h, a file that knows neither the builtin nor cu_kargs (it is included in front of them),
+    so that function gets the scene through its reference argument and nothing else."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "v-img_amd", "csrc")
-    users = {}
+    users, called = {}, []
     for name in sorted(os.listdir(csrc)):
         text = open(os.path.join(csrc, name)).read()
         code = re.sub(r"//[^\n]*", "", text)
         if "__builtin_amdgcn_kernarg_segment_ptr" in code:
             users[name] = code.count("__builtin_amdgcn_kernarg_segment_ptr")
+        if "noinline" in code:
+            assert "cu_kargs" not in code and "__builtin_amdgcn_kernarg_segment_ptr" not in code, name
+            assert code.count("noinline") == len(re.findall(r"__noinline__\s+\w+\s+\w+\s*\(", code)), name
+            called += [(name, f) for f in re.findall(r"__noinline__\s+\w+\s+(\w+)\s*\(", code)]
     assert users == {"render_cu_kernel.h": 1}, users
+    assert called == [("render_kernels.h", "col_at_uv_mipmap")], called
     cu = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "render_cu_kernel.h")).read())
-    assert "__noinline__" not in cu
     # every function of the header whose body calls cu_kargs() is VD (= __device__ __forceinline__) or __global__
     heads = [(m.start(), m.group(0)) for m in re.finditer(r"^(?:VD|__global__)[^\n;{]*\n?[^\n;{]*\{", cu, flags=re.M)]
     for m in re.finditer(r"cu_kargs\(\)", cu):
@@ -759,11 +764,6 @@ def test_no_called_function_reads_the_kernel_argument_segment():
         assert before, "cu_kargs() outside a function"
         assert before[-1][1].startswith(("VD", "__global__")), before[-1][1]
     assert len(list(re.finditer(r"cu_kargs\(\)", cu))) >= 4      # (definition, two stages, the kernel)
-    # the development build's non-inlined callee: block address through registers, never kernel arguments
-    p4 = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "render_pool4_kernel.h")).read())
-    sigs = re.findall(r"__noinline__\s+\w+\s+(\w+)\s*\(([^)]*)\)", p4)
-    assert sigs and all(args.strip().startswith("uint32_t k_lo, uint32_t k_hi") for _, args in sigs), sigs
-    assert all("DScene" not in args and "RenderArgs" not in args for _, args in sigs)
 
 
 def _kernel_notes(obj_path):

@@ -204,31 +204,6 @@ def test_errors_and_advance_only():
     acc.close()                                   # twice is harmless
 
 
-def test_development_schedulers_are_refused():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dev = os.path.join(root, "v-img_amd", "lib", "dev", "libvimg_hip.so")
-    assert os.path.exists(dev), "make dev"
-    code = (
-        "import sys; sys.path[:0] = [%r, %r]\n"
-        "import scenes\n"
-        "from vimg_amd import hip\n"
-        "s = scenes.json_scene('disney_spheres.json', res=(32, 16))\n"
-        "for name in ('pool', 'pool4', 'pool4g', 'stage'):\n"
-        "    d = hip.DeviceScene(s, scheduler=name)\n"
-        "    try:\n"
-        "        d.progressive(s.default_params())\n"
-        "        raise SystemExit(name + ' accepted')\n"
-        "    except hip.HipError as e:\n"
-        "        assert '[-3]' in str(e), str(e)\n"
-        "    d.close()\n"
-        "d = hip.DeviceScene(s, scheduler='cu')\n"
-        "d.progressive(s.default_params()).render(2)\n"
-        "print('REFUSED OK')\n") % (root, os.path.join(root, "tests"))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, VIMG_HIP_LIB=dev), capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0 and "REFUSED OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
-
-
 def test_cli_progressive_png_is_the_plain_runs(tmp_path):
     import vimg_amd
     exe = os.path.join(vimg_amd.abi.PKG_DIR, "bin", "vimg-amd")

@@ -2,7 +2,7 @@
 """Static attribution of a kernel's VALU instructions to source functions.
 Input: assembly from `hipcc -S -gline-tables-only --cuda-device-only`; for one kernel symbol, every
 instruction is credited to the innermost source line of its last .loc, lines are mapped to the
-enclosing function of render_kernels.h / render_pool_kernel.h by a brace scan.
+enclosing function of render_kernels.h / render_cu_kernel.h by a brace scan.
 Usage: tools/isa_attrib.py vimg_g.s <kernel-substring>"""
 import re, sys, collections, os
 asm, want = sys.argv[1], sys.argv[2]

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Frame time of one scheduler configuration on BASELINE config 2 (or a stand-in scene).
 Usage (GPU box): python tools/sched_bench.py <scheduler> [spp] [scene] [key=value ...]
-  scheduler: lane | pool | stage | auto;  scene: disney (default) | config3 | config4 | config5
-  key=value: VimgHipOptions fields (stage_slots=..., stage_seg_len=...), tile_world=N, tile_rank=R, res=WxH"""
+  scheduler: lane | cu | auto;  scene: disney (default) | config3 | config4 | config5
+  key=value: VimgHipOptions fields (pool_slots=..., cu_walkers=...), tile_world=N, tile_rank=R, res=WxH"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

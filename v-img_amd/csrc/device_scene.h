@@ -126,22 +126,23 @@ struct RenderArgs {
   uint32_t full_stats;
   uint32_t stack_entries;           // per-lane LDS stack depth (max_depth + 2)
   uint32_t lds_nodes;               // number of top-of-tree nodes staged into LDS
-  uint32_t stack_lds;               // pool4, deep trees: stack entries kept in LDS (== stack_entries: all of them);
+  // (the pool_* and stack_* fields below are read by the CU scheduler only; the lane-bound kernel's launches leave them 0)
+  uint32_t stack_lds;               // deep trees: stack entries kept in LDS (== stack_entries: all of them);
                                     // the LDS stack then has stack_lds + 1 rows (the last one takes the writes above)
-  VIMG_GLOBAL uint32_t* stack_ovf;  // pool4: the entries beyond, [wave of the grid][entry - stack_lds][lane] (scene-owned scratch)
-  VIMG_GLOBAL v4u* pool_cold;       // pooled kernel: cold slot records, [wave][slot][record] (scene-owned scratch)
-  uint32_t lds_leaf;                // pooled kernel: number of leaf records copied to LDS (all or 0)
-  VIMG_GLOBAL v4u* pool_state;      // pooled kernel: per work item {rng lo, rng hi, epoch + segments done, -}{acc.xyz, -}
-  uint32_t pool_segments;           // pooled kernel: segments a pixel's samples are split into (>= 1)
-  uint32_t pool_seg_len;            // pooled kernel: samples per segment
-  uint32_t pool_epoch;              // pooled kernel: tag base of this launch (stale records of earlier launches never match)
-  uint32_t pool_slots;              // pooled kernel: path slots per wave (0 = lane-bound kernel)
-  uint32_t pool_refill;             // pooled kernel: finished rays that trigger a refill pass
-  uint32_t pool_vbatch;             // pooled kernel: queued slots of one class that start a vertex batch
-  uint32_t pool_boxmin;             // pooled kernel: leave the box loop when fewer lanes than this still descend (0 = never)
-  uint32_t pool_starve;             // pooled kernel: idle walk lanes (with no ray queued) that force a partial vertex batch
-  uint32_t pool_gbreak;             // pool4 group build: a wave leaves the walk for a full batch only with this many rays or fewer in its lanes
-  uint32_t pool_classes;            // pooled kernel: vertex queues: 1 = one, 2 = Principled apart, 3 = + Lambertian apart
+  VIMG_GLOBAL uint32_t* stack_ovf;  // the entries beyond, per walking wave of the grid [entry - stack_lds][lane] (scene-owned scratch)
+  VIMG_GLOBAL v4u* pool_cold;       // cold slot records, one region per workgroup (scene-owned scratch)
+  uint32_t lds_leaf;                // number of leaf records copied to LDS (all or 0)
+  VIMG_GLOBAL v4u* pool_state;      // per work item {rng lo, rng hi, epoch + segments done, -}{acc.xyz, -}
+  uint32_t pool_segments;           // segments a pixel's samples are split into (>= 1)
+  uint32_t pool_seg_len;            // samples per segment
+  uint32_t pool_epoch;              // tag base of this launch (stale records of earlier launches never match)
+  uint32_t pool_slots;              // path slots per workgroup (0 = lane-bound kernel)
+  uint32_t pool_refill;             // finished rays of a walking wave that trigger hand-over and refill
+  uint32_t pool_vbatch;             // queued slots of one class that start a vertex batch
+  uint32_t pool_boxmin;             // leave the box loop when fewer lanes than this still descend (0 = never)
+  uint32_t pool_starve;             // smallest partial vertex batch a wave takes at once
+  uint32_t pool_gbreak;             // unused (a retired scheduler's; kept for the layout)
+  uint32_t pool_classes;            // vertex queues: 1 = one, 2 = Principled apart, 3 = + Lambertian apart
   uint32_t cu_walkers;              // CU scheduler: waves [0, cu_walkers) own traversal stacks and walk; the others only shade
   uint32_t cu_flex;                 // CU scheduler: bit 0 = a walking wave that holds no ray may run a vertex batch
   uint32_t cu_lowwater;             // CU scheduler: partial vertex batches only while fewer rays than this wait in the walk ring
@@ -164,8 +165,8 @@ struct RenderArgs {
 struct DeviceStats {
   unsigned long long closest, shadow, internal, leaf, prim, sphere, nan_samples;
   unsigned long long trip_descend, trip_prim, iterations;   // wave-level loop trips (diagnostic)
-  // -DVIMG_PROFILE builds only (make prof): s_memtime cycles of wave 0.. summed over waves, per
-  // stage of render_pool_kernel, and lanes switched on per vertex batch
+  // render_cu_kernel, statistics launches: per stage cycles [0..5], batches [6..10] and their slots [11..15];
+  // the walk's passes, rounds, sessions and refills [16..22]; looks for work and the ring counts seen [23..27]
   unsigned long long prof[28];
   unsigned long long wait_cyc[5], wait_n[5];   // render_cu_kernel, statistics launches: cycles slots waited in the rings (vertex 0-3, walk), and how many
   unsigned long long px_done[3];    // render_cu_kernel, statistics launches: when pixels finished (10 ns ticks since their workgroup started): sum, count, latest
@@ -174,9 +175,5 @@ struct DeviceStats {
   unsigned long long pv_cyc[7];     // ... Principled batches: cycles in state loads, hit record + path logic, light sample, BSDF sample, evaluations, stores + hand-over; batches
   unsigned long long walk_cyc[4];   // render_cu_kernel, statistics launches: cycles of the walk sessions in refill + set-up, box loop, leaf rounds, hand-over
 };
-enum : int { PF_TOTAL = 0, PF_V_LOAD, PF_V_LIGHT, PF_V_SAMPLE, PF_V_EVAL, PF_V_FINISH, PF_V_STORE,
-             PF_W_REFILL, PF_W_BOX, PF_W_LEAF, PF_W_RETIRE, PF_V_BATCHES, PF_V_LANES, PF_V_ATVERTEX,
-             PF_W_ROUNDS, PF_CLS_CYC0, PF_CLS_CYC1, PF_CLS_CYC2, PF_CLS_CYC3, PF_CLS_LANES0, PF_CLS_LANES1,
-             PF_CLS_LANES2, PF_CLS_LANES3, PF_DRAIN, PF_MAXWAVE, PF_COUNT };
 
 }  // namespace vimg

@@ -2,7 +2,6 @@
 //   vimg_hip.hip       init / options / last_error, the render entry points, enqueue_render
 //   scene_upload.hip   validation, baking and upload of a scene, its changes, its release
 //   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel
-//   launch_dev.hip     the retired schedulers POOL / POOL4 / POOL4G / STAGE (development build; stubs otherwise)
 //   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
 //   scene_rebuild.hip  a new tree for a resident scene, its cost       bvh_build.hip    the GPU builders and their cores
 #pragma once
@@ -16,8 +15,6 @@
 #include "../../include/vimg_hip.h"
 #include "device_scene.h"
 #include "kernel_tus.h"
-
-struct DevSchedState;   // launch_dev.hip
 
 struct VimgDeviceScene {
   vimg::DScene d{};
@@ -33,15 +30,14 @@ struct VimgDeviceScene {
   vimg::DeviceStats* d_stats = nullptr;
   unsigned int* d_counter = nullptr;
   float* d_frame = nullptr;
-  void* d_pool_cold = nullptr;   // pooled kernel: cold slot records of every resident wave
+  void* d_pool_cold = nullptr;   // CU scheduler: cold slot records of every workgroup
   size_t pool_cold_bytes = 0;
-  void* d_stack_ovf = nullptr;   // pool4, deep trees: the stack entries beyond the LDS part, per resident wave
+  void* d_stack_ovf = nullptr;   // CU scheduler, deep trees: the stack entries beyond the LDS part, per walking wave
   size_t stack_ovf_bytes = 0;
-  void* d_pool_state = nullptr;  // pooled kernel: per-pixel record between sample segments
+  void* d_pool_state = nullptr;  // CU scheduler: per-pixel record between sample segments
   size_t pool_state_bytes = 0;
   uint32_t pool_epoch = 0;       // bumped per launch: tags of earlier launches never match
   size_t frame_floats = 0;
-  DevSchedState* dev = nullptr;  // buffers of the retired schedulers (development build; null until one of them launches)
   // geometry updates (vimg_hip_scene_update_geometry): what the upload knew of the tables and the tree
   uint64_t generation = 0;       // bumped by every change of the resident scene; accumulators remember theirs
   uint32_t num_vertices = 0, num_tris = 0, num_spheres = 0;
@@ -98,14 +94,11 @@ inline uint32_t opt_or(int32_t v, uint32_t dflt) { return v == VIMG_OPT_AUTO ? d
 struct LaunchCfg {
   RenderArgs args;
   uint32_t grid, lds_bytes;
-  int sched;     // VIMG_SCHED_* of this launch
-  bool pooled;   // render_pool_kernel for this launch
+  int sched;     // VIMG_SCHED_CU or VIMG_SCHED_LANE
   int wps;       // register-budget build (waves per SIMD of __launch_bounds__)
-  int rays;      // pool4: rays a lane walks at the same time (1; two measured slower and are not built)
-  bool group;    // pool4: one pool and one set of queues per workgroup (VIMG_SCHED_POOL4G) instead of per wave
-  bool deep;     // pooled / staged kernel: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)
+  bool deep;     // CU scheduler: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)
   int cu_waves;  // CU scheduler: waves per workgroup (16 or 8)
-  size_t cold_bytes;   // scene-owned scratch of the launch: cold slot records of every resident wave (0: none) ...
+  size_t cold_bytes;   // scene-owned scratch of the launch: cold slot records of every workgroup (0: none) ...
   size_t ovf_bytes;    // ... and the stack entries beyond stack_lds (0: the stacks fit)
 };
 
@@ -139,18 +132,6 @@ uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint6
 // build for `stats`, the early-ray build for cu_flex bit 5)
 const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c);
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
-
-// ---- launch_dev.hip: the schedulers POOL, POOL4, POOL4G and STAGE.  Without -DVIMG_DEV_SCHEDULERS the
-// upload refuses them (kNoDevSchedulers) and these are stubs that answer the same.
-inline constexpr const char* kNoDevSchedulers =
-    "options: the schedulers POOL, POOL4, POOL4G and STAGE are reference implementations "
-    "of the development build (make dev), not part of this library";
-LaunchCfg dev_make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
-const void* dev_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, const char** name);
-// enqueues the launch (its queue resets, argument block and kernel) on `st`; ev0 is recorded right before the kernel
-int dev_enqueue(VimgDeviceScene* s, const LaunchCfg& c, float* d_out, DeviceStats* stats, hipStream_t st, hipEvent_t ev0);
-int dev_error_word(const VimgDeviceScene* s, unsigned int* word);   // the staged kernel's own error word (0 without one)
-void dev_free(VimgDeviceScene* s);
 
 }  // namespace vimg
 #pragma GCC visibility pop

@@ -1,8 +1,7 @@
 // The launch policy of the product: which kernel a launch runs and with what grid, LDS layout and scheduler
 // parameters.  Policy (AUTO): the CU-wide scheduler (render_cu_kernel) for every launch - whole frames, thin
 // shards, trace_pixel.  The lane-bound kernel runs when asked for by name and for frames wider than the 16-bit
-// pixel coordinates of the slot records; the schedulers of rounds 1 and 2 by name, in the development build
-// (launch_dev.hip).
+// pixel coordinates of the slot records.
 #include <cmath>
 
 #include "hip_internal.h"
@@ -81,9 +80,6 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   const VimgHipOptions& o = s->opt;
   const uint64_t items = (sx >= 0) ? 1 : uint64_t(local_tiles(s, p)) * 64u;
   c.sched = VIMG_SCHED_CU;
-  c.pooled = true;
-  c.group = false;
-  c.rays = 1;
   c.wps = 4;
   c.cu_waves = 16;   // (a build with two 8-wave workgroups per CU halves the pool a batch draws from; not built)
   const uint32_t nw = uint32_t(c.cu_waves);
@@ -99,7 +95,6 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   a.cu_sleep = std::min(127u, std::max(1u, opt_or(o.cu_sleep, 4u)));
   a.pool_starve = std::min(64u, std::max(1u, opt_or(o.pool_starve, 16u)));   // smallest partial batch worth a wave at once
   a.pool_classes = std::min(3u, std::max(1u, opt_or(o.pool_classes, 3u)));
-  a.pool_gbreak = 0;
   // LDS of the workgroup: the whole CU's (16 waves) or half of it, minus a margin
   const uint32_t share = (160u * 1024u) / (16u / nw) - 1024u;
   uint32_t node_budget = 4608u;
@@ -119,7 +114,7 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   // (stand-ins of configs 4 / 5: an eighth of the frame at 128 spp 82.8 / 77.9 against 93.3 / 82.3 ms,
   // a quarter 87.7 against 92.2, a half 101.9 against 107.8, the whole frame unchanged)
   a.pool_refill = std::max(1u, opt_or(o.pool_refill, c.deep ? 2u : 16u));
-  const uint32_t stack_rows = pool4_stack_rows_of(a.stack_entries, a.stack_lds);
+  const uint32_t stack_rows = cu_stack_rows_of(a.stack_entries, a.stack_lds);
   uint32_t leaf_bytes = 0;
   a.lds_leaf = 0;
   if (s->num_leaf_prims * 48u <= 4096u && o.lds_leaf != 0) {
@@ -175,7 +170,7 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   per_cu = std::min<int>(per_cu, int(16u / nw));
   const uint64_t need_blocks = (items + slots - 1) / slots;
   c.grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(need_blocks, uint64_t(s->num_cus) * per_cu)));
-  // segments: as the group build of render_pool4_kernel (the tail of a frame is one segment long)
+  // segments (the tail of a frame is one segment long)
   a.cu_watchdog = static_cast<uint32_t>(1000000000ull >> 20);
   if (sx < 0) {
     const uint32_t len = segments_for(s, p, items, uint64_t(c.grid) * slots, 176.0, 64.0, &a);
@@ -187,17 +182,16 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
 // the scene-owned scratch of a CU launch: one cold region per workgroup, one overflow stack per walking wave
 void cu_scratch(const VimgDeviceScene* s, LaunchCfg& c) {
   const RenderArgs& a = c.args;
-  c.cold_bytes = size_t(c.grid) * pool4_cold_records(s->textured) * a.pool_slots * 16u;
+  c.cold_bytes = size_t(c.grid) * cu_cold_records(s->textured) * a.pool_slots * 16u;
   if (a.stack_lds < a.stack_entries)
-    c.ovf_bytes = size_t(c.grid) * a.cu_walkers * uint32_t(c.rays) * (a.stack_entries - a.stack_lds) * 256u;
+    c.ovf_bytes = size_t(c.grid) * a.cu_walkers * (a.stack_entries - a.stack_lds) * 256u;
 }
 
 }  // namespace
 
 const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
   if (c.sched == VIMG_SCHED_CU) return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves));
-  if (c.sched == VIMG_SCHED_LANE) return reinterpret_cast<const void*>(vimg_lane_kernel(s->textured, c.wps));
-  return dev_kernel_of(s, c, nullptr);
+  return reinterpret_cast<const void*>(vimg_lane_kernel(s->textured, c.wps));
 }
 
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
@@ -214,7 +208,6 @@ LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, 
   // caches (latency-bound) and 2 on small ones (VALU-bound, fewest spills)
   c.wps = s->waves_per_simd;
   if (o.waves_per_simd != VIMG_OPT_AUTO) c.wps = o.waves_per_simd >= 3 ? 3 : 2;
-  c.rays = 1;
   RenderArgs& a = c.args = base_args(s, p, sx, sy);
   a.stack_lds = a.stack_entries;
   // LDS budget per 256-thread workgroup: stacks first, then as much of the top of the tree as
@@ -226,10 +219,6 @@ LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, 
   if (stack_bytes + 512 < budget) nodes = (budget - stack_bytes - 256) / 56u;
   a.lds_nodes = std::min(nodes, s->d.num_nodes);
   c.lds_bytes = ((a.lds_nodes * 56u + 255u) & ~255u) + stack_bytes;
-  // (queue parameters of the pooled kernels: the lane-bound kernel reads none of them)
-  a.pool_gbreak = std::min(64u, opt_or(o.pool_gbreak, 32u));
-  a.pool_classes = std::min(3u, std::max(1u, opt_or(o.pool_classes, 3u)));
-  a.pool_starve = std::min(64u, std::max(1u, opt_or(o.pool_starve, 24u)));
   // persistent grid: as many 4-wave workgroups as the kernel's registers and LDS let a CU hold
   // (asked of the runtime), never more than the work
   int per_cu = 0;
@@ -242,9 +231,8 @@ LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, 
 }
 
 LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
-  const int sched = s->opt.scheduler;
-  if (s->too_wide || sched == VIMG_SCHED_LANE) return make_launch_lane(s, p, sx, sy);   // slots pack pixel coordinates in 16 bits
-  if (sched != VIMG_OPT_AUTO && sched != VIMG_SCHED_CU) return dev_make_launch(s, p, sx, sy);
+  // (the upload admits the schedulers AUTO, LANE and CU only)
+  if (s->too_wide || s->opt.scheduler == VIMG_SCHED_LANE) return make_launch_lane(s, p, sx, sy);   // slots pack pixel coordinates in 16 bits
   LaunchCfg c = make_launch_cu(s, p, sx, sy);
   cu_scratch(s, c);
   return c;
@@ -265,10 +253,7 @@ const char* vimg_hip_launch_kernel(const VimgDeviceScene* s, const VimgRenderPar
   if (p->tile_world == 0 || p->tile_rank >= p->tile_world) return "";
   const LaunchCfg c = make_launch(s, p, -1, -1);
   if (c.sched == VIMG_SCHED_CU) return cu_names[s->textured ? 1 : 0][c.deep ? 1 : 0];
-  if (c.sched == VIMG_SCHED_LANE) return lane_names[s->textured ? 1 : 0][c.wps >= 3 ? 1 : 0];
-  const char* name = "";
-  (void)dev_kernel_of(s, c, &name);
-  return name;
+  return lane_names[s->textured ? 1 : 0][c.wps >= 3 ? 1 : 0];
 }
 
 const char* vimg_hip_scene_kernel(const VimgDeviceScene* s) {

@@ -1,7 +1,8 @@
 // CU-wide scheduler: ONE pool of path slots per compute unit, waves with ROLES, queues without a lock.
 //
-// What round 2's default (render_pool4_kernel<..., group>) measured, and what this build changes:
-//  * every queue operation of a wave ran under one workgroup lock: 19 % of the wave cycles of a
+// The design answers what round 2's pooled scheduler measured (a pool of slots per workgroup of four waves,
+// removed from the tree; `git show a486e20:v-img_amd/csrc/render_pool4_kernel.h` is the last commit with it):
+//  * there every queue operation of a wave ran under one workgroup lock: 19 % of the wave cycles of a
 //    config-2 frame (760 cycles to get it, 2 300 to release, profiles/r2_final/walk_diag_*).
 //    Here the five queues are multi-producer / multi-consumer TICKET RINGS in LDS: a producer
 //    reserves with one returning ds_add on the ring's tail, writes its entries, then adds to the
@@ -9,12 +10,12 @@
 //    claims indices with one returning ds_add on the head and reads its entries (an entry whose
 //    producer has reserved but not yet written reads EMPTY: the consumer re-reads).  No wave
 //    ever waits for another wave's critical section.
-//  * the vertex stage was a CALL out of the walk loop with the walk's lane state in callee-saved
+//  * there the vertex stage was a CALL out of the walk loop with the walk's lane state in callee-saved
 //    registers: 0.7 TB of scratch traffic per frame and rays that stand still while their wave
 //    shades.  Here a wave is a WALKER or a SHADER for as long as it holds state: walkers only walk
 //    (and may run a batch when they hold no ray at all), shaders only run vertex batches; nothing
 //    is live across a stage, every stage body is inlined, there is no call and no scratch.
-//  * a vertex walked its shadow ray and THEN its path ray (two hops through the walk queue).  All
+//  * there a vertex walked its shadow ray and THEN its path ray (two hops through the walk queue).  All
 //    draws of a vertex precede both rays (src/integrators/mis_integrator.cpp:45-120), so both
 //    are queued together and walked by whichever lanes are free; the second one to finish (an
 //    atomic OR on the slot's flag word tells) hands the slot to the vertex queue of its class.
@@ -38,13 +39,42 @@
 //  * stacks for all sixteen waves (they fit beside 1 280 slots) and shading waves that walk while no
 //    batch waits for them, taking rays only until a full batch does: config 2 297.5 against 296.9 ms
 //    at any threshold of 32 to 512 waiting rays - the shading side has no idle time worth lending.
-// Same device functions, same order of operations per path as every other scheduler: bit-identical.
+// Same device functions, same order of operations per path as the lane-bound render_kernel: bit-identical.
 #pragma once
 #include <type_traits>
 
-#include "sched_common.h"
+#include "render_kernels.h"
 
 namespace vimg {
+
+// Cold records of a slot, 16 bytes each, in the workgroup's region of global memory: the four every vertex
+// batch reads and writes are ONE aligned 64-byte line, [slot][4]; the pixel accumulator (finisher batches
+// only) and the ray cone (textured build only) live in planes of their own behind them, so that a vertex
+// batch moves one line per slot and not two
+enum : uint32_t {
+  SC_THROUGHPUT = 0,   // throughput.xyz | eta_scale
+  SC_RESULT,           // bounce_result.xyz | prev_pdf
+  SC_NEE,              // unoccluded next-event contribution.xyz | -
+  SC4_RNG,             // rng lo | rng hi | px + (py << 16) | sample index
+  SC4_MAIN             // records of the main line
+};
+// 16-byte records per slot in a cold region: main line + accumulator + cone
+__host__ __device__ constexpr uint32_t cu_cold_records(bool tex) { return SC4_MAIN + 1u + (tex ? 1u : 0u); }
+// rows of a lane's LDS stack: all entries, or the first stack_lds and one more that takes the
+// writes of the entries kept in global memory
+__host__ __device__ constexpr uint32_t cu_stack_rows_of(uint32_t entries, uint32_t in_lds) { return in_lds < entries ? in_lds + 1u : entries; }
+constexpr uint32_t SLOT_IDLE = 0xffffffffu;   // a walking lane that holds no ray
+
+// words of a pixel's between-segments record: agent-scope relaxed atomics (global_load/store sc1)
+VD void state_store(VIMG_GLOBAL uint32_t* p, uint32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+VD uint32_t state_load(VIMG_GLOBAL uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+VD uint32_t lane_rank(unsigned long long mask, uint32_t lane) {
+  return __popcll(mask & ((1ull << lane) - 1ull));
+}
 
 // flag word of a slot (CR_DIR.w).  The shader writes it whole; walkers OR their result bits in.
 enum : uint32_t {
@@ -104,7 +134,7 @@ __host__ __device__ constexpr uint32_t cu_pool_bytes(uint32_t slots, uint32_t wa
   return CU_LDS_BYTES * slots + uint32_t(sizeof(CuCtl)) + waves * uint32_t(sizeof(CuWaveRec));
 }
 // divisor d -> (magic, shift) with n / d == mulhi(n, magic) >> shift for every n < 2^31
-// (Granlund & Montgomery; host side in vimg_hip.hip:make_launch)
+// (Granlund & Montgomery; host side in launch_policy.hip:magic_div)
 VD uint32_t cu_mod(uint32_t n, uint32_t d, uint32_t magic, uint32_t shift) { return n - d * (__umulhi(n, magic) >> shift); }
 VD int32_t lds_add_rtn(VIMG_LDS int32_t* p, int32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 VD uint32_t lds_add_rtn(VIMG_LDS uint32_t* p, uint32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -154,7 +184,7 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] const bool material_mode = (A.integrator == VIMG_INTEGRATOR_MATERIAL);                               \
   [[maybe_unused]] const uint32_t P = A.pool_slots;                                                                     \
   [[maybe_unused]] const bool can_walk = wave < A.cu_walkers;                                                           \
-  const uint32_t stack_rows_ = pool4_stack_rows_of(A.stack_entries, A.stack_lds);                                       \
+  const uint32_t stack_rows_ = cu_stack_rows_of(A.stack_entries, A.stack_lds);                                          \
   const uint32_t node_bytes_ = (lds_node_bytes(A.lds_nodes) + 255u) & ~255u;                                            \
   [[maybe_unused]] VIMG_LDS uint32_t* stack0 =                                                                          \
       reinterpret_cast<VIMG_LDS uint32_t*>((VIMG_LDS unsigned char*)lds_raw + node_bytes_) +                            \
@@ -183,7 +213,7 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] const uint32_t box_min = A.pool_boxmin;                                                              \
   /* cold records of the workgroup's slots in global memory: [slot][4] main lines (throughput, result, NEE term, RNG),  \
      then the accumulator plane, then the cone plane (textured build) */                                                \
-  [[maybe_unused]] VIMG_GLOBAL v4u* cold = A.pool_cold + size_t(blockIdx.x) * (size_t(pool4_cold_records(TEX)) * P);    \
+  [[maybe_unused]] VIMG_GLOBAL v4u* cold = A.pool_cold + size_t(blockIdx.x) * (size_t(cu_cold_records(TEX)) * P);       \
   [[maybe_unused]] VIMG_GLOBAL v4u* cold_acc = cold + size_t(SC4_MAIN) * P;                                             \
   [[maybe_unused]] VIMG_GLOBAL v4u* cold_cone = cold_acc + P;                                                           \
   [[maybe_unused]] auto crd = [&](uint32_t r, uint32_t slot) -> v4u { return cold[slot * SC4_MAIN + r]; };              \
@@ -300,7 +330,7 @@ VD CuKPtr cu_kargs() {
   }
 
 // ======================================================================== one vertex batch
-// (the body is render_pool4_kernel's vertex stage; FIN: the finisher queue, MTC: material the shading
+// (FIN: the finisher queue, MTC: material the shading
 // is specialised for, -1 = any).  `n` slots; lane i < n holds its slot id in `slot`.
 template <bool TEX, int NW, bool DIAG, int EARLY, bool FIN, int MTC>
 VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan, uint32_t& n_dead) {

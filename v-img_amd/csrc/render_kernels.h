@@ -115,16 +115,6 @@ VD f3 sample_sphere_cap(float rand1, float rand2, float cos_theta_max) {
   float y = sn * sin_theta;
   return f3{x, y, cos_theta};
 }
-VD f3 sample_hemisphere_cosine(float rand1, float rand2) {
-  float phi = 2 * kPi * rand1;
-  float cos_theta = sqrt_f(rand2);
-  float sin_theta = sqrt_f(1 - cos_theta * cos_theta);
-  double sn, cs;
-  D_sincos(phi, sn, cs);
-  float x = static_cast<float>(cs) * sin_theta;
-  float y = static_cast<float>(sn) * sin_theta;
-  return f3{x, y, cos_theta};
-}
 
 // ================================================================================ records
 struct RayCone {
@@ -155,12 +145,8 @@ VD Scatter no_scatter() { return Scatter{f3{0.f, 0.f, 0.f}, 0.f, false, false}; 
 
 struct Counters {
   uint32_t closest, shadow, internal, leaf, prim, sphere;
-  uint32_t trip_descend, trip_prim;   // wave-level loop trips (credited to the first active lane)
+  uint32_t trip_descend, trip_prim;   // wave-level loop trips (no kernel that remains counts them: 0)
 };
-VD bool first_active_lane() {
-  const unsigned long long m = __ballot(1);
-  return (threadIdx.x & 63u) == static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1);
-}
 
 // ONB helpers: reference include/hit_utils.h:32-59
 VD f3 xform_with_onb(const Onb& o, f3 v) { return o.u * v.x + o.v * v.y + o.w * v.z; }
@@ -190,10 +176,6 @@ VD f3 load3k(const float* p) { return f3{p[0], p[1], p[2]}; }   // kernel-argume
 VD VimgPrim load_prim(gptr<VimgPrim> p) {
   v2u v = *reinterpret_cast<const VIMG_GLOBAL v2u*>(p);
   return VimgPrim{v.x, v.y};
-}
-VD VimgLight load_light(gptr<VimgLight> p) {
-  v2u v = *reinterpret_cast<const VIMG_GLOBAL v2u*>(p);
-  return VimgLight{v.x, v.y};
 }
 
 // ================================================================================ ray cones
@@ -442,45 +424,9 @@ VD float diff_of_products_double(float a, float b, float c, float d) {
   double cd = c * d;
   return static_cast<float>(__builtin_fma(static_cast<double>(a), static_cast<double>(b), -cd));
 }
-// Triangle::tri_hit_template: reference include/geometry/triangle.h:74-180
-VD bool tri_test(f3 p0, f3 p1, f3 p2, const TravRay& ray, const TriRayConst& rc, float& t_out,
-                 float& e0o, float& e1o, float& e2o, float& inv_det_o) {
-  f3 p0t = permute(p0 - ray.o, rc.kz);
-  f3 p1t = permute(p1 - ray.o, rc.kz);
-  f3 p2t = permute(p2 - ray.o, rc.kz);
-  p0t.x += rc.sx * p0t.z;
-  p0t.y += rc.sy * p0t.z;
-  p1t.x += rc.sx * p1t.z;
-  p1t.y += rc.sy * p1t.z;
-  p2t.x += rc.sx * p2t.z;
-  p2t.y += rc.sy * p2t.z;
-  float e0 = diff_of_products(p1t.x, p2t.y, p1t.y, p2t.x);
-  float e1 = diff_of_products(p2t.x, p0t.y, p2t.y, p0t.x);
-  float e2 = diff_of_products(p0t.x, p1t.y, p0t.y, p1t.x);
-  if (e0 == 0.f || e1 == 0.f || e2 == 0.f) {
-    e0 = diff_of_products_double(p1t.x, p2t.y, p1t.y, p2t.x);
-    e1 = diff_of_products_double(p2t.x, p0t.y, p2t.y, p0t.x);
-    e2 = diff_of_products_double(p0t.x, p1t.y, p0t.y, p1t.x);
-  }
-  if ((e0 < 0 || e1 < 0 || e2 < 0) && (e0 > 0 || e1 > 0 || e2 > 0)) return false;
-  float det = e0 + e1 + e2;
-  if (det == 0) return false;
-  p0t.z *= rc.sz;
-  p1t.z *= rc.sz;
-  p2t.z *= rc.sz;
-  float t_scaled = e0 * p0t.z + e1 * p1t.z + e2 * p2t.z;
-  if (det < 0 && (t_scaled >= 0 || t_scaled < ray.max_t * det || t_scaled > ray.min_t * det))
-    return false;
-  else if (det > 0 && (t_scaled <= 0 || t_scaled > ray.max_t * det || t_scaled < ray.min_t * det))
-    return false;
-  float inv_det = 1.f / det;
-  t_out = t_scaled * inv_det;
-  e0o = e0, e1o = e1, e2o = e2, inv_det_o = inv_det;
-  return true;
-}
-// The same test with its rejections folded into one predicate (one exec-mask region for the
-// hit instead of one per early return: the primitive loop of the walk is dominated by mask
-// bookkeeping otherwise).  Comparisons keep the reference's form, so NaN operands take the same
+// Triangle::tri_hit_template (reference include/geometry/triangle.h:74-180) with its rejections folded
+// into one predicate (one exec-mask region for the hit instead of one per early return: the primitive
+// loop of the walk is dominated by mask bookkeeping otherwise).  Comparisons keep the reference's form, so NaN operands take the same
 // way out (every ordered comparison false -> accepted, as in the reference).
 VD bool tri_test_flat(f3 p0, f3 p1, f3 p2, const TravRay& ray, const TriRayConst& rc, float& t_out,
                       float& e0o, float& e1o, float& e2o, float& inv_det_o) {
@@ -594,8 +540,8 @@ VD bool traverse(const DScene& g, const Lds& L, TravRay& ray, HitRec& rec, Count
   uint32_t cur = g.root_ref;
   bool found = false;
   const uint32_t stat_inc = full_stats ? 1u : 0u;   // event counters without a branch in the loops
-  // the box loop in two builds (see render_pool_kernel.h): only a wave that carries a ray with a
-  // zero direction component runs the one with the exact select form of the slab test
+  // the box loop in two builds: only a wave that carries a ray with a zero direction component runs
+  // the one with the exact select form of the slab test
   auto box_loop = [&](auto exact_possible) {
     while (cur != REF_DONE && ref_count(cur) == 0) {
       v4f na, nb, nc;

@@ -170,10 +170,7 @@ void options_from_env(VimgHipOptions* o) {
       {"VIMG_HIP_POOL_REFILL", &o->pool_refill},       {"VIMG_HIP_POOL_VBATCH", &o->pool_vbatch},
       {"VIMG_HIP_POOL_CLASSES", &o->pool_classes},     {"VIMG_HIP_POOL_STARVE", &o->pool_starve},
       {"VIMG_HIP_POOL_BOXMIN", &o->pool_boxmin},       {"VIMG_HIP_LDS_LEAF", &o->lds_leaf},
-      {"VIMG_HIP_STAGE_SLOTS", &o->stage_slots},       {"VIMG_HIP_STAGE_SEG_LEN", &o->stage_seg_len},
-      {"VIMG_HIP_STAGE_WCHUNK", &o->stage_wchunk},     {"VIMG_HIP_STAGE_WALK_QUOTA", &o->stage_walk_quota},
-      {"VIMG_HIP_POOL4_RAYS", &o->pool4_rays},             {"VIMG_HIP_LDS_STACK", &o->lds_stack},
-      {"VIMG_HIP_POOL_GBREAK", &o->pool_gbreak},       {"VIMG_HIP_CU_WAVES", &o->cu_waves},
+      {"VIMG_HIP_LDS_STACK", &o->lds_stack},           {"VIMG_HIP_CU_WAVES", &o->cu_waves},
       {"VIMG_HIP_CU_WALKERS", &o->cu_walkers},         {"VIMG_HIP_CU_FLEX", &o->cu_flex},
       {"VIMG_HIP_CU_LOWWATER", &o->cu_lowwater},       {"VIMG_HIP_CU_PATIENCE", &o->cu_patience},
       {"VIMG_HIP_CU_JOIN", &o->cu_join},               {"VIMG_HIP_CU_SLEEP", &o->cu_sleep}};
@@ -473,9 +470,10 @@ int resolve_options(VimgDeviceScene* s, const VimgHipOptions* opts) {
   if (const char* e = getenv("VIMG_HIP_QUERY_BLOCKS")) s->query_launch = atoi(e) != 0 ? 1 : 0;
   if (s->opt.scheduler != VIMG_OPT_AUTO && (s->opt.scheduler < VIMG_SCHED_LANE || s->opt.scheduler > VIMG_SCHED_CU))
     return fail(VIMG_E_INVALID, "options: unknown scheduler");
-  if (s->opt.scheduler != VIMG_OPT_AUTO && s->opt.scheduler != VIMG_SCHED_LANE && s->opt.scheduler != VIMG_SCHED_CU &&
-      !vimg_has_dev_schedulers())
-    return fail(VIMG_E_UNSUPPORTED, kNoDevSchedulers);
+  // the one gate: every launch builder relies on a resident scene's scheduler being AUTO, LANE or CU
+  if (s->opt.scheduler != VIMG_OPT_AUTO && s->opt.scheduler != VIMG_SCHED_LANE && s->opt.scheduler != VIMG_SCHED_CU)
+    return fail(VIMG_E_UNSUPPORTED, "options: the schedulers POOL, POOL4, POOL4G and STAGE are retired; "
+                                    "the library renders with CU (AUTO) or LANE");
   s->too_wide = (s->d.res_x > 65535 || s->d.res_y > 65535);   // slots pack pixel coordinates in 16 bits
   return VIMG_OK;
 }
@@ -559,7 +557,6 @@ int vimg_hip_scene_free(VimgDeviceScene* s) {
   for (void* q : {(void*)s->d_stats, (void*)s->d_counter, (void*)s->d_root_box, (void*)s->d_frame, s->d_pool_cold, s->d_stack_ovf,
                   s->d_pool_state})
     if (q) (void)hipFree(q);
-  dev_free(s);
   delete s;
   return VIMG_OK;
 }

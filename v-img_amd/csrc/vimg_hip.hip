@@ -1,7 +1,7 @@
 // libvimg_hip.so - C ABI (include/vimg_hip.h) over the gfx950 kernels in render_kernels.h.  This unit holds
 // the render entry points and the one path every render takes (enqueue_render); the scene's upload, the
-// launch policy, the retired schedulers, the ray queries and the pre / post steps have units of their
-// own (hip_internal.h).  There is no CPU render path in this library.
+// launch policy, the ray queries and the pre / post steps have units of their own (hip_internal.h).  There is
+// no CPU render path in this library.
 #include <cstdio>
 #include <cstdlib>
 
@@ -54,9 +54,9 @@ int check_params(const VimgDeviceScene* s, const VimgRenderParams* p) {
   return VIMG_OK;
 }
 
-// The pooled kernels keep the cold records of their path slots in global memory, and deep trees the stack
-// entries beyond the LDS part: one region per resident wave, owned by the scene and grown on demand (42 MB
-// for config 2 on 256 CUs); and a per-pixel record between sample segments.
+// The CU scheduler keeps the cold records of its path slots in global memory, and deep trees the stack
+// entries beyond the LDS part: one region per workgroup (per walking wave), owned by the scene and grown on
+// demand (42 MB for config 2 on 256 CUs); and a per-pixel record between sample segments.
 int ensure_pool(VimgDeviceScene* s, LaunchCfg& c) {
   c.args.pool_cold = nullptr;
   if (!c.cold_bytes) return VIMG_OK;
@@ -99,10 +99,6 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, 
                    hipEvent_t ev1 = nullptr, const ProgLaunch* prog = nullptr) {
   LaunchCfg c = make_launch(s, p, sx, sy);
   if (prog) {
-    // only the two schedulers of the product library carry a pixel across launches
-    if (c.sched != VIMG_SCHED_CU && c.sched != VIMG_SCHED_LANE)
-      return fail(VIMG_E_UNSUPPORTED, "progressive rendering: the schedulers POOL, POOL4, POOL4G and STAGE of the "
-                                      "development build do not resume pixels across launches");
     c.args.sample_base = prog->base;
     c.args.spp_div = static_cast<float>(prog->base + p->samples);   // (the caller keeps the total <= UINT32_MAX)
     c.args.prog_in = (const VIMG_GLOBAL v4u*)prog->in;
@@ -123,35 +119,29 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, 
     CuKArgs ka{s->d, c.args, d_out, stats, s->d_counter};
     void* kargs[] = {&ka};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(uint32_t(c.cu_waves) * 64u), kargs, c.lds_bytes, st));
-  } else if (c.sched == VIMG_SCHED_LANE) {
+  } else {
     if (ev0) HIP_TRY(hipEventRecord(ev0, st));
     void* kargs[] = {&s->d, &c.args, &d_out, &stats, &s->d_counter};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(256), kargs, c.lds_bytes, st));
-  } else if (int rc = dev_enqueue(s, c, d_out, stats, st, ev0)) {
-    return rc;
   }
   if (ev1) HIP_TRY(hipEventRecord(ev1, st));
   HIP_TRY(hipGetLastError());
   return VIMG_OK;
 }
 
-// d_counter[1] is the error word of the last launch (raised by the pooled kernel's watchdog); the
-// staged kernel of the development build has its own
+// d_counter[1] is the error word of the last launch (raised by render_cu_kernel's watchdog)
 int check_kernel_error(VimgDeviceScene* s) {
   unsigned int words[2] = {0, 0};
   HIP_TRY(hipMemcpy(words, s->d_counter, sizeof(words), hipMemcpyDeviceToHost));
-  unsigned int stage_err = 0;
-  if (int rc = dev_error_word(s, &stage_err)) return rc;
   if (words[1] != 0) HIP_TRY(hipMemset(s->d_counter + 1, 0, sizeof(unsigned int)));   // read once
-  if (words[1] != 0 || stage_err != 0) {
+  if (words[1] != 0) {
     // bits of the launch's error word (render_cu_kernel.h: raise): 1 a wave found nothing to do for ten seconds
-    // while slots were live, 2 a group lock timed out (development build), 4 a ring entry was reserved and never
-    // written, 8 a compute unit queued more than 2^31 rays or slots in one launch
+    // while slots were live, 4 a ring entry was reserved and never written, 8 a compute unit queued more than 2^31 rays or slots in one launch
     const std::string what = (words[1] & 8u) ? "a compute unit queued more than 2^31 rays in one launch: render fewer samples per launch "
                                                "(vimg_hip_progressive_render adds a frame's samples in increments)"
                                              : "a wave waited for work that never came";
     return fail(VIMG_E_DEVICE, "render kernel watchdog: " + what + " (the frame is incomplete), code " +
-                                   std::to_string(words[1] | (stage_err << 8)));
+                                   std::to_string(words[1]));
   }
   return VIMG_OK;
 }
@@ -179,9 +169,8 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
     std::fprintf(stderr, "[vimg diag] wave trips: descend %llu (lane visits %llu, util %.3f)  prim %llu (lane tests %llu, util %.3f)  main-loop iterations %llu\n",
                  ds.trip_descend, ds.internal, ds.trip_descend ? double(ds.internal) / (64.0 * ds.trip_descend) : 0.0,
                  ds.trip_prim, ds.prim, ds.trip_prim ? double(ds.prim) / (64.0 * ds.trip_prim) : 0.0, ds.iterations);
-#ifndef VIMG_PROFILE
-  if (getenv("VIMG_HIP_DIAG") && ds.prof[6 + 4]) {   // staged kernel: cycles and batch fill per stage
-    static const char* st_names[6] = {"finisher", "lambertian", "principled", "other", "walk", "looking for work"};   // (pool4: walk includes waiting)
+  if (getenv("VIMG_HIP_DIAG") && ds.prof[6 + 4]) {   // statistics build of render_cu_kernel: cycles and batch fill per stage
+    static const char* st_names[6] = {"finisher", "lambertian", "principled", "other", "walk", "looking for work"};
     unsigned long long total = 0;
     for (int k = 0; k < 6; ++k) total += ds.prof[k];
     for (int k = 0; k < 6; ++k)
@@ -223,21 +212,6 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
     for (int k = 0; k < 12; ++k) std::fprintf(stderr, "[vimg walk] %-24s %14llu\n", wd_names[k], ds.prof[16 + k]);
 #endif
   }
-#endif
-#ifdef VIMG_PROFILE
-  if (getenv("VIMG_HIP_DIAG") && ds.prof[PF_TOTAL]) {
-    static const char* names[PF_COUNT] = {"total", "v_load+logic+hit_info", "v_light_sample", "v_bsdf_sample",
-                                          "v_bsdf_eval_x2", "v_finish+regen", "v_store", "w_refill+setup",
-                                          "w_box_loop", "w_leaf_loop", "w_retire", "v_batches", "v_lanes",
-                                          "v_at_vertex", "w_rounds", "cyc_finisher", "cyc_lambertian",
-                                          "cyc_principled", "cyc_other", "lanes_finisher", "lanes_lambertian",
-                                          "lanes_principled", "lanes_other", "drain (after last fetch)",
-                                          "longest wave"};
-    for (int k = 0; k < PF_COUNT; ++k)
-      std::fprintf(stderr, "[vimg prof] %-24s %14llu  %6.2f %%\n", names[k], ds.prof[k],
-                   100.0 * double(ds.prof[k]) / double(ds.prof[PF_TOTAL]));
-  }
-#endif
   return VIMG_OK;
 }
 
@@ -312,9 +286,6 @@ int vimg_hip_progressive_create(VimgDeviceScene* s, const VimgRenderParams* p, V
   VimgRenderParams q = *p;
   q.samples = 1;   // (ignored: every increment says how many)
   if (int rc = check_params(s, &q)) return rc;
-  if (s->opt.scheduler != VIMG_OPT_AUTO && s->opt.scheduler != VIMG_SCHED_LANE && s->opt.scheduler != VIMG_SCHED_CU)
-    return fail(VIMG_E_UNSUPPORTED, "progressive rendering: the schedulers POOL, POOL4, POOL4G and STAGE of the "
-                                    "development build do not resume pixels across launches");
   VimgProgressive* a = new VimgProgressive{};
   a->scene = s;
   a->generation = s->generation;

@@ -68,7 +68,7 @@ def init(device=0):
 
 class DeviceScene:
     """A scene resident in HBM (vimg_hip_scene_upload_opts).  `options`: abi.HipOptions, or keyword
-    arguments for one (scheduler="lane" | "pool" | "stage", pool_segments=..., ...); nothing given
+    arguments for one (scheduler="lane" | "cu", pool_segments=..., ...); nothing given
     = the library's policy."""
 
     def __init__(self, host_scene: HostScene, options=None, **opt_kw):
