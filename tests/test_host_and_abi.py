@@ -74,6 +74,62 @@ def test_hip_path_fails_loudly_without_a_gpu():
         hip.device_count()
 
 
+def test_a_failing_builder_leaves_its_own_message():
+    """include/vimg_hip.h: vimg_hip_last_error is the message of the calling thread's last failure.  The exported
+    builders answer VIMG_E_INVALID for n = 0 and, in a container without a GPU, VIMG_E_DEVICE for good arguments;
+    each time the message names the builder, and is not the text of the failure provoked right before the call."""
+    import torch
+    lib = abi.hip_lib()
+    n = 4
+    bounds = np.zeros((n, 6), np.float32)
+    bounds[:, 3:] = 1.0
+    num_nodes, max_depth = C.c_uint32(), C.c_uint32()
+    nodes = np.zeros((2 * n, 2), np.uint32)
+    bb = np.zeros((4 * n + 2, 3), np.float32)
+    obj = np.zeros(n, np.uint32)
+    pf = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+
+    def call(fn, count):
+        assert lib.vimg_hip_check(None) == -1                 # VIMG_E_INVALID, with a message of its own
+        stale = lib.vimg_hip_last_error().decode()
+        assert stale == "null scene"
+        rc = fn(count, pf(bounds), C.byref(num_nodes), C.byref(max_depth), nodes.ctypes.data_as(C.c_void_p), pf(bb),
+                obj.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return rc, lib.vimg_hip_last_error().decode(), stale
+
+    for fn, name in ((lib.vimg_hip_build_lbvh, "build_lbvh"), (lib.vimg_hip_build_ploc, "build_ploc")):
+        rc, msg, stale = call(fn, 0)
+        assert rc == -1, rc                                    # VIMG_E_INVALID
+        assert msg and msg != stale and name in msg, msg
+        if not torch.cuda.is_available():                      # (where test_hip_path_fails_loudly_without_a_gpu runs)
+            rc, msg, stale = call(fn, n)
+            assert rc == -2, rc                                # VIMG_E_DEVICE
+            assert msg and msg != stale and name in msg, msg
+
+
+def test_device_memory_and_events_have_one_owner_type():
+    """Every hipFree and hipEventDestroy of the library sits in the destructors (and alloc) of the owner types of
+    ONE header; no .hip unit frees by hand, so no return path can forget to.  The hand-written owners and the
+    silent error macro that the owner types replaced stay gone."""
+    csrc = os.path.join(ROOT, "v-img_amd", "csrc")
+    holders = {"hipFree(": [], "hipEventDestroy(": []}
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        for gone in ("LB_TRY", "replace_alloc"):
+            assert gone not in text, (name, gone)
+        assert not re.search(r"struct\s+(Buf|PreBuf|Dev)\b", text), name      # (whole names: DevBuf, DeviceTree stay)
+        for call, where in holders.items():
+            if call in text:
+                assert name.endswith(".h"), (name, call)
+                where.append(name)
+    assert holders["hipFree("] == holders["hipEventDestroy("] and len(holders["hipFree("]) == 1, holders
+    header = open(os.path.join(csrc, holders["hipFree("][0])).read()
+    for call, owner in (("hipFree(", "DevBuf"), ("hipEventDestroy(", "DevEvent")):
+        body = header[header.index("struct " + owner + " {"):]
+        body = body[:body.index("\n};") + 3]
+        assert header.count(call) == body.count(call) >= 1, (call, owner)
+
+
 def test_product_package_never_touches_the_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "v-img_amd")):
         for f in files:

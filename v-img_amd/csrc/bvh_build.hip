@@ -41,11 +41,8 @@
 
 namespace {
 
-#define LB_TRY(expr)                                 \
-  do {                                               \
-    hipError_t e_ = (expr);                          \
-    if (e_ != hipSuccess) return VIMG_E_DEVICE;      \
-  } while (0)
+using vimg::DevBuf;
+using vimg::fail;
 
 __device__ __forceinline__ uint32_t ordered(float f) {   // order-preserving float -> uint
   const uint32_t u = __float_as_uint(f);
@@ -161,12 +158,6 @@ __global__ void lb_boxes(const unsigned long long* __restrict__ keys, const floa
   }
 }
 
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-};
-
 // ---- a binary tree over the sorted leaves -> the reference layout (include/bvh.h:22-57): breadth-first
 // numbering with the two children of a node adjacent, the sibling-pair box table, obj_indices with
 // every leaf's primitives contiguous, max_depth.  One level of the tree per step: the level's entries in
@@ -243,47 +234,48 @@ int emit_reference_layout(const EmitTree& t, uint32_t root_id, vimg::DeviceTree*
   const uint32_t n = t.n, threads = 256;
   const size_t max_nodes = size_t(2) * n - 1, bb_rows = 2 * max_nodes + 3;
   out->level_internal.clear();
-  Buf d_level[2], d_packed, d_scanned, d_totals, d_nodes, d_bb, d_obj, d_scan;
-  for (auto& b : d_level) LB_TRY(hipMalloc(&b.p, size_t(n) * sizeof(uint2)));
-  LB_TRY(hipMalloc(&d_packed.p, size_t(n) * 8));
-  LB_TRY(hipMalloc(&d_scanned.p, size_t(n) * 8));
-  LB_TRY(hipMalloc(&d_totals.p, 8));
-  LB_TRY(hipMalloc(&d_nodes.p, max_nodes * sizeof(VimgBVHNode)));
-  LB_TRY(hipMalloc(&d_bb.p, bb_rows * 3 * sizeof(float)));
-  LB_TRY(hipMalloc(&d_obj.p, size_t(n) * 4));
+  DevBuf d_level[2], d_packed, d_scanned, d_totals, d_nodes, d_bb, d_obj, d_scan;   // (d_nodes, d_bb, d_obj: handed to `out` at the end)
+  for (auto& b : d_level)
+    if (int rc = b.alloc(size_t(n) * sizeof(uint2))) return rc;
+  if (int rc = d_packed.alloc(size_t(n) * 8)) return rc;
+  if (int rc = d_scanned.alloc(size_t(n) * 8)) return rc;
+  if (int rc = d_totals.alloc(8)) return rc;
+  if (int rc = d_nodes.alloc(max_nodes * sizeof(VimgBVHNode))) return rc;
+  if (int rc = d_bb.alloc(bb_rows * 3 * sizeof(float))) return rc;
+  if (int rc = d_obj.alloc(size_t(n) * 4)) return rc;
   size_t scan_bytes = 0;
-  LB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, d_packed.as<unsigned long long>(), d_scanned.as<unsigned long long>(), 0ull, n,
-                                 rocprim::plus<unsigned long long>()));
-  LB_TRY(hipMalloc(&d_scan.p, std::max<size_t>(scan_bytes, 16)));
+  HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, d_packed.as<unsigned long long>(), d_scanned.as<unsigned long long>(), 0ull, n,
+                                  rocprim::plus<unsigned long long>()));
+  if (int rc = d_scan.alloc(std::max<size_t>(scan_bytes, 16))) return rc;
   const uint2 first{root_id, 0u};
-  LB_TRY(hipMemcpy(d_level[0].p, &first, sizeof(first), hipMemcpyHostToDevice));
-  LB_TRY(hipMemsetAsync(d_bb.p, 0, 4 * 3 * sizeof(float), 0));   // (rows 1 and 3 belong to no node)
+  HIP_TRY(hipMemcpy(d_level[0].p, &first, sizeof(first), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(d_bb.p, 0, 4 * 3 * sizeof(float), 0));   // (rows 1 and 3 belong to no node)
   uint32_t size = 1, child_base = 1, prim_base = 0, depth = 0;
   int cur = 0;
   while (size != 0u) {
-    if (++depth > 4096u) return VIMG_E_DEVICE;
+    if (++depth > 4096u) return fail(VIMG_E_DEVICE, "bvh layout: more than 4096 levels");
     const uint32_t blocks = (size + threads - 1) / threads;
     hipLaunchKernelGGL(emit_classify, dim3(blocks), dim3(threads), 0, 0, t, d_level[cur].as<uint2>(), size, d_packed.as<unsigned long long>());
-    LB_TRY(rocprim::exclusive_scan(d_scan.p, scan_bytes, d_packed.as<unsigned long long>(), d_scanned.as<unsigned long long>(), 0ull, size,
-                                   rocprim::plus<unsigned long long>()));
+    HIP_TRY(rocprim::exclusive_scan(d_scan.p, scan_bytes, d_packed.as<unsigned long long>(), d_scanned.as<unsigned long long>(), 0ull, size,
+                                    rocprim::plus<unsigned long long>()));
     hipLaunchKernelGGL(emit_write, dim3(blocks), dim3(threads), 0, 0, t, d_level[cur].as<uint2>(), size, d_packed.as<unsigned long long>(),
                        d_scanned.as<unsigned long long>(), child_base, prim_base, d_level[cur ^ 1].as<uint2>(), d_nodes.as<VimgBVHNode>(),
                        d_bb.as<float>(), d_obj.as<uint32_t>(), d_totals.as<unsigned long long>());
     unsigned long long totals = 0;
-    LB_TRY(hipMemcpy(&totals, d_totals.p, 8, hipMemcpyDeviceToHost));   // (also the level's synchronisation)
+    HIP_TRY(hipMemcpy(&totals, d_totals.p, 8, hipMemcpyDeviceToHost));   // (also the level's synchronisation)
     const uint32_t with_children = static_cast<uint32_t>(totals >> 32);
     child_base += 2u * with_children, prim_base += static_cast<uint32_t>(totals & 0xffffffffull);
-    if (child_base > max_nodes || prim_base > n) return VIMG_E_DEVICE;
+    if (child_base > max_nodes || prim_base > n)
+      return fail(VIMG_E_DEVICE, "bvh layout: a level's totals exceed the tree's nodes or primitives");
     size = 2u * with_children;
     if (with_children) out->level_internal.push_back(with_children);
     cur ^= 1;
   }
-  LB_TRY(hipGetLastError());
-  if (prim_base != n) return VIMG_E_DEVICE;   // every primitive sits in exactly one leaf
+  HIP_TRY(hipGetLastError());
+  if (prim_base != n) return fail(VIMG_E_DEVICE, "bvh layout: the leaves do not hold every primitive exactly once");
   out->num_nodes = child_base;
   out->max_depth = depth;
-  out->nodes = d_nodes.as<VimgBVHNode>(), out->bb = d_bb.as<float>(), out->obj_indices = d_obj.as<uint32_t>();
-  d_nodes.p = d_bb.p = d_obj.p = nullptr;   // (out owns them now)
+  out->nodes = std::move(d_nodes), out->bb = std::move(d_bb), out->obj_indices = std::move(d_obj);
   return VIMG_OK;
 }
 
@@ -292,20 +284,34 @@ int download_tree(const vimg::DeviceTree& t, uint32_t n, uint32_t* num_nodes, ui
                   uint32_t* obj_indices) {
   *num_nodes = t.num_nodes;
   *max_depth = t.max_depth;
-  LB_TRY(hipMemcpy(nodes, t.nodes, size_t(t.num_nodes) * sizeof(VimgBVHNode), hipMemcpyDeviceToHost));
-  LB_TRY(hipMemcpy(bb, t.bb, (size_t(2) * t.num_nodes + 2) * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  LB_TRY(hipMemcpy(obj_indices, t.obj_indices, size_t(n) * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nodes, t.nodes.p, size_t(t.num_nodes) * sizeof(VimgBVHNode), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(bb, t.bb.p, (size_t(2) * t.num_nodes + 2) * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(obj_indices, t.obj_indices.p, size_t(n) * 4, hipMemcpyDeviceToHost));
   return VIMG_OK;
 }
 
-struct HostBounds {   // the primitive bounds of an exported builder's caller, copied up
-  Buf d;
-  int upload(uint32_t n, const float* bounds6) {
-    LB_TRY(hipMalloc(&d.p, size_t(n) * 6 * sizeof(float)));
-    LB_TRY(hipMemcpy(d.p, bounds6, size_t(n) * 6 * sizeof(float), hipMemcpyHostToDevice));
-    return VIMG_OK;
-  }
+// What both builders start with: the bounds of the primitive centres, a Morton key per primitive, the keys
+// sorted (`sorted`: what the trees are built over).  On the null stream; `started`, when given, is recorded in
+// front of the first kernel.  The four buffers live as long as the build: nothing is freed between its launches.
+struct SortedKeys {
+  DevBuf mm, keys, sorted, tmp;
 };
+int sort_morton_keys(uint32_t n, const float* bounds, hipEvent_t started, SortedKeys* k) {
+  const uint32_t threads = 256, blocks = (n + threads - 1) / threads;
+  if (int rc = k->mm.alloc(6 * sizeof(uint32_t))) return rc;
+  if (int rc = k->keys.alloc(size_t(n) * 8)) return rc;
+  if (int rc = k->sorted.alloc(size_t(n) * 8)) return rc;
+  const uint32_t mm_init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+  HIP_TRY(hipMemcpy(k->mm.p, mm_init, sizeof(mm_init), hipMemcpyHostToDevice));
+  if (started) HIP_TRY(hipEventRecord(started, 0));
+  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, bounds, n, k->mm.as<uint32_t>());
+  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, bounds, n, k->mm.as<uint32_t>(), k->keys.as<unsigned long long>());
+  size_t tmp_bytes = 0;
+  HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, k->keys.as<unsigned long long>(), k->sorted.as<unsigned long long>(), n, 0, 62));
+  if (int rc = k->tmp.alloc(std::max<size_t>(tmp_bytes, 16))) return rc;
+  HIP_TRY(rocprim::radix_sort_keys(k->tmp.p, tmp_bytes, k->keys.as<unsigned long long>(), k->sorted.as<unsigned long long>(), n, 0, 62));
+  return VIMG_OK;
+}
 
 // ---- PLOC (parallel locally-ordered clustering, Meister & Bittner 2018): bottom-up agglomeration
 // over the Morton-sorted clusters.  Per round: every cluster looks at its 2 * R neighbours in the
@@ -605,30 +611,17 @@ top_level(const TopItem* __restrict__ in, TopItem* __restrict__ out, const TopJo
 // the LBVH over `n` primitive bounds on the device
 int lbvh_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
   const uint32_t threads = 256, blocks = (n + threads - 1) / threads;
-  Buf d_mm, d_keys, d_keys2, d_left, d_right, d_pi, d_pl, d_box, d_visits, d_tmp;
-  LB_TRY(hipMalloc(&d_mm.p, 6 * sizeof(uint32_t)));
-  LB_TRY(hipMalloc(&d_keys.p, size_t(n) * 8));
-  LB_TRY(hipMalloc(&d_keys2.p, size_t(n) * 8));
-  LB_TRY(hipMalloc(&d_left.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_right.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_pi.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_pl.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_box.p, size_t(2) * n * 6 * sizeof(float)));   // the leaves' boxes, then the nodes'
-  LB_TRY(hipMalloc(&d_visits.p, size_t(n) * 4));
-  const uint32_t mm_init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-  LB_TRY(hipMemcpy(d_mm.p, mm_init, sizeof(mm_init), hipMemcpyHostToDevice));
-  LB_TRY(hipMemset(d_visits.p, 0, size_t(n) * 4));
-
-  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, bounds, n,
-                     d_mm.as<uint32_t>());
-  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, bounds, n,
-                     d_mm.as<uint32_t>(), d_keys.as<unsigned long long>());
-  size_t tmp_bytes = 0;
-  LB_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys.as<unsigned long long>(),
-                                  d_keys2.as<unsigned long long>(), n, 0, 62));
-  LB_TRY(hipMalloc(&d_tmp.p, std::max<size_t>(tmp_bytes, 16)));
-  LB_TRY(rocprim::radix_sort_keys(d_tmp.p, tmp_bytes, d_keys.as<unsigned long long>(),
-                                  d_keys2.as<unsigned long long>(), n, 0, 62));
+  SortedKeys keys;
+  DevBuf& d_keys2 = keys.sorted;
+  DevBuf d_left, d_right, d_pi, d_pl, d_box, d_visits;
+  if (int rc = d_left.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_right.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_pi.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_pl.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_box.alloc(size_t(2) * n * 6 * sizeof(float))) return rc;   // the leaves' boxes, then the nodes'
+  if (int rc = d_visits.alloc(size_t(n) * 4)) return rc;
+  HIP_TRY(hipMemset(d_visits.p, 0, size_t(n) * 4));
+  if (int rc = sort_morton_keys(n, bounds, nullptr, &keys)) return rc;
   if (n > 1)
     hipLaunchKernelGGL(lb_radix_tree, dim3(blocks), dim3(threads), 0, 0, d_keys2.as<unsigned long long>(), int(n),
                        d_left.as<uint32_t>(), d_right.as<uint32_t>(), d_pi.as<uint32_t>(), d_pl.as<uint32_t>());
@@ -636,7 +629,7 @@ int lbvh_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
                      bounds, int(n), d_left.as<uint32_t>(), d_right.as<uint32_t>(),
                      d_pi.as<uint32_t>(), d_pl.as<uint32_t>(), d_box.as<float>(), d_box.as<float>() + size_t(n) * 6,
                      d_visits.as<uint32_t>());
-  LB_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   // (one primitive per leaf: no subtree ends as a leaf; the root is internal node 0, or the only leaf)
   const EmitTree tree{d_left.as<uint32_t>(), d_right.as<uint32_t>(), d_box.as<float>(), nullptr, nullptr, d_keys2.as<unsigned long long>(), n, 1u};
   return emit_reference_layout(tree, n == 1 ? 0u : n, out);
@@ -651,46 +644,35 @@ int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
   // ids: [0, n) the sorted leaves, [n, 2n - 1) the nodes of the agglomeration, from 2n - 1 the nodes of the new top
   // (at most one per subtree of the cut, and the cut has at most n subtrees)
   const size_t ids = size_t(3) * n;
-  Buf d_mm, d_keys, d_keys2, d_tmp, d_box, d_cl[2], d_nn, d_merged, d_keep, d_pos, d_left, d_right, d_counter, d_scan;
-  Buf d_nprims, d_cost, d_as_leaf, d_parent, d_firstpos, d_key, d_sorted, d_sort_tmp, d_at, d_items[2], d_jobs[2], d_counts;
-  LB_TRY(hipMalloc(&d_mm.p, 6 * sizeof(uint32_t)));
-  LB_TRY(hipMalloc(&d_keys.p, size_t(n) * 8));
-  LB_TRY(hipMalloc(&d_keys2.p, size_t(n) * 8));
-  LB_TRY(hipMalloc(&d_box.p, ids * 6 * sizeof(float)));
-  for (auto& b : d_cl) LB_TRY(hipMalloc(&b.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_nn.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_merged.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_keep.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_pos.p, size_t(n) * 4));
-  LB_TRY(hipMalloc(&d_left.p, size_t(2) * n * 4));
-  LB_TRY(hipMalloc(&d_right.p, size_t(2) * n * 4));
-  LB_TRY(hipMalloc(&d_counter.p, 4));
-  LB_TRY(hipMalloc(&d_nprims.p, ids * 4));
-  LB_TRY(hipMalloc(&d_as_leaf.p, ids * 4));
-  LB_TRY(hipMalloc(&d_cost.p, size_t(2) * n * 4));
-  LB_TRY(hipMalloc(&d_parent.p, size_t(2) * n * 4));
-  LB_TRY(hipMalloc(&d_firstpos.p, size_t(2) * n * 4));
+  SortedKeys keys;
+  DevBuf& d_keys2 = keys.sorted;
+  DevBuf d_box, d_cl[2], d_nn, d_merged, d_keep, d_pos, d_left, d_right, d_counter, d_scan;
+  DevBuf d_nprims, d_cost, d_as_leaf, d_parent, d_firstpos, d_key, d_sorted, d_sort_tmp, d_at, d_items[2], d_jobs[2], d_counts;
+  if (int rc = d_box.alloc(ids * 6 * sizeof(float))) return rc;
+  for (auto& b : d_cl)
+    if (int rc = b.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_nn.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_merged.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_keep.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_pos.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_left.alloc(size_t(2) * n * 4)) return rc;
+  if (int rc = d_right.alloc(size_t(2) * n * 4)) return rc;
+  if (int rc = d_counter.alloc(4)) return rc;
+  if (int rc = d_nprims.alloc(ids * 4)) return rc;
+  if (int rc = d_as_leaf.alloc(ids * 4)) return rc;
+  if (int rc = d_cost.alloc(size_t(2) * n * 4)) return rc;
+  if (int rc = d_parent.alloc(size_t(2) * n * 4)) return rc;
+  if (int rc = d_firstpos.alloc(size_t(2) * n * 4)) return rc;
   const PlocRec rec{d_nprims.as<uint32_t>(), d_cost.as<float>(), d_as_leaf.as<uint32_t>(), d_parent.as<uint32_t>(), d_firstpos.as<uint32_t>()};
-  struct Ev {   // (destroyed on every way out)
-    hipEvent_t e = nullptr;
-    ~Ev() { if (e) (void)hipEventDestroy(e); }
-  } e0, e1;
-  LB_TRY(hipEventCreate(&e0.e));
-  LB_TRY(hipEventCreate(&e1.e));
+  size_t scan_bytes = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>()));
+  if (int rc = d_scan.alloc(std::max<size_t>(scan_bytes, 16))) return rc;
+  vimg::DevEvent e0, e1;   // around the kernels, for the diagnostic line
+  if (int rc = e0.create()) return rc;
+  if (int rc = e1.create()) return rc;
   const hipEvent_t ev0 = e0.e, ev1 = e1.e;
-  const uint32_t mm_init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-  LB_TRY(hipMemcpy(d_mm.p, mm_init, sizeof(mm_init), hipMemcpyHostToDevice));
-  LB_TRY(hipMemset(d_counter.p, 0, 4));
-  LB_TRY(hipEventRecord(ev0, 0));
-  hipLaunchKernelGGL(lb_centre_bounds, dim3(blocks), dim3(threads), 0, 0, bounds, n, d_mm.as<uint32_t>());
-  hipLaunchKernelGGL(lb_morton, dim3(blocks), dim3(threads), 0, 0, bounds, n, d_mm.as<uint32_t>(),
-                     d_keys.as<unsigned long long>());
-  size_t tmp_bytes = 0, scan_bytes = 0;
-  LB_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(), n, 0, 62));
-  LB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>()));
-  LB_TRY(hipMalloc(&d_tmp.p, std::max<size_t>(tmp_bytes, 16)));
-  LB_TRY(hipMalloc(&d_scan.p, std::max<size_t>(scan_bytes, 16)));
-  LB_TRY(rocprim::radix_sort_keys(d_tmp.p, tmp_bytes, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(), n, 0, 62));
+  HIP_TRY(hipMemset(d_counter.p, 0, 4));
+  if (int rc = sort_morton_keys(n, bounds, ev0, &keys)) return rc;
   hipLaunchKernelGGL(ploc_leaf_boxes, dim3(blocks), dim3(threads), 0, 0, d_keys2.as<unsigned long long>(),
                      bounds, n, d_box.as<float>(), d_cl[0].as<uint32_t>(), rec);
   uint32_t c = n, radius = PLOC_R;
@@ -703,19 +685,20 @@ int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
     hipLaunchKernelGGL(ploc_merge, dim3(cb), dim3(threads), 0, 0, d_cl[cur].as<uint32_t>(), d_nn.as<uint32_t>(), c, n,
                        d_box.as<float>(), d_left.as<uint32_t>(), d_right.as<uint32_t>(), d_counter.as<uint32_t>(),
                        d_merged.as<uint32_t>(), d_keep.as<uint32_t>(), rec);
-    LB_TRY(rocprim::exclusive_scan(d_scan.p, scan_bytes, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, c, rocprim::plus<uint32_t>()));
+    HIP_TRY(rocprim::exclusive_scan(d_scan.p, scan_bytes, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, c, rocprim::plus<uint32_t>()));
     hipLaunchKernelGGL(ploc_compact, dim3(cb), dim3(threads), 0, 0, d_merged.as<uint32_t>(), d_keep.as<uint32_t>(),
                        d_pos.as<uint32_t>(), c, d_cl[cur ^ 1].as<uint32_t>());
     uint32_t created = 0;
-    LB_TRY(hipMemcpy(&created, d_counter.p, 4, hipMemcpyDeviceToHost));   // (also the round's synchronisation)
+    HIP_TRY(hipMemcpy(&created, d_counter.p, 4, hipMemcpyDeviceToHost));   // (also the round's synchronisation)
     const uint32_t c_new = n - created;
-    if (c_new >= c || ++rounds > 4096) return VIMG_E_DEVICE;   // a round always merges the closest pair at least
+    if (c_new >= c || ++rounds > 4096)   // a round always merges the closest pair at least
+      return fail(VIMG_E_DEVICE, "build_ploc: a clustering round merged nothing");
     c = c_new;
     cur ^= 1;
   }
-  LB_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   uint32_t root_id = 0;
-  LB_TRY(hipMemcpy(&root_id, d_cl[cur].p, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&root_id, d_cl[cur].p, 4, hipMemcpyDeviceToHost));
 
   // ---- the top, rebuilt over the cut (nothing to do for trees of a few leaves)
   uint32_t top_items_n = 0, top_levels = 0;
@@ -724,37 +707,39 @@ int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
     if (const char* e = getenv("VIMG_PLOC_TOP")) cut = uint32_t(std::max(4, atoi(e)));
     const uint32_t internal = n - 1u, opened = std::min(cut - 1u, internal);
     const uint32_t nb = (internal + threads - 1) / threads, idb = (2u * n + threads - 1) / threads;
-    LB_TRY(hipMalloc(&d_key.p, size_t(n) * 4));
-    LB_TRY(hipMalloc(&d_sorted.p, size_t(n) * 4));
-    LB_TRY(hipMalloc(&d_at.p, size_t(n) * 4));
+    if (int rc = d_key.alloc(size_t(n) * 4)) return rc;
+    if (int rc = d_sorted.alloc(size_t(n) * 4)) return rc;
+    if (int rc = d_at.alloc(size_t(n) * 4)) return rc;
     size_t sort_bytes = 0;
-    LB_TRY(rocprim::radix_sort_keys_desc(nullptr, sort_bytes, d_key.as<uint32_t>(), d_sorted.as<uint32_t>(), internal));
-    LB_TRY(hipMalloc(&d_sort_tmp.p, std::max<size_t>(sort_bytes, 16)));
+    HIP_TRY(rocprim::radix_sort_keys_desc(nullptr, sort_bytes, d_key.as<uint32_t>(), d_sorted.as<uint32_t>(), internal));
+    if (int rc = d_sort_tmp.alloc(std::max<size_t>(sort_bytes, 16))) return rc;
     hipLaunchKernelGGL(top_keys, dim3(nb), dim3(threads), 0, 0, d_box.as<float>(), d_nprims.as<uint32_t>(), n, d_key.as<uint32_t>());
-    LB_TRY(rocprim::radix_sort_keys_desc(d_sort_tmp.p, sort_bytes, d_key.as<uint32_t>(), d_sorted.as<uint32_t>(), internal));
-    LB_TRY(hipMemsetAsync(d_keep.p, 0, size_t(n) * 4, 0));   // (the flags of the cut, by first sorted position)
+    HIP_TRY(rocprim::radix_sort_keys_desc(d_sort_tmp.p, sort_bytes, d_key.as<uint32_t>(), d_sorted.as<uint32_t>(), internal));
+    HIP_TRY(hipMemsetAsync(d_keep.p, 0, size_t(n) * 4, 0));   // (the flags of the cut, by first sorted position)
     hipLaunchKernelGGL(top_mark, dim3(idb), dim3(threads), 0, 0, d_key.as<uint32_t>(), d_sorted.as<uint32_t>(), opened, n,
                        d_parent.as<uint32_t>(), d_firstpos.as<uint32_t>(), d_keep.as<uint32_t>(), d_at.as<uint32_t>());
-    LB_TRY(rocprim::exclusive_scan(d_scan.p, scan_bytes, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>()));
+    HIP_TRY(rocprim::exclusive_scan(d_scan.p, scan_bytes, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>()));
     uint32_t last_pos = 0, last_flag = 0;
-    LB_TRY(hipMemcpy(&last_pos, d_pos.as<uint32_t>() + (n - 1u), 4, hipMemcpyDeviceToHost));
-    LB_TRY(hipMemcpy(&last_flag, d_keep.as<uint32_t>() + (n - 1u), 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&last_pos, d_pos.as<uint32_t>() + (n - 1u), 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&last_flag, d_keep.as<uint32_t>() + (n - 1u), 4, hipMemcpyDeviceToHost));
     top_items_n = last_pos + last_flag;
     if (top_items_n >= 3u) {
-      for (auto& b : d_items) LB_TRY(hipMalloc(&b.p, size_t(top_items_n) * sizeof(TopItem)));
-      for (auto& b : d_jobs) LB_TRY(hipMalloc(&b.p, (size_t(top_items_n) / 2u + 1u) * sizeof(TopJob)));
+      for (auto& b : d_items)
+        if (int rc = b.alloc(size_t(top_items_n) * sizeof(TopItem))) return rc;
+      for (auto& b : d_jobs)
+        if (int rc = b.alloc((size_t(top_items_n) / 2u + 1u) * sizeof(TopJob))) return rc;
       uint32_t lg = 0;
       while ((1u << lg) < top_items_n) ++lg;
       top_levels = TOP_SAH_LEVELS + lg + 1u;
-      LB_TRY(hipMalloc(&d_counts.p, size_t(top_levels + 1u) * 4));
-      LB_TRY(hipMemsetAsync(d_counts.p, 0, size_t(top_levels + 1u) * 4, 0));
+      if (int rc = d_counts.alloc(size_t(top_levels + 1u) * 4)) return rc;
+      HIP_TRY(hipMemsetAsync(d_counts.p, 0, size_t(top_levels + 1u) * 4, 0));
       hipLaunchKernelGGL(top_items, dim3(blocks), dim3(threads), 0, 0, d_keep.as<uint32_t>(), d_pos.as<uint32_t>(), d_at.as<uint32_t>(), n,
                          d_box.as<float>(), d_nprims.as<uint32_t>(), d_items[0].as<TopItem>());
       const uint32_t new_root = n + (n - 1u), one = 1u, next = n;   // (the agglomeration made n - 1 nodes)
       const TopJob first{0u, top_items_n, new_root, 0u};
-      LB_TRY(hipMemcpy(d_jobs[0].p, &first, sizeof(first), hipMemcpyHostToDevice));
-      LB_TRY(hipMemcpy(d_counts.p, &one, 4, hipMemcpyHostToDevice));
-      LB_TRY(hipMemcpy(d_counter.p, &next, 4, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_jobs[0].p, &first, sizeof(first), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_counts.p, &one, 4, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_counter.p, &next, 4, hipMemcpyHostToDevice));
       for (uint32_t level = 0; level < top_levels; ++level) {
         // (at most 2^level nodes on a level, and every node of a level holds two items at least)
         const uint64_t most = std::min<uint64_t>(level < 31u ? (1ull << level) : ~0ull, top_items_n / 2u);
@@ -766,15 +751,16 @@ int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
       root_id = new_root;
     }
   }
-  LB_TRY(hipEventRecord(ev1, 0));
-  LB_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev1, 0));
+  HIP_TRY(hipGetLastError());
   if (top_levels) {
     uint32_t left_over = 0, made = 0;
-    LB_TRY(hipMemcpy(&made, d_counter.p, 4, hipMemcpyDeviceToHost));   // nodes in all (the copy waits for the kernels)
-    LB_TRY(hipMemcpy(&left_over, d_counts.as<uint32_t>() + top_levels, 4, hipMemcpyDeviceToHost));
-    if (left_over != 0u || made > 2u * n) return VIMG_E_DEVICE;   // (the median levels end every range: not reachable)
+    HIP_TRY(hipMemcpy(&made, d_counter.p, 4, hipMemcpyDeviceToHost));   // nodes in all (the copy waits for the kernels)
+    HIP_TRY(hipMemcpy(&left_over, d_counts.as<uint32_t>() + top_levels, 4, hipMemcpyDeviceToHost));
+    if (left_over != 0u || made > 2u * n)   // (the median levels end every range: not reachable)
+      return fail(VIMG_E_DEVICE, "build_ploc: the top's levels left ranges unsplit, or made more nodes than the cut allows");
   }
-  LB_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
   float gpu_ms = 0.f;
   (void)hipEventElapsedTime(&gpu_ms, ev0, ev1);
   const auto t_gpu = std::chrono::steady_clock::now();
@@ -794,15 +780,18 @@ int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
 
 int build_exported(uint32_t builder, uint32_t n, const float* bounds6, uint32_t* num_nodes, uint32_t* max_depth, VimgBVHNode* nodes,
                    float* bb, uint32_t* obj_indices) {
+  const std::string name = builder == VIMG_BUILDER_PLOC ? "build_ploc" : "build_lbvh";
   if (!bounds6 || !num_nodes || !max_depth || !nodes || !bb || !obj_indices || n == 0 || n > (1u << 25))
-    return VIMG_E_INVALID;
-  if (vimg_hip_device_count() <= 0) return VIMG_E_DEVICE;
+    return fail(VIMG_E_INVALID, name + ": a null argument, or a primitive count outside [1, 2^25]");
+  const int devices = vimg_hip_device_count();   // (an error of the count is VIMG_E_DEVICE with HIP's words)
+  if (devices <= 0) return fail(VIMG_E_DEVICE, name + ": no device" + (devices < 0 ? std::string(" (") + vimg_hip_last_error() + ")" : ""));
   const auto t_begin = std::chrono::steady_clock::now();
-  HostBounds up;
-  if (int rc = up.upload(n, bounds6)) return rc;
+  DevBuf d_bounds;   // the caller's primitive bounds, copied up
+  if (int rc = d_bounds.alloc(size_t(n) * 6 * sizeof(float))) return rc;
+  HIP_TRY(hipMemcpy(d_bounds.p, bounds6, d_bounds.bytes, hipMemcpyHostToDevice));
   const auto t_up = std::chrono::steady_clock::now();
   vimg::DeviceTree tree;
-  if (int rc = vimg::build_tree_device(builder, n, up.d.as<float>(), &tree)) return rc;
+  if (int rc = vimg::build_tree_device(builder, n, d_bounds.as<float>(), &tree)) return rc;
   const auto t_built = std::chrono::steady_clock::now();
   if (int rc = download_tree(tree, n, num_nodes, max_depth, nodes, bb, obj_indices)) return rc;
   if (getenv("VIMG_HIP_DIAG")) {
@@ -817,16 +806,12 @@ int build_exported(uint32_t builder, uint32_t n, const float* bounds6, uint32_t*
 
 namespace vimg {
 
-DeviceTree::~DeviceTree() {
-  for (void* p : {(void*)nodes, (void*)bb, (void*)obj_indices})
-    if (p) (void)hipFree(p);
-}
-
 int build_tree_device(uint32_t builder, uint32_t n, const float* d_bounds6, DeviceTree* out) {
-  if (!d_bounds6 || !out || n == 0 || n > (1u << 25)) return VIMG_E_INVALID;
+  if (!d_bounds6 || !out || n == 0 || n > (1u << 25))
+    return fail(VIMG_E_INVALID, "bvh build: null bounds or tree, or a primitive count outside [1, 2^25]");
   if (builder == VIMG_BUILDER_PLOC) return ploc_core(n, d_bounds6, out);
   if (builder == VIMG_BUILDER_LBVH) return lbvh_core(n, d_bounds6, out);
-  return VIMG_E_INVALID;
+  return fail(VIMG_E_INVALID, "bvh build: unknown builder");
 }
 
 }  // namespace vimg

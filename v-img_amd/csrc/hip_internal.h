@@ -4,6 +4,7 @@
 //   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel
 //   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
 //   scene_rebuild.hip  a new tree for a resident scene, its cost       bvh_build.hip    the GPU builders and their cores
+//   device_mem.h       fail / HIP_TRY, and DevBuf / DevEvent: the one owner type of device memory, and of events
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,40 +14,40 @@
 #include <vector>
 
 #include "../../include/vimg_hip.h"
+#include "device_mem.h"
 #include "device_scene.h"
 #include "kernel_tus.h"
 
+#pragma GCC visibility push(hidden)
 struct VimgDeviceScene {
-  vimg::DScene d{};
-  std::vector<void*> allocs;
-  size_t total_bytes = 0;
+  vimg::DScene d{};            // the kernels' view: raw pointers into the buffers below
+  // the tables a rebuild replaces, under their own names; the others, fixed at upload, in upload order
+  vimg::DevBuf nodes, leaf_prims;
+  vimg::DevBuf chain_leaf;     // per chain record {first slot, count} of its whole leaf (uint32_t pairs; empty: no chains)
+  std::vector<vimg::DevBuf> tables;
+  size_t total_bytes = 0;      // of nodes, leaf_prims and tables (vimg_hip_scene_bytes)
   bool textured = false;       // needs the TEX=true kernels (cones, image textures, env map)
   VimgHipOptions opt{};        // the caller's options (VIMG_OPT_AUTO where the policy decides)
   int waves_per_simd = 2;      // LANE register budget by policy (scene size)
   bool too_wide = false;       // resolution beyond the 16-bit pixel coordinates of the slot records
   uint32_t num_cus = 0;
   uint32_t num_leaf_prims = 0;   // records in d.leaf_prims (= primitives of the scene)
-  // scratch owned by the scene: stats, work counter, host-render framebuffer
-  vimg::DeviceStats* d_stats = nullptr;
-  unsigned int* d_counter = nullptr;
-  float* d_frame = nullptr;
-  void* d_pool_cold = nullptr;   // CU scheduler: cold slot records of every workgroup
-  size_t pool_cold_bytes = 0;
-  void* d_stack_ovf = nullptr;   // CU scheduler, deep trees: the stack entries beyond the LDS part, per walking wave
-  size_t stack_ovf_bytes = 0;
-  void* d_pool_state = nullptr;  // CU scheduler: per-pixel record between sample segments
-  size_t pool_state_bytes = 0;
+  // scratch owned by the scene; the last four grow to what a launch asks for and never shrink
+  vimg::DevBuf stats;            // one DeviceStats
+  vimg::DevBuf counter;          // unsigned int[2]: the work counter, the error word of the last launch
+  vimg::DevBuf root_box;         // 6 floats the refit leaves the root's box in
+  vimg::DevBuf frame;            // host renders: the frame before it is copied out
+  vimg::DevBuf pool_cold;        // CU scheduler: cold slot records of every workgroup
+  vimg::DevBuf stack_ovf;        // CU scheduler, deep trees: the stack entries beyond the LDS part, per walking wave
+  vimg::DevBuf pool_state;       // CU scheduler: per-pixel record between sample segments
   uint32_t pool_epoch = 0;       // bumped per launch: tags of earlier launches never match
-  size_t frame_floats = 0;
   // geometry updates (vimg_hip_scene_update_geometry): what the upload knew of the tables and the tree
   uint64_t generation = 0;       // bumped by every change of the resident scene; accumulators remember theirs
   uint32_t num_vertices = 0, num_tris = 0, num_spheres = 0;
   std::vector<std::pair<uint32_t, uint32_t>> normal_rows;   // (first vertex, count) of the meshes with normals, merged
   uint32_t n_internal = 0;       // DNode records of the tree; the n_chain chain records follow them
   uint32_t n_chain = 0;
-  const uint32_t* d_chain_leaf = nullptr;   // per chain record {first slot, count} of its whole leaf
   std::vector<uint32_t> level_begin;        // breadth-first levels of the internal nodes: [level_begin[k], level_begin[k+1])
-  float* d_root_box = nullptr;              // 6 floats the refit leaves the root's box in
   // ray queries (vimg_hip_trace_rays, _occluded): the LDS layout and the blocks per CU of each query build, worked
   // out at the first query and again after vimg_hip_scene_rebuild_bvh (which resets query_ready: both depend on
   // max_depth and num_nodes; nothing else changes the tree's shape, and the options never change after upload)
@@ -63,29 +64,17 @@ struct VimgProgressive {
   VimgDeviceScene* scene = nullptr;
   VimgRenderParams params{};      // samples field unused
   uint64_t items = 0;             // work items of a launch (64 per tile of the shard)
-  void* d_rec[2] = {nullptr, nullptr};   // 32 B per item each; d_rec[cur] holds the state after `samples`
+  vimg::DevBuf rec[2];            // 32 B per item each; rec[cur] holds the state after `samples`
   int cur = 0;
   uint32_t samples = 0;           // samples per pixel so far
-  void* d_scratch = nullptr;      // the means of increments asked for without an output buffer
-  size_t scratch_bytes = 0;
+  vimg::DevBuf scratch;           // the means of increments asked for without an output buffer
   uint64_t generation = 0;        // the scene's generation its records were made in
 };
 
-#pragma GCC visibility push(hidden)
 namespace vimg {
 
 extern hipStream_t g_stream;   // vimg_hip.hip (vimg_hip_init)
 extern int g_device;
-
-int fail(int code, const std::string& msg);   // sets vimg_hip_last_error of this thread; returns code
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return fail(VIMG_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
-int grow(void** p, size_t* have, size_t need);   // a device buffer of at least `need` bytes (contents lost when it grows)
 
 inline uint32_t tiles_of(int n) { return (static_cast<uint32_t>(n) + 7u) / 8u; }
 uint32_t local_tiles(const VimgDeviceScene* s, const VimgRenderParams* p);
@@ -104,18 +93,12 @@ struct LaunchCfg {
 
 // ---- bvh_build.hip: the cores of vimg_hip_build_ploc / _lbvh.  They take the primitive bounds (n x {min.xyz,
 // max.xyz}) on the device and leave the tree in the reference's layout (include/bvh.h:22-57) there too: nodes
-// [num_nodes], bb [(2 num_nodes + 2) x 3], obj_indices [n].  Blocking, on the null stream; VIMG_PLOC_* and
-// VIMG_HIP_DIAG as for the exported builders.
+// [num_nodes] of VimgBVHNode, bb [(2 num_nodes + 2) x 3] floats, obj_indices [n] of uint32_t.  Blocking, on the
+// null stream; VIMG_PLOC_* and VIMG_HIP_DIAG as for the exported builders.
 struct DeviceTree {
-  VimgBVHNode* nodes = nullptr;
-  float* bb = nullptr;
-  uint32_t* obj_indices = nullptr;
+  DevBuf nodes, bb, obj_indices;
   uint32_t num_nodes = 0, max_depth = 0;
   std::vector<uint32_t> level_internal;   // nodes with children on every level that has some, root level first
-  DeviceTree() = default;
-  DeviceTree(const DeviceTree&) = delete;
-  DeviceTree& operator=(const DeviceTree&) = delete;
-  ~DeviceTree();   // frees the three arrays
 };
 int build_tree_device(uint32_t builder /* VIMG_BUILDER_* */, uint32_t n, const float* d_bounds6, DeviceTree* out);
 

@@ -19,7 +19,7 @@ int vimg_hip_post_rgb8(const void* d_rgb, int w, int h, int tonemapper, void* d_
   }
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
   const size_t n = size_t(w) * h;
-  static unsigned int* d_max = nullptr;
+  static unsigned int* d_max = nullptr;   // (deliberately of the process, never freed: per call it would add an allocation to every post step)
   if (!d_max) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_max), sizeof(unsigned int)));
   if (tonemapper == 2) {
     HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(unsigned int), st));
@@ -37,12 +37,6 @@ int vimg_hip_post_rgb8(const void* d_rgb, int w, int h, int tonemapper, void* d_
 // ---- the pre-step of the path on the GPU; host buffers in and out: these
 // replace the host library's OpenMP loops while a scene is being assembled, before the upload
 namespace {
-struct PreBuf {   // device scratch freed on every exit path
-  void* p = nullptr;
-  ~PreBuf() { if (p) (void)hipFree(p); }
-  float* f32() { return static_cast<float*>(p); }
-  uint8_t* u8() { return static_cast<uint8_t*>(p); }
-};
 int pre_ready() {
   if (g_device < 0) return vimg_hip_init(0);
   return VIMG_OK;
@@ -75,9 +69,9 @@ int vimg_hip_build_mip_chain(uint32_t w, uint32_t h, const float* level0, uint32
   if (int rc = pre_ready()) return rc;
   uint32_t levels = 0;
   const uint64_t texels = vimg_hip_mip_chain_texels(w, h, &levels);
-  PreBuf d;
-  HIP_TRY(hipMalloc(&d.p, texels * 3 * sizeof(float)));
-  float* base = d.f32();
+  DevBuf d;
+  if (int rc = d.alloc(texels * 3 * sizeof(float))) return rc;
+  float* base = d.as<float>();
   HIP_TRY(hipMemcpyAsync(base, level0, size_t(w) * h * 3 * sizeof(float), hipMemcpyHostToDevice, g_stream));
   uint64_t prev_off = 0;
   uint32_t pw = w, ph = h;
@@ -106,27 +100,27 @@ int vimg_hip_build_env_cdfs(const float* img, uint32_t w, uint32_t h, float* row
     sin_elev[y] = static_cast<float>(std::sin(3.141592653589793238462643383279502884 * v));
   }
   const size_t n = size_t(w) * h;
-  PreBuf d_img, d_sin, d_lum, d_cdf, d_rowint, d_rowcdf, d_rowtot;
-  HIP_TRY(hipMalloc(&d_img.p, n * 3 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_sin.p, h * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_lum.p, n * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_cdf.p, size_t(h) * (w + 1) * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_rowint.p, h * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_rowcdf.p, (size_t(h) + 1) * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_rowtot.p, sizeof(float)));
+  DevBuf d_img, d_sin, d_lum, d_cdf, d_rowint, d_rowcdf, d_rowtot;
+  if (int rc = d_img.alloc(n * 3 * sizeof(float))) return rc;
+  if (int rc = d_sin.alloc(h * sizeof(float))) return rc;
+  if (int rc = d_lum.alloc(n * sizeof(float))) return rc;
+  if (int rc = d_cdf.alloc(size_t(h) * (w + 1) * sizeof(float))) return rc;
+  if (int rc = d_rowint.alloc(h * sizeof(float))) return rc;
+  if (int rc = d_rowcdf.alloc((size_t(h) + 1) * sizeof(float))) return rc;
+  if (int rc = d_rowtot.alloc(sizeof(float))) return rc;
   HIP_TRY(hipMemcpyAsync(d_img.p, img, n * 3 * sizeof(float), hipMemcpyHostToDevice, g_stream));
   HIP_TRY(hipMemcpyAsync(d_sin.p, sin_elev.data(), h * sizeof(float), hipMemcpyHostToDevice, g_stream));
-  hipLaunchKernelGGL(pre_env_lum_kernel, dim3(pre_grid(n)), dim3(256), 0, g_stream, d_img.f32(), w, h,
-                     d_sin.f32(), d_lum.f32());
+  hipLaunchKernelGGL(pre_env_lum_kernel, dim3(pre_grid(n)), dim3(256), 0, g_stream, d_img.as<float>(), w, h,
+                     d_sin.as<float>(), d_lum.as<float>());
   // one conditional distribution per image row, then the marginal over the row integrals
-  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(h), dim3(64), 0, g_stream, d_lum.f32(), h, w,
-                     d_cdf.f32(), d_rowint.f32());
+  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(h), dim3(64), 0, g_stream, d_lum.as<float>(), h, w,
+                     d_cdf.as<float>(), d_rowint.as<float>());
   hipLaunchKernelGGL(pre_cdf_normalise_kernel, dim3(pre_grid(size_t(h) * (w + 1))), dim3(256), 0, g_stream,
-                     d_cdf.f32(), h, w, d_rowint.f32());
-  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(1), dim3(64), 0, g_stream, d_rowint.f32(), 1u, h,
-                     d_rowcdf.f32(), d_rowtot.f32());
+                     d_cdf.as<float>(), h, w, d_rowint.as<float>());
+  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(1), dim3(64), 0, g_stream, d_rowint.as<float>(), 1u, h,
+                     d_rowcdf.as<float>(), d_rowtot.as<float>());
   hipLaunchKernelGGL(pre_cdf_normalise_kernel, dim3(pre_grid(size_t(h) + 1)), dim3(256), 0, g_stream,
-                     d_rowcdf.f32(), 1u, h, d_rowtot.f32());
+                     d_rowcdf.as<float>(), 1u, h, d_rowtot.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(col_cdfs, d_cdf.p, size_t(h) * (w + 1) * sizeof(float), hipMemcpyDeviceToHost, g_stream));
   HIP_TRY(hipMemcpyAsync(row_cdf, d_rowcdf.p, (size_t(h) + 1) * sizeof(float), hipMemcpyDeviceToHost, g_stream));
@@ -138,14 +132,14 @@ int vimg_hip_lut8_to_float(const uint8_t* in, uint64_t n, const float* lut256, f
   if (!in || !lut256 || !out) return fail(VIMG_E_INVALID, "lut8_to_float: bad arguments");
   if (n == 0) return VIMG_OK;
   if (int rc = pre_ready()) return rc;
-  PreBuf d_in, d_lut, d_out;
-  HIP_TRY(hipMalloc(&d_in.p, n));
-  HIP_TRY(hipMalloc(&d_lut.p, 256 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_out.p, n * sizeof(float)));
+  DevBuf d_in, d_lut, d_out;
+  if (int rc = d_in.alloc(n)) return rc;
+  if (int rc = d_lut.alloc(256 * sizeof(float))) return rc;
+  if (int rc = d_out.alloc(n * sizeof(float))) return rc;
   HIP_TRY(hipMemcpyAsync(d_in.p, in, n, hipMemcpyHostToDevice, g_stream));
   HIP_TRY(hipMemcpyAsync(d_lut.p, lut256, 256 * sizeof(float), hipMemcpyHostToDevice, g_stream));
-  hipLaunchKernelGGL(pre_lut8_kernel, dim3(pre_grid(n)), dim3(256), 0, g_stream, d_in.u8(), size_t(n),
-                     d_lut.f32(), d_out.f32());
+  hipLaunchKernelGGL(pre_lut8_kernel, dim3(pre_grid(n)), dim3(256), 0, g_stream, d_in.as<uint8_t>(), size_t(n),
+                     d_lut.as<float>(), d_out.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost, g_stream));
   HIP_TRY(hipStreamSynchronize(g_stream));
@@ -156,12 +150,12 @@ int vimg_hip_rgb8_to_normal(const uint8_t* rgb8, uint64_t n_pixels, float scale,
   if (!rgb8 || !out) return fail(VIMG_E_INVALID, "rgb8_to_normal: bad arguments");
   if (n_pixels == 0) return VIMG_OK;
   if (int rc = pre_ready()) return rc;
-  PreBuf d_in, d_out;
-  HIP_TRY(hipMalloc(&d_in.p, n_pixels * 3));
-  HIP_TRY(hipMalloc(&d_out.p, n_pixels * 3 * sizeof(float)));
+  DevBuf d_in, d_out;
+  if (int rc = d_in.alloc(n_pixels * 3)) return rc;
+  if (int rc = d_out.alloc(n_pixels * 3 * sizeof(float))) return rc;
   HIP_TRY(hipMemcpyAsync(d_in.p, rgb8, n_pixels * 3, hipMemcpyHostToDevice, g_stream));
-  hipLaunchKernelGGL(pre_normal8_kernel, dim3(pre_grid(n_pixels)), dim3(256), 0, g_stream, d_in.u8(),
-                     size_t(n_pixels), scale, d_out.f32());
+  hipLaunchKernelGGL(pre_normal8_kernel, dim3(pre_grid(n_pixels)), dim3(256), 0, g_stream, d_in.as<uint8_t>(),
+                     size_t(n_pixels), scale, d_out.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_out.p, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, g_stream));
   HIP_TRY(hipStreamSynchronize(g_stream));

@@ -171,27 +171,6 @@ scene_bvh_cost_final(const DScene d, uint32_t n_internal, const uint32_t* __rest
   *cost = (sh[0] + root * ref_weight(d.root_ref, n_internal, chain_leaf)) / root;
 }
 
-namespace {
-
-struct Dev {   // a device buffer of this call
-  void* p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-  void* release() { void* q = p; p = nullptr; return q; }
-};
-
-// the scene's own allocation `old` becomes `now` (same place in the list the scene frees)
-void replace_alloc(VimgDeviceScene* s, const void* old, void* now) {
-  for (void*& p : s->allocs)
-    if (p == old) {
-      p = now;
-      return;
-    }
-  s->allocs.push_back(now);
-}
-
-}  // namespace
-
 }  // namespace vimg
 
 using namespace vimg;
@@ -211,27 +190,27 @@ int vimg_hip_scene_rebuild_bvh(VimgDeviceScene* s, const VimgRebuildOptions* opt
   const uint32_t n = s->num_leaf_prims;
 
   // 1. primitive bounds, after whatever the stream still holds; the builders run on the null stream
-  Dev d_bounds;
-  HIP_TRY(hipMalloc(&d_bounds.p, size_t(n) * 6 * sizeof(float)));
+  DevBuf d_bounds;
+  if (int rc = d_bounds.alloc(size_t(n) * 6 * sizeof(float))) return rc;
   hipLaunchKernelGGL(scene_rebuild_bounds, blocks_for(n), dim3(kBlock), 0, st, s->d, n, d_bounds.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
 
   // 2. the tree, in the reference's layout, on the device
   DeviceTree tree;
-  if (int rc = build_tree_device(builder, n, d_bounds.as<float>(), &tree)) return fail(rc, "rebuild_bvh: the builder failed");
+  if (int rc = build_tree_device(builder, n, d_bounds.as<float>(), &tree)) return rc;   // (the builder's own message stands)
   if (tree.max_depth + 2 > 96) return fail(VIMG_E_INVALID, "rebuild_bvh: BVH deeper than the 94-level stack bound");
   const uint32_t num_nodes = tree.num_nodes;
 
   // 3. the device layout: every node with children at the count of such nodes before it
-  Dev d_packed, d_scanned, d_scan_tmp, d_nodes, d_cls, d_slots;
-  HIP_TRY(hipMalloc(&d_packed.p, size_t(num_nodes) * 8));
-  HIP_TRY(hipMalloc(&d_scanned.p, size_t(num_nodes) * 8));
+  DevBuf d_packed, d_scanned, d_scan_tmp, d_nodes, d_cls, d_slots;
+  if (int rc = d_packed.alloc(size_t(num_nodes) * 8)) return rc;
+  if (int rc = d_scanned.alloc(size_t(num_nodes) * 8)) return rc;
   size_t scan_bytes = 0;
   HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, d_packed.as<unsigned long long>(), d_scanned.as<unsigned long long>(), 0ull,
                                   num_nodes, rocprim::plus<unsigned long long>(), st));
-  HIP_TRY(hipMalloc(&d_scan_tmp.p, std::max<size_t>(scan_bytes, 16)));
-  hipLaunchKernelGGL(scene_rebuild_classify, blocks_for(num_nodes), dim3(kBlock), 0, st, tree.nodes, num_nodes,
+  if (int rc = d_scan_tmp.alloc(std::max<size_t>(scan_bytes, 16))) return rc;
+  hipLaunchKernelGGL(scene_rebuild_classify, blocks_for(num_nodes), dim3(kBlock), 0, st, tree.nodes.as<VimgBVHNode>(), num_nodes,
                      d_packed.as<unsigned long long>());
   HIP_TRY(rocprim::exclusive_scan(d_scan_tmp.p, scan_bytes, d_packed.as<unsigned long long>(), d_scanned.as<unsigned long long>(), 0ull,
                                   num_nodes, rocprim::plus<unsigned long long>(), st));
@@ -240,8 +219,8 @@ int vimg_hip_scene_rebuild_bvh(VimgDeviceScene* s, const VimgRebuildOptions* opt
   HIP_TRY(hipMemcpyAsync(&last[1], d_packed.as<unsigned long long>() + (num_nodes - 1u), 8, hipMemcpyDeviceToHost, st));
   VimgBVHNode root{};
   float root_rows[9];   // bb rows 0 and 2: the root's box
-  HIP_TRY(hipMemcpyAsync(&root, tree.nodes, sizeof(root), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(root_rows, tree.bb, sizeof(root_rows), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&root, tree.nodes.p, sizeof(root), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(root_rows, tree.bb.p, sizeof(root_rows), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const unsigned long long totals = last[0] + last[1];
   const uint32_t n_internal = static_cast<uint32_t>(totals & 0xffffffffull);
@@ -253,37 +232,29 @@ int vimg_hip_scene_rebuild_bvh(VimgDeviceScene* s, const VimgRebuildOptions* opt
   if (begin != n_internal || n_internal >= (1u << 25) || (root.obj_count == 0u) != (n_internal != 0u))
     return fail(VIMG_E_DEVICE, "rebuild_bvh: the builder's levels and its nodes disagree");
   const size_t node_bytes = std::max<size_t>(n_internal, 1) * sizeof(DNode);
-  HIP_TRY(hipMalloc(&d_nodes.p, node_bytes));
+  if (int rc = d_nodes.alloc(node_bytes)) return rc;
   if (n_internal)
-    hipLaunchKernelGGL(scene_rebuild_nodes, blocks_for(num_nodes), dim3(kBlock), 0, st, tree.nodes, tree.bb,
+    hipLaunchKernelGGL(scene_rebuild_nodes, blocks_for(num_nodes), dim3(kBlock), 0, st, tree.nodes.as<VimgBVHNode>(), tree.bb.as<float>(),
                        d_scanned.as<unsigned long long>(), num_nodes, n_internal, d_nodes.as<DNode>());
 
   // 4. the leaf slots in the new order (DTriShade, spheres, prims: by primitive, untouched)
-  HIP_TRY(hipMalloc(&d_cls.p, size_t(n) * 4));
-  HIP_TRY(hipMalloc(&d_slots.p, size_t(n) * sizeof(DLeafPrim)));
+  if (int rc = d_cls.alloc(size_t(n) * 4)) return rc;
+  if (int rc = d_slots.alloc(size_t(n) * sizeof(DLeafPrim))) return rc;
   hipLaunchKernelGGL(scene_rebuild_cls, blocks_for(n), dim3(kBlock), 0, st, s->d, n, d_cls.as<uint32_t>());
-  hipLaunchKernelGGL(scene_rebuild_slots, blocks_for(n), dim3(kBlock), 0, st, s->d, tree.obj_indices, d_cls.as<uint32_t>(), n,
+  hipLaunchKernelGGL(scene_rebuild_slots, blocks_for(n), dim3(kBlock), 0, st, s->d, tree.obj_indices.as<uint32_t>(), d_cls.as<uint32_t>(), n,
                      d_slots.as<DLeafPrim>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
 
   // 5. every step succeeded: swap, and drop what was derived from the old tree's shape
+  // (a move frees what the scene held: the old records, the old slots, the chain-leaf table of an uploaded tree)
   DScene& d = s->d;
-  const size_t old_node_bytes = std::max<size_t>(d.num_nodes, 1) * sizeof(DNode);
-  void* old_nodes = (void*)d.nodes;
-  void* old_slots = (void*)d.leaf_prims;
-  replace_alloc(s, old_nodes, d_nodes.p);
-  replace_alloc(s, old_slots, d_slots.p);
-  d.nodes = (decltype(d.nodes))d_nodes.release();
-  d.leaf_prims = (decltype(d.leaf_prims))d_slots.release();
-  (void)hipFree(old_nodes);
-  (void)hipFree(old_slots);
-  if (s->d_chain_leaf) {
-    std::erase(s->allocs, (void*)s->d_chain_leaf);
-    (void)hipFree((void*)s->d_chain_leaf);
-    s->d_chain_leaf = nullptr;
-  }
-  s->total_bytes = s->total_bytes - old_node_bytes + node_bytes;
+  s->total_bytes = s->total_bytes - s->nodes.bytes + node_bytes;
+  s->nodes = std::move(d_nodes);
+  s->leaf_prims = std::move(d_slots);
+  s->chain_leaf = DevBuf{};
+  d.nodes = (decltype(d.nodes))s->nodes.p;
+  d.leaf_prims = (decltype(d.leaf_prims))s->leaf_prims.p;
   s->waves_per_simd = (s->total_bytes > (32u << 20)) ? 3 : 2;   // (the policy of the upload, on the bytes an upload would count)
   d.num_nodes = n_internal;
   d.max_depth = tree.max_depth;
@@ -302,12 +273,12 @@ int vimg_hip_scene_bvh_cost(VimgDeviceScene* s, void* stream, double* cost) {
   if (g_device < 0) return fail(VIMG_E_DEVICE, "bvh_cost: no device");
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
   const uint32_t num_partial = (s->n_internal + kBlock - 1) / kBlock;
-  Dev d_sums;   // the partial sums, then the result
-  HIP_TRY(hipMalloc(&d_sums.p, (size_t(num_partial) + 1) * sizeof(double)));
+  DevBuf d_sums;   // the partial sums, then the result
+  if (int rc = d_sums.alloc((size_t(num_partial) + 1) * sizeof(double))) return rc;
   if (num_partial)
-    hipLaunchKernelGGL(scene_bvh_cost_partial, dim3(num_partial), dim3(kBlock), 0, st, s->d, s->n_internal, s->d_chain_leaf,
+    hipLaunchKernelGGL(scene_bvh_cost_partial, dim3(num_partial), dim3(kBlock), 0, st, s->d, s->n_internal, s->chain_leaf.as<const uint32_t>(),
                        d_sums.as<double>());
-  hipLaunchKernelGGL(scene_bvh_cost_final, dim3(1), dim3(kBlock), 0, st, s->d, s->n_internal, s->d_chain_leaf, d_sums.as<double>(),
+  hipLaunchKernelGGL(scene_bvh_cost_final, dim3(1), dim3(kBlock), 0, st, s->d, s->n_internal, s->chain_leaf.as<const uint32_t>(), d_sums.as<double>(),
                      num_partial, d_sums.as<double>() + num_partial);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(cost, d_sums.as<double>() + num_partial, sizeof(double), hipMemcpyDeviceToHost, st));

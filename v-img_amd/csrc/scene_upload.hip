@@ -4,8 +4,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numbers>
-#include <type_traits>
 
 #include "hip_internal.h"
 #include "scene_bake.h"
@@ -15,16 +15,12 @@ using namespace vimg;
 
 namespace {
 
+// a table of the scene into `b`, counted in the scene's bytes (an empty table still gets one element's worth)
 template <typename T>
-int upload(VimgDeviceScene* s, const T* host, size_t count, const T** out) {
-  *out = nullptr;
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, bytes));
-  s->allocs.push_back(p);
-  s->total_bytes += bytes;
-  if (count) HIP_TRY(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
-  *out = static_cast<const T*>(p);
+int upload(VimgDeviceScene* s, DevBuf& b, const T* host, size_t count) {
+  if (int rc = b.alloc(std::max<size_t>(count, 1) * sizeof(T))) return rc;
+  s->total_bytes += b.bytes;
+  if (count) HIP_TRY(hipMemcpy(b.p, host, count * sizeof(T), hipMemcpyHostToDevice));
   return VIMG_OK;
 }
 
@@ -400,15 +396,15 @@ int upload_tables(VimgDeviceScene* s, const VimgScene* sc, const Tree& t, const 
                   const std::vector<float>& area_pdf, const std::vector<DLeafPrim>& leaf,
                   const std::vector<DLight>& dlights, const std::vector<uint32_t>& mflags) {
   DScene& d = s->d;
-#define UP(field, host, count)                                                     \
-  do {                                                                             \
-    const std::remove_cv_t<std::remove_pointer_t<decltype(host)>>* p_ = nullptr;   \
-    int rc_ = upload(s, host, count, &p_);                                         \
-    if (rc_) return rc_;                                                           \
-    d.field = (decltype(d.field))p_;                                               \
+#define UP_TO(owner, field, host, count)                     \
+  do {                                                       \
+    DevBuf& b_ = owner;                                      \
+    if (int rc_ = upload(s, b_, host, count)) return rc_;    \
+    d.field = (decltype(d.field))b_.p;                       \
   } while (0)
-  UP(nodes, t.nodes.data(), t.nodes.size());
-  UP(leaf_prims, leaf.data(), leaf.size());
+#define UP(field, host, count) UP_TO(s->tables.emplace_back(), field, host, count)
+  UP_TO(s->nodes, nodes, t.nodes.data(), t.nodes.size());
+  UP_TO(s->leaf_prims, leaf_prims, leaf.data(), leaf.size());
   s->num_leaf_prims = static_cast<uint32_t>(leaf.size());
   UP(prims, sc->prims, sc->num_prims);
   UP(tri_shade, shade.data(), shade.size());
@@ -427,13 +423,10 @@ int upload_tables(VimgDeviceScene* s, const VimgScene* sc, const Tree& t, const 
   UP(dlights, dlights.data(), dlights.size());
   UP(cdf_pool, sc->cdf_pool, sc->num_cdf);
 #undef UP
+#undef UP_TO
   if (!t.chain_leaf.empty()) {   // (refit bookkeeping: not counted in the scene's bytes)
-    void* p = nullptr;
-    if (hipMalloc(&p, t.chain_leaf.size() * sizeof(uint32_t)) != hipSuccess) return fail(VIMG_E_DEVICE, "hipMalloc failed");
-    s->allocs.push_back(p);
-    if (hipMemcpy(p, t.chain_leaf.data(), t.chain_leaf.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-      return fail(VIMG_E_DEVICE, "hipMemcpy failed");
-    s->d_chain_leaf = static_cast<const uint32_t*>(p);
+    if (int rc = s->chain_leaf.alloc(t.chain_leaf.size() * sizeof(uint32_t))) return rc;
+    HIP_TRY(hipMemcpy(s->chain_leaf.p, t.chain_leaf.data(), s->chain_leaf.bytes, hipMemcpyHostToDevice));
   }
   return VIMG_OK;
 }
@@ -482,15 +475,14 @@ int alloc_scratch(VimgDeviceScene* s) {
   hipDeviceProp_t prop{};
   if (hipGetDeviceProperties(&prop, g_device) != hipSuccess) return fail(VIMG_E_DEVICE, "hipGetDeviceProperties failed");
   s->num_cus = static_cast<uint32_t>(prop.multiProcessorCount);
-  if (hipMalloc(reinterpret_cast<void**>(&s->d_stats), sizeof(DeviceStats)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->d_counter), 2 * sizeof(unsigned int)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->d_root_box), 6 * sizeof(float)) != hipSuccess)
-    return fail(VIMG_E_DEVICE, "hipMalloc of scratch failed");
-  if (hipMemset(s->d_counter, 0, 2 * sizeof(unsigned int)) != hipSuccess) return fail(VIMG_E_DEVICE, "hipMemset of scratch failed");
+  if (int rc = s->stats.alloc(sizeof(DeviceStats))) return rc;
+  if (int rc = s->counter.alloc(2 * sizeof(unsigned int))) return rc;
+  if (int rc = s->root_box.alloc(6 * sizeof(float))) return rc;
+  HIP_TRY(hipMemset(s->counter.p, 0, s->counter.bytes));
   return VIMG_OK;
 }
 
-// validated scene -> resident scene; on an error the caller frees what `s` holds by then
+// validated scene -> resident scene; on an error the caller drops `s` and what it holds by then
 int build_scene(VimgDeviceScene* s, const VimgScene* sc, const VimgHipOptions* opts) {
   DScene& d = s->d;
   bake_camera(sc->camera, d);
@@ -541,22 +533,15 @@ int vimg_hip_scene_upload_opts(const VimgScene* sc, const VimgHipOptions* opts, 
   }
   int rc = validate(sc);
   if (rc) return rc;
-  auto* s = new VimgDeviceScene();
-  rc = build_scene(s, sc, opts);
-  if (rc) {
-    vimg_hip_scene_free(s);
-    return rc;
-  }
-  *out = s;
+  auto s = std::make_unique<VimgDeviceScene>();
+  rc = build_scene(s.get(), sc, opts);
+  if (rc) return rc;
+  *out = s.release();
   return VIMG_OK;
 }
 
 int vimg_hip_scene_free(VimgDeviceScene* s) {
   if (!s) return VIMG_OK;
-  for (void* p : s->allocs) (void)hipFree(p);
-  for (void* q : {(void*)s->d_stats, (void*)s->d_counter, (void*)s->d_root_box, (void*)s->d_frame, s->d_pool_cold, s->d_stack_ovf,
-                  s->d_pool_state})
-    if (q) (void)hipFree(q);
   delete s;
   return VIMG_OK;
 }
@@ -585,13 +570,13 @@ int vimg_hip_scene_update_geometry(VimgDeviceScene* s, const VimgGeometryUpdate*
   up.num_slots = s->num_leaf_prims;
   up.n_internal = s->n_internal;
   up.n_chain = s->n_chain;
-  up.chain_leaf = s->d_chain_leaf;
+  up.chain_leaf = s->chain_leaf.as<const uint32_t>();
   up.level_begin = s->level_begin.data();
   up.num_levels = static_cast<uint32_t>(s->level_begin.size() - 1);
-  up.root_box = s->d_root_box;
+  up.root_box = s->root_box.as<float>();
   HIP_TRY(enqueue_scene_update(s->d, up, st));
   float box[6];
-  HIP_TRY(hipMemcpyAsync(box, s->d_root_box, sizeof(box), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(box, s->root_box.p, sizeof(box), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   for (int a = 0; a < 3; ++a) s->d.root_min[a] = box[a], s->d.root_max[a] = box[3 + a];
   return VIMG_OK;

@@ -4,6 +4,7 @@
 // no CPU render path in this library.
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 
 #include "hip_internal.h"
 #include "aux_kernels.h"
@@ -22,16 +23,6 @@ thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
-}
-
-int grow(void** p, size_t* have, size_t need) {
-  if (need <= *have) return VIMG_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  HIP_TRY(hipMalloc(p, need));
-  *have = need;
-  return VIMG_OK;
 }
 
 }  // namespace vimg
@@ -60,25 +51,25 @@ int check_params(const VimgDeviceScene* s, const VimgRenderParams* p) {
 int ensure_pool(VimgDeviceScene* s, LaunchCfg& c) {
   c.args.pool_cold = nullptr;
   if (!c.cold_bytes) return VIMG_OK;
-  if (int rc = grow(&s->d_pool_cold, &s->pool_cold_bytes, c.cold_bytes)) return rc;
-  c.args.pool_cold = (VIMG_GLOBAL v4u*)s->d_pool_cold;
+  if (int rc = s->pool_cold.grow(c.cold_bytes)) return rc;
+  c.args.pool_cold = (VIMG_GLOBAL v4u*)s->pool_cold.p;
   if (c.ovf_bytes) {
-    if (int rc = grow(&s->d_stack_ovf, &s->stack_ovf_bytes, c.ovf_bytes)) return rc;
-    c.args.stack_ovf = (VIMG_GLOBAL uint32_t*)s->d_stack_ovf;
+    if (int rc = s->stack_ovf.grow(c.ovf_bytes)) return rc;
+    c.args.stack_ovf = (VIMG_GLOBAL uint32_t*)s->stack_ovf.p;
   }
   c.args.pool_state = nullptr;
   c.args.pool_epoch = 0;
   if (c.args.pool_segments > 1) {
-    const size_t had = s->pool_state_bytes;
-    if (int rc = grow(&s->d_pool_state, &s->pool_state_bytes, size_t(c.args.num_local_tiles) * 64u * 32u)) return rc;
-    if (s->pool_state_bytes != had) s->pool_epoch = 0xffff0000u;   // a new buffer starts like a wrapped epoch: wiped
+    const size_t had = s->pool_state.bytes;
+    if (int rc = s->pool_state.grow(size_t(c.args.num_local_tiles) * 64u * 32u)) return rc;
+    if (s->pool_state.bytes != had) s->pool_epoch = 0xffff0000u;   // a new buffer starts like a wrapped epoch: wiped
     // tags are epoch + segment index (< 4096): one epoch step per launch, wrap with a wipe
     s->pool_epoch += 4096u;
     if (s->pool_epoch >= 0xffff0000u) {
-      HIP_TRY(hipMemset(s->d_pool_state, 0, s->pool_state_bytes));
+      HIP_TRY(hipMemset(s->pool_state.p, 0, s->pool_state.bytes));
       s->pool_epoch = 4096u;
     }
-    c.args.pool_state = (VIMG_GLOBAL v4u*)s->d_pool_state;
+    c.args.pool_state = (VIMG_GLOBAL v4u*)s->pool_state.p;
     c.args.pool_epoch = s->pool_epoch;
   }
   return VIMG_OK;
@@ -108,20 +99,20 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, 
   c.args.full_stats = full_stats ? 1u : 0u;
   if (c.args.num_local_tiles == 0 && sx < 0) return VIMG_OK;
   // (the work counter only: the error word behind it is sticky until a blocking call or vimg_hip_check reads it)
-  HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(unsigned int), st));
-  if (want_stats) HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DeviceStats), st));
-  DeviceStats* stats = want_stats ? s->d_stats : nullptr;
+  HIP_TRY(hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), st));
+  if (want_stats) HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DeviceStats), st));
+  DeviceStats* stats = want_stats ? s->stats.as<DeviceStats>() : nullptr;
   const void* kernel = launched_kernel_of(s, c, full_stats);
   if (c.lds_bytes > 48u * 1024u)   // ask for the large dynamic-LDS carve-out
     HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(c.lds_bytes)));
   if (c.sched == VIMG_SCHED_CU) {
     if (ev0) HIP_TRY(hipEventRecord(ev0, st));
-    CuKArgs ka{s->d, c.args, d_out, stats, s->d_counter};
+    CuKArgs ka{s->d, c.args, d_out, stats, s->counter.as<unsigned int>()};
     void* kargs[] = {&ka};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(uint32_t(c.cu_waves) * 64u), kargs, c.lds_bytes, st));
   } else {
     if (ev0) HIP_TRY(hipEventRecord(ev0, st));
-    void* kargs[] = {&s->d, &c.args, &d_out, &stats, &s->d_counter};
+    void* kargs[] = {&s->d, &c.args, &d_out, &stats, &s->counter.p};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(256), kargs, c.lds_bytes, st));
   }
   if (ev1) HIP_TRY(hipEventRecord(ev1, st));
@@ -132,8 +123,8 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, 
 // d_counter[1] is the error word of the last launch (raised by render_cu_kernel's watchdog)
 int check_kernel_error(VimgDeviceScene* s) {
   unsigned int words[2] = {0, 0};
-  HIP_TRY(hipMemcpy(words, s->d_counter, sizeof(words), hipMemcpyDeviceToHost));
-  if (words[1] != 0) HIP_TRY(hipMemset(s->d_counter + 1, 0, sizeof(unsigned int)));   // read once
+  HIP_TRY(hipMemcpy(words, s->counter.p, sizeof(words), hipMemcpyDeviceToHost));
+  if (words[1] != 0) HIP_TRY(hipMemset(s->counter.as<unsigned int>() + 1, 0, sizeof(unsigned int)));   // read once
   if (words[1] != 0) {
     // bits of the launch's error word (render_cu_kernel.h: raise): 1 a wave found nothing to do for ten seconds
     // while slots were live, 4 a ring entry was reserved and never written, 8 a compute unit queued more than 2^31 rays or slots in one launch
@@ -148,7 +139,7 @@ int check_kernel_error(VimgDeviceScene* s) {
 
 int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* out) {
   DeviceStats ds{};
-  HIP_TRY(hipMemcpy(&ds, s->d_stats, sizeof(ds), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
   *out = VimgRenderStats{};
   out->closest_rays = ds.closest;
   out->shadow_rays = ds.shadow;
@@ -286,19 +277,15 @@ int vimg_hip_progressive_create(VimgDeviceScene* s, const VimgRenderParams* p, V
   VimgRenderParams q = *p;
   q.samples = 1;   // (ignored: every increment says how many)
   if (int rc = check_params(s, &q)) return rc;
-  VimgProgressive* a = new VimgProgressive{};
+  auto a = std::make_unique<VimgProgressive>();
   a->scene = s;
   a->generation = s->generation;
   a->params = q;
   a->items = uint64_t(local_tiles(s, &q)) * 64u;
   const size_t bytes = std::max<size_t>(a->items, 1) * 32u;
-  for (int k = 0; k < 2; ++k) {
-    if (hipMalloc(&a->d_rec[k], bytes) != hipSuccess) {
-      vimg_hip_progressive_free(a);
-      return fail(VIMG_E_DEVICE, "progressive: hipMalloc of the pixel records failed");
-    }
-  }
-  *out = a;
+  for (auto& r : a->rec)
+    if (int rc = r.alloc(bytes)) return rc;
+  *out = a.release();
   return VIMG_OK;
 }
 
@@ -318,10 +305,10 @@ int vimg_hip_progressive_render(VimgDeviceScene* s, VimgProgressive* a, uint32_t
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
   if (!d_out) {   // advance only: the means go to a buffer of the accumulator's
     const size_t floats = (p.tile_world == 1 ? size_t(s->d.res_x) * s->d.res_y : size_t(a->items)) * 3u;
-    if (int rc = grow(&a->d_scratch, &a->scratch_bytes, std::max<size_t>(floats, 3) * sizeof(float))) return rc;
-    d_out = a->d_scratch;
+    if (int rc = a->scratch.grow(std::max<size_t>(floats, 3) * sizeof(float))) return rc;
+    d_out = a->scratch.p;
   }
-  const ProgLaunch pl{a->samples, a->d_rec[a->cur], a->d_rec[a->cur ^ 1]};
+  const ProgLaunch pl{a->samples, a->rec[a->cur].p, a->rec[a->cur ^ 1].p};
   int rc = enqueue_render(s, &p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1, nullptr,
                           nullptr, &pl);
   if (rc) return rc;
@@ -344,8 +331,6 @@ int vimg_hip_progressive_reset(VimgProgressive* a) {
 
 int vimg_hip_progressive_free(VimgProgressive* a) {
   if (!a) return VIMG_OK;
-  for (void* q : {a->d_rec[0], a->d_rec[1], a->d_scratch})
-    if (q) (void)hipFree(q);
   delete a;
   return VIMG_OK;
 }
@@ -379,15 +364,10 @@ int vimg_hip_render_to_host(VimgDeviceScene* s, const VimgRenderParams* p, float
   if (!out_host) return fail(VIMG_E_INVALID, "null output pointer");
   if (p->tile_world != 1) return fail(VIMG_E_INVALID, "render_to_host needs tile_world == 1");
   const size_t floats = size_t(s->d.res_x) * s->d.res_y * 3;
-  if (s->frame_floats < floats) {
-    if (s->d_frame) (void)hipFree(s->d_frame);
-    s->d_frame = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_frame), floats * sizeof(float)));
-    s->frame_floats = floats;
-  }
-  rc = vimg_hip_render(s, p, s->d_frame, nullptr, stats);
+  if ((rc = s->frame.grow(floats * sizeof(float)))) return rc;
+  rc = vimg_hip_render(s, p, s->frame.p, nullptr, stats);
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(out_host, s->d_frame, floats * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_host, s->frame.p, floats * sizeof(float), hipMemcpyDeviceToHost));
   return VIMG_OK;
 }
 
@@ -397,14 +377,11 @@ int vimg_hip_trace_pixel(VimgDeviceScene* s, const VimgRenderParams* p, int x, i
   if (rc) return rc;
   if (!out_host || x < 0 || y < 0 || x >= s->d.res_x || y >= s->d.res_y)
     return fail(VIMG_E_INVALID, "trace_pixel: pixel out of range");
-  if (s->frame_floats < 3) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_frame), 3 * sizeof(float)));
-    s->frame_floats = 3;
-  }
-  rc = enqueue_render(s, p, s->d_frame, g_stream, false, false, x, y);
+  if ((rc = s->frame.grow(3 * sizeof(float)))) return rc;
+  rc = enqueue_render(s, p, s->frame.as<float>(), g_stream, false, false, x, y);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(g_stream));
-  HIP_TRY(hipMemcpy(out_host, s->d_frame, 3 * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_host, s->frame.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
   return VIMG_OK;
 }
 
@@ -431,17 +408,17 @@ int vimg_hip_time_renders(VimgDeviceScene* s, const VimgRenderParams* p, void* d
   int rc = check_params(s, p);
   if (rc) return rc;
   if (!d_out || steps <= 0 || !ms_per_launch) return fail(VIMG_E_INVALID, "time_renders: bad arguments");
-  std::vector<hipEvent_t> ev(size_t(steps) * 2);
-  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+  std::vector<DevEvent> ev(size_t(steps) * 2);
+  for (auto& e : ev)
+    if (int rc2 = e.create()) return rc2;
   for (int i = 0; i < steps; ++i) {
     // the counter / queue resets are part of a launch's prologue; the events bracket the kernel only
-    if (int rc2 = enqueue_render(s, p, static_cast<float*>(d_out), g_stream, false, false, -1, -1, ev[2 * i], ev[2 * i + 1]))
+    if (int rc2 = enqueue_render(s, p, static_cast<float*>(d_out), g_stream, false, false, -1, -1, ev[2 * i].e, ev[2 * i + 1].e))
       return rc2;
   }
   HIP_TRY(hipStreamSynchronize(g_stream));
   if (int rc2 = check_kernel_error(s)) return rc2;
-  for (int i = 0; i < steps; ++i) HIP_TRY(hipEventElapsedTime(&ms_per_launch[i], ev[2 * i], ev[2 * i + 1]));
-  for (auto& e : ev) (void)hipEventDestroy(e);
+  for (int i = 0; i < steps; ++i) HIP_TRY(hipEventElapsedTime(&ms_per_launch[i], ev[2 * i].e, ev[2 * i + 1].e));
   return VIMG_OK;
 }
 
@@ -451,24 +428,22 @@ int vimg_hip_probe(VimgDeviceScene* s, int kind, int n, const float* in_host, fl
   static const int n_out[9] = {0, 8, 28, 1, 5, 7, 10, 4, 5};
   if (!s || kind < 1 || kind > 8 || n <= 0 || !in_host || !out_host)
     return fail(VIMG_E_INVALID, "probe: bad arguments");
-  float *d_in = nullptr, *d_out = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), size_t(n) * n_in[kind] * sizeof(float)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), size_t(n) * n_out[kind] * sizeof(float)));
-  HIP_TRY(hipMemcpy(d_in, in_host, size_t(n) * n_in[kind] * sizeof(float), hipMemcpyHostToDevice));
+  DevBuf d_in, d_out;
+  if (int rc = d_in.alloc(size_t(n) * n_in[kind] * sizeof(float))) return rc;
+  if (int rc = d_out.alloc(size_t(n) * n_out[kind] * sizeof(float))) return rc;
+  HIP_TRY(hipMemcpy(d_in.p, in_host, size_t(n) * n_in[kind] * sizeof(float), hipMemcpyHostToDevice));
   VimgRenderParams p{VIMG_INTEGRATOR_MIS, 1, 1, 0, 1};
   LaunchCfg c = make_launch_lane(s, &p, -1, -1);
   const uint32_t grid = (uint32_t(n) + 255) / 256;
   if (s->textured)
     hipLaunchKernelGGL(probe_kernel<true>, dim3(grid), dim3(256), c.lds_bytes, g_stream, s->d, c.args,
-                       kind, n, d_in, d_out);
+                       kind, n, d_in.as<float>(), d_out.as<float>());
   else
     hipLaunchKernelGGL(probe_kernel<false>, dim3(grid), dim3(256), c.lds_bytes, g_stream, s->d, c.args,
-                       kind, n, d_in, d_out);
+                       kind, n, d_in.as<float>(), d_out.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(g_stream));
-  HIP_TRY(hipMemcpy(out_host, d_out, size_t(n) * n_out[kind] * sizeof(float), hipMemcpyDeviceToHost));
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
+  HIP_TRY(hipMemcpy(out_host, d_out.p, size_t(n) * n_out[kind] * sizeof(float), hipMemcpyDeviceToHost));
   return VIMG_OK;
 }
 
