@@ -200,8 +200,8 @@ int vimg_hip_render(VimgDeviceScene* scene, const VimgRenderParams* params, void
 /* Progressive rendering: one frame (or shard) of `scene` rendered a few samples at a time.  An accumulator
  * is bound to one scene and one set of parameters: integrator, depth, tile_rank and tile_world are fixed
  * for its life, params->samples is ignored.  It keeps a 32-byte record per pixel of the launch (the RNG
- * state and the float sum, in the compact tile-major order of shards; twice, so that a failed increment
- * leaves the last good state).
+ * state and the float sum - and the pixel's count and statistics, see adaptive sampling below - in the compact
+ * tile-major order of shards; twice, so that a failed increment leaves the last good state).
  * Contract: increments n_1 .. n_k give, after each one, exactly the bits vimg_hip_render gives at
  * samples = n_1 + .. + n_i - the same per-pixel PCG stream, the same jitter index, the same division -
  * for every integrator, every shard and every scheduler configuration of this library.
@@ -221,6 +221,61 @@ int vimg_hip_progressive_render(VimgDeviceScene* scene, VimgProgressive* acc, ui
 uint64_t vimg_hip_progressive_samples(const VimgProgressive* acc);
 int vimg_hip_progressive_reset(VimgProgressive* acc);
 int vimg_hip_progressive_free(VimgProgressive* acc);
+
+/* Adaptive sampling on an accumulator: increments that reach only some pixels, and a per-pixel
+ * error to choose them by.  The accumulator keeps, in the three spare words of its 32-byte record, each pixel's
+ * count N, the number K of increments it has taken part in, and M2 (below).  Per-pixel buffers are DEVICE pointers
+ * in the pixel order of d_out_rgb for the accumulator: the image layout (x + (H-1-y)*W) for tile_world == 1, the
+ * compact tile-major layout of the shard otherwise (off-image slots of ragged tiles: never selected, count 0).
+ *  _render_masked : adds `samples` samples to exactly the pixels whose d_mask byte (uint8) is non-zero, then
+ *      writes EVERY pixel's mean to d_out_rgb (NULL = advance only).  d_mask == NULL selects every pixel; on an
+ *      accumulator whose pixels all stand at one count that is vimg_hip_progressive_render itself, the same single
+ *      launch over every item (plus the pass that keeps N, K and M2).  Masked and unmasked calls follow each
+ *      other in any order.
+ *      Contract: after any sequence of calls a pixel whose count is N carries exactly the bits vimg_hip_render
+ *      gives that pixel at samples = N - its PCG stream goes on from its record, the jitter index of a sample is
+ *      px + py + (N before the call) + its number within the call, the mean is one division sum / float(N) - for
+ *      all four integrators, every shard and every scheduler configuration.  A pixel at N == 0 is written 0 0 0.
+ *      Cost: the sample base is a constant of a launch, so the selected pixels are rendered one launch per
+ *      DISTINCT COUNT among them, in ascending count, each over the compacted list of its pixels and each with
+ *      the ~1.6 ms tail of a launch; each class also costs one 16-byte read-back.  The adaptive
+ *      loop (select, then a masked increment) only ever has one class.
+ *      All or nothing: every launch writes the accumulator's other buffer; buffers, counts, statistics and
+ *      _launches advance only when every launch succeeded and the scene's error word is clean, otherwise the
+ *      accumulator stays at its last good state.  VIMG_E_INVALID, found before anything is enqueued and with
+ *      the accumulator untouched: samples == 0, NULL scene or accumulator, another scene's accumulator, a
+ *      scene changed since the records were made (reset first), a selected pixel whose count would pass
+ *      UINT32_MAX.  (The last one is decided on the host from the largest count of any pixel; only when THAT
+ *      would pass the bound does it depend on which pixels the device mask selects, and the largest selected
+ *      count is then read back - two read-only kernels and 4 bytes - before any render launch.)  stats (HOST, optional): the events of this call's launches, summed; paths =
+ *      selected pixels x samples.
+ *  _samples (above) : every pixel's count while all pixels stand at one; after masked calls the largest count.
+ *  _launches : render launches of the successful calls since creation or the last reset.
+ *  _state : the records, each buffer optional (NULL): d_sum_rgb 3 float32 per pixel (the running sums), d_count
+ *      uint32 N, d_batches uint32 K, d_m2 float32 M2.  Only enqueues on `stream`.
+ *  _error : one float32 per pixel, the estimated relative standard error of the pixel's mean luminance (err
+ *      below; +inf while K < 2).  Only enqueues.
+ *  _select : d_mask (uint8 per pixel) = 1 where (err > target && N < max_samples) || K < 2, else 0; *active_out
+ *      (HOST) = the number of ones, one 4-byte read-back after which the call returns.  target must be >= 0.
+ * The statistic, in float32 with IEEE +, -, *, /, sqrt and no fused multiply-add, evaluated in the order written
+ * (a numpy float32 restatement gives the same bits).  Y(v) = v.x * 0.212671f + v.y * 0.715160f + v.z * 0.072169f,
+ * the luminance of the post chain's Reinhard operator.  An increment of n samples takes a selected pixel's sums
+ * from S to S', its count from N to N' = N + n:
+ *      b     = Y(S' - S) / float(n)                    (the increment's batch mean; S' - S per component)
+ *      m_old = N ? Y(S) / float(N) : 0                 m_new = Y(S') / float(N')
+ *      M2'   = M2 + float(n) * (b - m_old) * (b - m_new)       ((float(n) * (b - m_old)) * (b - m_new))
+ *      K'    = K + 1
+ *      err   = K < 2 ? +inf : sqrt((M2 < 0 ? 0 : M2) / float(K - 1) / float(N)) / (fabs(Y(S) / float(N)) + 1e-3f)
+ * vimg_hip_progressive_reset clears N, K and M2 with the sums; it waits for the device first, so read-outs that
+ * were only enqueued (_state, _error) are finished before the records are wiped. */
+int vimg_hip_progressive_render_masked(VimgDeviceScene* scene, VimgProgressive* acc, uint32_t samples,
+                                       const uint8_t* d_mask, void* d_out_rgb, void* stream, VimgRenderStats* stats);
+uint64_t vimg_hip_progressive_launches(const VimgProgressive* acc);
+int vimg_hip_progressive_state(VimgProgressive* acc, void* d_sum_rgb, void* d_count, void* d_batches, void* d_m2,
+                               void* stream);
+int vimg_hip_progressive_error(VimgProgressive* acc, void* d_err, void* stream);
+int vimg_hip_progressive_select(VimgProgressive* acc, float target, uint32_t max_samples, uint8_t* d_mask,
+                                void* stream, uint32_t* active_out);
 
 /* Same as vimg_hip_render but only enqueues (no host wait, no stats); used by bench.py to time
  * back-to-back launches with HIP events on `stream`.  A scene renders one frame at a time: its

@@ -257,6 +257,11 @@ HIP_SYMBOLS = {
     "vimg_hip_progressive_samples": (C.c_uint64, [C.c_void_p]),
     "vimg_hip_progressive_reset": (C.c_int, [C.c_void_p]),
     "vimg_hip_progressive_free": (C.c_int, [C.c_void_p]),
+    "vimg_hip_progressive_render_masked": (C.c_int, [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, PStats]),
+    "vimg_hip_progressive_launches": (C.c_uint64, [C.c_void_p]),
+    "vimg_hip_progressive_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_hip_progressive_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_hip_progressive_select": (C.c_int, [C.c_void_p, f32, u32, C.c_void_p, C.c_void_p, C.POINTER(u32)]),
     "vimg_hip_check": (C.c_int, [C.c_void_p]),
     "vimg_hip_render_to_host": (C.c_int, [C.c_void_p, PParams, Pf32, PStats]),
     "vimg_hip_trace_pixel": (C.c_int, [C.c_void_p, PParams, C.c_int, C.c_int, Pf32]),

@@ -4,7 +4,8 @@
 // -d "x y" single-pixel trace, -b 0 binned / 1 sweep BVH (default 0 as main.cpp:183-187),
 // -m factor heatmap mode (BVH traversal cost, main.cpp:62-65,98-100,250-256), plus
 // -s spp override, -p step progressive rendering (increments of `step` samples, the PNG rewritten
-// after each; the last one is byte-identical to a plain run) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
+// after each; the last one is byte-identical to a plain run), -e target adaptive sampling on top of -p (increments
+// only where the estimated relative error of a pixel is above `target`, -s the cap per pixel) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
 // here on the host (libvimg_host); the render and the post chain go through the C ABI of
 // libvimg_hip.
 #include <algorithm>
@@ -28,7 +29,7 @@ int main(int argc, char** argv) {
   std::string scene_path, out_path = "v_img_amd.png";
   int tonemapper = 0, bvh_type = VIMG_BVH_BINNED, px = -1, py = -1;   // clamp, as src/main.cpp:46
   long spp_override = -1, prog_step = 0;
-  float heatmap_max = -1.f;
+  float heatmap_max = -1.f, err_target = -1.f;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -42,6 +43,7 @@ int main(int argc, char** argv) {
     else if (a == "-b") bvh_type = std::atoi(next()) == 1 ? VIMG_BVH_SWEEP : VIMG_BVH_BINNED;
     else if (a == "-s") spp_override = std::atol(next());
     else if (a == "-p") prog_step = std::atol(next());
+    else if (a == "-e") err_target = static_cast<float>(std::atof(next()));
     else if (a == "-m") heatmap_max = static_cast<float>(std::atof(next()));
     else if (a == "-o") out_path = next();
     else if (a == "-d") {
@@ -50,9 +52,13 @@ int main(int argc, char** argv) {
         return 2;
       }
     } else {
-      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step] [-d \"x y\"] [-o out.png]\n");
+      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-o out.png]\n");
       return 2;
     }
+  }
+  if (err_target >= 0.f && prog_step <= 0) {   // adaptive sampling is a loop of increments: it needs their size
+    std::fprintf(stderr, "-e target needs -p step\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-o out.png]\n");
+    return 2;
   }
   if (scene_path.empty()) {
     std::fprintf(stderr, "No input file given\n");
@@ -131,9 +137,26 @@ int main(int argc, char** argv) {
       return 1;
     }
     std::vector<uint8_t> rgb8(n * 3);
+    // -e: two increments for everyone (the error needs two), then only the pixels vimg_hip_progressive_select
+    // names - those all stand at `done`, so every step is one launch - until none is left or -s is reached
+    const bool adaptive = err_target >= 0.f;
+    uint8_t* d_mask = nullptr;
+    if (adaptive && hipMalloc(reinterpret_cast<void**>(&d_mask), n) != hipSuccess) {
+      std::fprintf(stderr, "hipMalloc failed\n");
+      return 1;
+    }
+    uint32_t active = static_cast<uint32_t>(n);
     for (uint32_t done = 0; done < params.samples;) {
       const uint32_t k = static_cast<uint32_t>(std::min<long>(prog_step, long(params.samples - done)));
-      if (vimg_hip_progressive_render(dev, acc, k, d_rgb, nullptr, nullptr) != VIMG_OK) {
+      const bool masked = adaptive && done >= 2u * static_cast<uint32_t>(prog_step);
+      if (masked) {
+        if (vimg_hip_progressive_select(acc, err_target, params.samples, d_mask, nullptr, &active) != VIMG_OK) {
+          std::fprintf(stderr, "select failed: %s\n", vimg_hip_last_error());
+          return 1;
+        }
+        if (active == 0) break;
+      }
+      if (vimg_hip_progressive_render_masked(dev, acc, k, masked ? d_mask : nullptr, d_rgb, nullptr, nullptr) != VIMG_OK) {
         std::fprintf(stderr, "render failed: %s\n", vimg_hip_last_error());
         return 1;
       }
@@ -144,9 +167,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "preview write failed: %s %s\n", vimg_hip_last_error(), vimg_host_last_error());
         return 1;
       }
-      std::printf("samples %u / %u (%.3f s)\n", done, params.samples, now_s() - t3);
+      if (adaptive)
+        std::printf("samples %u / %u, active pixels %u (%.3f s)\n", done, params.samples, active, now_s() - t3);
+      else
+        std::printf("samples %u / %u (%.3f s)\n", done, params.samples, now_s() - t3);
       std::fflush(stdout);
     }
+    if (d_mask) (void)hipFree(d_mask);
     vimg_hip_progressive_free(acc);
   } else {
     if (vimg_hip_render(dev, &params, d_rgb, nullptr, &st) != VIMG_OK) {

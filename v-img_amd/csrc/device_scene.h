@@ -160,6 +160,11 @@ struct RenderArgs {
   float spp_div;                    // static_cast<float>(sample_base + samples): the divisor of the mean
   const VIMG_GLOBAL v4u* prog_in;   // per work item {rng lo, rng hi, -, -}{acc.xyz, -}, in the launch's item order
   VIMG_GLOBAL v4u* prog_out;        // the same records after this launch (another buffer: a failed launch leaves prog_in as it was)
+  // masked progressive launches (vimg_hip_progressive_render_masked, progressive_adaptive.hip): the work items of
+  // the launch are item_list[0 .. item_count), ascending; a claim's index is looked up there and everything
+  // else (pixel, records, output offset) goes by the item found.  Other launches: nullptr, 0
+  const VIMG_GLOBAL uint32_t* item_list;
+  uint32_t item_count;
 };
 
 struct DeviceStats {

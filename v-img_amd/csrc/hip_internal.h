@@ -66,9 +66,16 @@ struct VimgProgressive {
   uint64_t items = 0;             // work items of a launch (64 per tile of the shard)
   vimg::DevBuf rec[2];            // 32 B per item each; rec[cur] holds the state after `samples`
   int cur = 0;
-  uint32_t samples = 0;           // samples per pixel so far
+  uint32_t samples = 0;           // samples per pixel so far: every pixel's count while `uniform`, else the largest
   vimg::DevBuf scratch;           // the means of increments asked for without an output buffer
   uint64_t generation = 0;        // the scene's generation its records were made in
+  // adaptive sampling (progressive_adaptive.hip): the records also keep each pixel's count, increments and M2
+  bool uniform = true;            // every pixel stands at `samples` (no masked call since the last reset left some behind)
+  uint64_t valid_items = 0;       // items that are pixels (ragged tiles have slots off the image)
+  uint64_t launches = 0;          // render launches of the successful calls since the last reset
+  vimg::DevBuf item_list;         // the work items of one count class, `items` words
+  vimg::DevBuf block_counts;      // members per workgroup of the list kernels, then their offsets
+  vimg::DevBuf ctl;               // control words of a call (adaptive_kernels.h: ACTL_*)
 };
 
 namespace vimg {
@@ -101,6 +108,27 @@ struct DeviceTree {
   std::vector<uint32_t> level_internal;   // nodes with children on every level that has some, root level first
 };
 int build_tree_device(uint32_t builder /* VIMG_BUILDER_* */, uint32_t n, const float* d_bounds6, DeviceTree* out);
+
+// ---- vimg_hip.hip: the one path every render takes, shared with progressive_adaptive.hip
+// A progressive launch: p->samples more samples for pixels that have had `base`, their records read from `in`
+// (when base > 0) and written to `out`; item_list, when given, names the work items of the launch (a masked
+// increment's count class); keep_stats adds the launch's events to the scene's instead of starting them at 0.
+struct ProgLaunch {
+  uint32_t base;
+  const void* in;
+  void* out;
+  const uint32_t* item_list = nullptr;
+  uint32_t item_count = 0;
+  bool keep_stats = false;
+};
+int check_params(const VimgDeviceScene* s, const VimgRenderParams* p);
+// Enqueues one render on `st` (counter / queue resets, then the kernel); ev0 / ev1, when given, are recorded
+// right before and right after the kernel itself.
+int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, hipStream_t st, bool full_stats,
+                   bool want_stats, int sx, int sy, hipEvent_t ev0, hipEvent_t ev1, const ProgLaunch* prog);
+int check_kernel_error(VimgDeviceScene* s);    // reads (and clears) the scene's error word
+uint64_t fetch_shard_pixels(const VimgDeviceScene* s, const VimgRenderParams* p);   // pixels the shard owns
+int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* out);   // (paths = pixels x p->samples)
 
 // ---- launch_policy.hip
 LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);

@@ -177,7 +177,7 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] const uint32_t stat_inc = full_stats ? 1u : 0u;                                                      \
   [[maybe_unused]] const uint32_t W = static_cast<uint32_t>(g.res_x), H = static_cast<uint32_t>(g.res_y);               \
   [[maybe_unused]] const bool single = A.single_x >= 0;                                                                 \
-  [[maybe_unused]] const uint32_t total_items = single ? 1u : A.num_local_tiles * 64u;                                  \
+  [[maybe_unused]] const uint32_t total_items = single ? 1u : (A.item_list ? A.item_count : A.num_local_tiles * 64u);  \
   [[maybe_unused]] const uint32_t n_seg = A.pool_segments, seg_len = A.pool_seg_len;                                    \
   [[maybe_unused]] const uint32_t total_claims = total_items * n_seg;                                                   \
   [[maybe_unused]] constexpr uint32_t roulette_threshold = 5;                                                           \
@@ -790,6 +790,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         } else {
           const uint32_t seg = claim / total_items;
           item = claim - seg * total_items;
+          if (A.item_list) item = A.item_list[item];   // a masked launch: the claim names an entry of its list
           bool valid = true;
           if (single) {
             px = static_cast<uint32_t>(A.single_x), py = static_cast<uint32_t>(A.single_y);

@@ -1555,7 +1555,7 @@ render_kernel(const DScene g, const RenderArgs A, float* __restrict__ out,
   const bool full_stats = A.full_stats != 0;
   const uint32_t W = static_cast<uint32_t>(g.res_x), H = static_cast<uint32_t>(g.res_y);
   const bool single = A.single_x >= 0;
-  const uint32_t total_items = single ? 1u : A.num_local_tiles * 64u;
+  const uint32_t total_items = single ? 1u : (A.item_list ? A.item_count : A.num_local_tiles * 64u);
   constexpr uint32_t roulette_threshold = 5;
 
   Counters cnt{0, 0, 0, 0, 0, 0, 0, 0};
@@ -1591,6 +1591,7 @@ render_kernel(const DScene g, const RenderArgs A, float* __restrict__ out,
           if (item >= total_items) {
             alive = false;
           } else {
+            if (A.item_list) item = A.item_list[item];   // a masked launch: the claim names an entry of its list
             bool valid = true;
             if (single) {
               px = static_cast<uint32_t>(A.single_x), py = static_cast<uint32_t>(A.single_y);

@@ -29,7 +29,7 @@ int fail(int code, const std::string& msg) {
 
 using namespace vimg;
 
-namespace {
+namespace vimg {
 
 int check_params(const VimgDeviceScene* s, const VimgRenderParams* p) {
   if (!s || !p) return fail(VIMG_E_INVALID, "null scene or params");
@@ -44,6 +44,10 @@ int check_params(const VimgDeviceScene* s, const VimgRenderParams* p) {
                                 "GroupOfEmitters::sample is undefined without one)");
   return VIMG_OK;
 }
+
+}  // namespace vimg
+
+namespace {
 
 // The CU scheduler keeps the cold records of its path slots in global memory, and deep trees the stack
 // entries beyond the LDS part: one region per workgroup (per walking wave), owned by the scene and grown on
@@ -75,32 +79,30 @@ int ensure_pool(VimgDeviceScene* s, LaunchCfg& c) {
   return VIMG_OK;
 }
 
-// A progressive launch (vimg_hip_progressive_render): p->samples more samples for pixels that have had
-// `base`, their records read from `in` (when base > 0) and written to `out`.
-struct ProgLaunch {
-  uint32_t base;
-  const void* in;
-  void* out;
-};
+}  // namespace
+
+namespace vimg {
 
 // Enqueues one render on `st` (counter / queue resets, then the kernel); ev0 / ev1, when given, are
 // recorded right before and right after the kernel itself.
 int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, hipStream_t st,
-                   bool full_stats, bool want_stats, int sx, int sy, hipEvent_t ev0 = nullptr,
-                   hipEvent_t ev1 = nullptr, const ProgLaunch* prog = nullptr) {
+                   bool full_stats, bool want_stats, int sx, int sy, hipEvent_t ev0, hipEvent_t ev1,
+                   const ProgLaunch* prog) {
   LaunchCfg c = make_launch(s, p, sx, sy);
   if (prog) {
     c.args.sample_base = prog->base;
     c.args.spp_div = static_cast<float>(prog->base + p->samples);   // (the caller keeps the total <= UINT32_MAX)
     c.args.prog_in = (const VIMG_GLOBAL v4u*)prog->in;
     c.args.prog_out = (VIMG_GLOBAL v4u*)prog->out;
+    c.args.item_list = (const VIMG_GLOBAL uint32_t*)prog->item_list;
+    c.args.item_count = prog->item_count;
   }
   if (int rc = ensure_pool(s, c)) return rc;
   c.args.full_stats = full_stats ? 1u : 0u;
   if (c.args.num_local_tiles == 0 && sx < 0) return VIMG_OK;
   // (the work counter only: the error word behind it is sticky until a blocking call or vimg_hip_check reads it)
   HIP_TRY(hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), st));
-  if (want_stats) HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DeviceStats), st));
+  if (want_stats && !(prog && prog->keep_stats)) HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DeviceStats), st));
   DeviceStats* stats = want_stats ? s->stats.as<DeviceStats>() : nullptr;
   const void* kernel = launched_kernel_of(s, c, full_stats);
   if (c.lds_bytes > 48u * 1024u)   // ask for the large dynamic-LDS carve-out
@@ -137,6 +139,17 @@ int check_kernel_error(VimgDeviceScene* s) {
   return VIMG_OK;
 }
 
+// pixels owned by this shard (ragged edge tiles counted exactly)
+uint64_t fetch_shard_pixels(const VimgDeviceScene* s, const VimgRenderParams* p) {
+  const uint32_t W = s->d.res_x, H = s->d.res_y, ty_n = tiles_of(H), total = tiles_of(W) * ty_n;
+  uint64_t px = 0;
+  for (uint32_t t = p->tile_rank; t < total; t += p->tile_world) {
+    uint32_t tx = t / ty_n, ty = t % ty_n;
+    px += uint64_t(std::min(8u, W - tx * 8)) * std::min(8u, H - ty * 8);
+  }
+  return px;
+}
+
 int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* out) {
   DeviceStats ds{};
   HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
@@ -148,14 +161,7 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
   out->prim_tests = ds.prim;
   out->sphere_tests = ds.sphere;
   out->nan_samples = ds.nan_samples;
-  // pixels owned by this shard (ragged edge tiles counted exactly)
-  const uint32_t W = s->d.res_x, H = s->d.res_y, ty_n = tiles_of(H), total = tiles_of(W) * ty_n;
-  uint64_t px = 0;
-  for (uint32_t t = p->tile_rank; t < total; t += p->tile_world) {
-    uint32_t tx = t / ty_n, ty = t % ty_n;
-    px += uint64_t(std::min(8u, W - tx * 8)) * std::min(8u, H - ty * 8);
-  }
-  out->paths = px * p->samples;
+  out->paths = fetch_shard_pixels(s, p) * p->samples;
   if (getenv("VIMG_HIP_DIAG"))
     std::fprintf(stderr, "[vimg diag] wave trips: descend %llu (lane visits %llu, util %.3f)  prim %llu (lane tests %llu, util %.3f)  main-loop iterations %llu\n",
                  ds.trip_descend, ds.internal, ds.trip_descend ? double(ds.internal) / (64.0 * ds.trip_descend) : 0.0,
@@ -206,7 +212,7 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
   return VIMG_OK;
 }
 
-}  // namespace
+}  // namespace vimg
 
 extern "C" {
 
@@ -244,7 +250,7 @@ int vimg_hip_render_async(VimgDeviceScene* s, const VimgRenderParams* p, void* d
   if (rc) return rc;
   if (!d_out) return fail(VIMG_E_INVALID, "null output pointer");
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
-  return enqueue_render(s, p, static_cast<float*>(d_out), st, false, false, -1, -1);
+  return enqueue_render(s, p, static_cast<float*>(d_out), st, false, false, -1, -1, nullptr, nullptr, nullptr);
 }
 
 int vimg_hip_check(VimgDeviceScene* s) {
@@ -258,7 +264,7 @@ int vimg_hip_render(VimgDeviceScene* s, const VimgRenderParams* p, void* d_out, 
   if (rc) return rc;
   if (!d_out) return fail(VIMG_E_INVALID, "null output pointer");
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
-  rc = enqueue_render(s, p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1);
+  rc = enqueue_render(s, p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1, nullptr, nullptr, nullptr);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   if (int rc2 = check_kernel_error(s)) return rc2;
@@ -283,48 +289,31 @@ int vimg_hip_progressive_create(VimgDeviceScene* s, const VimgRenderParams* p, V
   a->params = q;
   a->items = uint64_t(local_tiles(s, &q)) * 64u;
   const size_t bytes = std::max<size_t>(a->items, 1) * 32u;
-  for (auto& r : a->rec)
+  for (auto& r : a->rec) {
     if (int rc = r.alloc(bytes)) return rc;
+    HIP_TRY(hipMemset(r.p, 0, bytes));   // counts, increments and M2 of every pixel start at 0
+  }
+  a->valid_items = fetch_shard_pixels(s, &q);
   *out = a.release();
   return VIMG_OK;
 }
 
+// (the increments themselves, masked or not, and the accumulator's read-outs: progressive_adaptive.hip)
 int vimg_hip_progressive_render(VimgDeviceScene* s, VimgProgressive* a, uint32_t samples, void* d_out, void* stream,
                                 VimgRenderStats* stats) {
-  if (!s || !a) return fail(VIMG_E_INVALID, "progressive: null scene or accumulator");
-  if (a->scene != s) return fail(VIMG_E_INVALID, "progressive: the accumulator belongs to another scene");
-  if (a->generation != s->generation)
-    return fail(VIMG_E_INVALID, "progressive: the scene changed (geometry or camera) since the accumulator's records "
-                                "were made; reset it");
-  if (samples == 0) return fail(VIMG_E_INVALID, "samples must be > 0");
-  if (uint64_t(a->samples) + samples > 0xffffffffull)
-    return fail(VIMG_E_INVALID, "progressive: more than 2^32 - 1 samples per pixel in all (the reference counts them in 32 bits)");
-  VimgRenderParams p = a->params;
-  p.samples = samples;
-  if (int rc = check_params(s, &p)) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
-  if (!d_out) {   // advance only: the means go to a buffer of the accumulator's
-    const size_t floats = (p.tile_world == 1 ? size_t(s->d.res_x) * s->d.res_y : size_t(a->items)) * 3u;
-    if (int rc = a->scratch.grow(std::max<size_t>(floats, 3) * sizeof(float))) return rc;
-    d_out = a->scratch.p;
-  }
-  const ProgLaunch pl{a->samples, a->rec[a->cur].p, a->rec[a->cur ^ 1].p};
-  int rc = enqueue_render(s, &p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1, nullptr,
-                          nullptr, &pl);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  if (int rc2 = check_kernel_error(s)) return rc2;
-  a->samples += samples;
-  a->cur ^= 1;
-  if (stats) return fetch_stats(s, &p, stats);
-  return VIMG_OK;
+  return vimg_hip_progressive_render_masked(s, a, samples, nullptr, d_out, stream, stats);
 }
 
 uint64_t vimg_hip_progressive_samples(const VimgProgressive* a) { return a ? a->samples : 0u; }
 
 int vimg_hip_progressive_reset(VimgProgressive* a) {
   if (!a) return fail(VIMG_E_INVALID, "progressive: null accumulator");
+  // (_state and _error only enqueue, on any stream: they must have read the records before these are wiped)
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemset(a->rec[a->cur].p, 0, a->rec[a->cur].bytes));   // every pixel's count, increments and M2
   a->samples = 0;   // the next increment seeds every pixel again
+  a->uniform = true;
+  a->launches = 0;
   a->generation = a->scene->generation;
   return VIMG_OK;
 }
@@ -378,7 +367,7 @@ int vimg_hip_trace_pixel(VimgDeviceScene* s, const VimgRenderParams* p, int x, i
   if (!out_host || x < 0 || y < 0 || x >= s->d.res_x || y >= s->d.res_y)
     return fail(VIMG_E_INVALID, "trace_pixel: pixel out of range");
   if ((rc = s->frame.grow(3 * sizeof(float)))) return rc;
-  rc = enqueue_render(s, p, s->frame.as<float>(), g_stream, false, false, x, y);
+  rc = enqueue_render(s, p, s->frame.as<float>(), g_stream, false, false, x, y, nullptr, nullptr, nullptr);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(g_stream));
   HIP_TRY(hipMemcpy(out_host, s->frame.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
@@ -413,7 +402,7 @@ int vimg_hip_time_renders(VimgDeviceScene* s, const VimgRenderParams* p, void* d
     if (int rc2 = e.create()) return rc2;
   for (int i = 0; i < steps; ++i) {
     // the counter / queue resets are part of a launch's prologue; the events bracket the kernel only
-    if (int rc2 = enqueue_render(s, p, static_cast<float*>(d_out), g_stream, false, false, -1, -1, ev[2 * i].e, ev[2 * i + 1].e))
+    if (int rc2 = enqueue_render(s, p, static_cast<float*>(d_out), g_stream, false, false, -1, -1, ev[2 * i].e, ev[2 * i + 1].e, nullptr))
       return rc2;
   }
   HIP_TRY(hipStreamSynchronize(g_stream));

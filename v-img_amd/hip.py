@@ -437,28 +437,153 @@ class Progressive:
 
     @property
     def samples(self):
-        """Samples per pixel so far."""
+        """Samples per pixel so far (after masked increments: the largest count of any pixel)."""
         return int(self._lib.vimg_hip_progressive_samples(self._handle()))
 
-    def render(self, samples, out=None, stats=False, stream=None):
+    @property
+    def launches(self):
+        """Render launches of the successful increments since creation or the last reset."""
+        return int(self._lib.vimg_hip_progressive_launches(self._handle()))
+
+    @property
+    def pixel_shape(self):
+        """Shape of a per-pixel buffer of this accumulator: (H, W), or (shard_pixels,) when tile_world > 1."""
+        w, ht = self._dev.resolution
+        return (ht, w) if self.params.tile_world == 1 else (self._dev.shard_pixels(self.params),)
+
+    def _new_image(self):
+        import torch
+        if self.params.tile_world == 1:
+            return torch.empty(self.pixel_shape + (3,), dtype=torch.float32, device="cuda")
+        return torch.zeros(self.pixel_shape + (3,), dtype=torch.float32, device="cuda")
+
+    def _device_mask(self, mask):
+        """A uint8 (or bool) per-pixel mask on this process's GPU: a CUDA tensor as it is, a numpy array copied up."""
+        import torch
+        if isinstance(mask, np.ndarray):
+            if mask.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"mask: dtype must be uint8 or bool, not {mask.dtype}")
+            mask = torch.from_numpy(np.ascontiguousarray(mask).view(np.uint8)).to("cuda")
+        elif isinstance(mask, torch.Tensor):
+            if not mask.is_cuda or mask.device.index != torch.cuda.current_device():
+                raise ValueError(f"mask: the tensor must be on the current CUDA device, not {mask.device}")
+            if mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"mask: dtype must be uint8 or bool, not {mask.dtype}")
+            if not mask.is_contiguous():
+                raise ValueError("mask: the tensor must be contiguous")
+        else:
+            raise ValueError(f"mask: expected a torch CUDA tensor or a numpy array, not {type(mask).__name__}")
+        if tuple(mask.shape) != self.pixel_shape:
+            raise ValueError(f"mask: shape must be {self.pixel_shape}, not {tuple(mask.shape)}")
+        return mask
+
+    def render(self, samples, out=None, stats=False, stream=None, mask=None):
         """Adds `samples` samples per pixel and returns the running mean in ``DeviceScene.render``'s shapes
         ([H, W, 3], or the shard's compact [shard_pixels, 3] when tile_world > 1), with this increment's
-        RenderStats when ``stats``.  ``out=False``: advance only, nothing is written or returned but the stats."""
-        import torch
+        RenderStats when ``stats``.  ``out=False``: advance only, nothing is written or returned but the stats.
+        ``mask`` (uint8 or bool, ``pixel_shape``; CUDA tensor or numpy array): only the pixels whose entry is
+        non-zero get the samples (vimg_hip_progressive_render_masked); every pixel's mean is returned, each
+        bit for bit ``DeviceScene.render`` at that pixel's own count."""
         h = self._handle()
-        w, ht = self._dev.resolution
         if out is None:
-            if self.params.tile_world == 1:
-                out = torch.empty((ht, w, 3), dtype=torch.float32, device="cuda")
-            else:
-                out = torch.zeros((self._dev.shard_pixels(self.params), 3), dtype=torch.float32, device="cuda")
+            out = self._new_image()
         ptr = None if out is False else C.c_void_p(out.data_ptr())
         st = abi.RenderStats()
+        m = None if mask is None else self._device_mask(mask)
         with _Ordered(stream) as sp:
-            _check(self._lib.vimg_hip_progressive_render(self._dev._h, h, int(samples), ptr, sp,
-                                                         C.byref(st) if stats else None))
+            _check(self._lib.vimg_hip_progressive_render_masked(self._dev._h, h, int(samples),
+                                                                None if m is None else C.c_void_p(m.data_ptr()), ptr, sp,
+                                                                C.byref(st) if stats else None))
         img = None if out is False else out
         return (img, st) if stats else img
+
+    def state(self, stream=None):
+        """The per-pixel records (vimg_hip_progressive_state) as CUDA tensors in ``pixel_shape``: a dict with
+        ``sum`` [.., 3] float32 (running sums), ``count`` int64 N, ``batches`` int64 K (increments the pixel
+        took part in; both are uint32 in the library, widened here because torch has no such type) and ``m2``
+        float32."""
+        import torch
+        h = self._handle()
+        shp = self.pixel_shape
+        t = dict(sum=torch.zeros(shp + (3,), dtype=torch.float32, device="cuda"),
+                 count=torch.zeros(shp, dtype=torch.int32, device="cuda"),
+                 batches=torch.zeros(shp, dtype=torch.int32, device="cuda"),
+                 m2=torch.zeros(shp, dtype=torch.float32, device="cuda"))
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_progressive_state(h, *(C.c_void_p(t[k].data_ptr()) for k in ("sum", "count", "batches", "m2")), sp))
+        for k in ("count", "batches"):
+            t[k] = t[k].to(torch.int64) & 0xFFFFFFFF
+        return t
+
+    def counts(self, stream=None):
+        """Samples each pixel has had: int64 CUDA tensor in ``pixel_shape`` (uint32 in the library)."""
+        import torch
+        h = self._handle()
+        n = torch.zeros(self.pixel_shape, dtype=torch.int32, device="cuda")
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_progressive_state(h, None, C.c_void_p(n.data_ptr()), None, None, sp))
+        return n.to(torch.int64) & 0xFFFFFFFF
+
+    def error(self, stream=None):
+        """Estimated relative standard error of each pixel's mean luminance (vimg_hip_progressive_error): float32
+        CUDA tensor in ``pixel_shape``, +inf for pixels that took part in fewer than two increments."""
+        import torch
+        h = self._handle()
+        e = torch.zeros(self.pixel_shape, dtype=torch.float32, device="cuda")
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_progressive_error(h, C.c_void_p(e.data_ptr()), sp))
+        return e
+
+    def select(self, target, max_samples, out=None, stream=None):
+        """(mask, active): the uint8 mask of the pixels that still need samples - error above ``target`` and count
+        below ``max_samples``, or fewer than two increments so far - and how many there are
+        (vimg_hip_progressive_select)."""
+        import torch
+        h = self._handle()
+        if out is None:
+            out = torch.zeros(self.pixel_shape, dtype=torch.uint8, device="cuda")
+        else:
+            out = self._device_mask(out)
+        n = abi.u32(0)
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_progressive_select(h, float(target), int(max_samples), C.c_void_p(out.data_ptr()), sp,
+                                                         C.byref(n)))
+        return out, int(n.value)
+
+    def render_adaptive(self, target, step, max_samples, min_samples=None, out=None, stream=None, progress=None):
+        """Samples until every pixel's error is at most ``target`` or its count is ``max_samples``: unmasked
+        increments of ``step`` up to ``min_samples`` (default 2 * step), then select -> masked increment of
+        ``step`` until no pixel is active.  A pixel that drops out stays out, so the active pixels all stand at
+        one count and every step is one launch.  ``max_samples`` and ``min_samples`` must be multiples of
+        ``step``, min_samples >= 2 * step (the error needs two increments).  Returns the image; ``counts()``
+        tells what each pixel got.  ``progress(samples, active)`` is called after every step."""
+        step, max_samples = int(step), int(max_samples)
+        min_samples = 2 * step if min_samples is None else int(min_samples)
+        if step <= 0 or min_samples < 2 * step or min_samples % step or max_samples % step or max_samples < min_samples:
+            raise ValueError("render_adaptive: step > 0, min_samples and max_samples multiples of step, "
+                             "2 * step <= min_samples <= max_samples")
+        if not target >= 0:
+            raise ValueError("render_adaptive: target must be >= 0")
+        if out is None:
+            out = self._new_image()
+        wrote = False
+        while self.samples < min_samples:
+            self.render(step, out=out, stream=stream)
+            wrote = True
+            if progress:
+                progress(self.samples, int(np.prod(self.pixel_shape)))
+        mask = None
+        while True:
+            mask, active = self.select(target, max_samples, out=mask, stream=stream)
+            if active == 0:
+                break
+            self.render(step, out=out, stream=stream, mask=mask)
+            wrote = True
+            if progress:
+                progress(self.samples, active)
+        if not wrote:     # nothing left to do: the all-zero mask renders nothing and writes every pixel's mean
+            self.render(step, out=out, stream=stream, mask=mask)
+        return out
 
     def reset(self, stream=None):
         """Back to 0 samples: the next increment seeds every pixel again."""
