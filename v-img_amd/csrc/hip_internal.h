@@ -30,6 +30,7 @@ struct VimgDeviceScene {
   VimgHipOptions opt{};        // the caller's options (VIMG_OPT_AUTO where the policy decides)
   int waves_per_simd = 2;      // LANE register budget by policy (scene size)
   bool too_wide = false;       // resolution beyond the 16-bit pixel coordinates of the slot records
+  bool force_general = false;  // VIMG_HIP_PLAIN=0 at upload: never a PLAIN build of render_cu_kernel (tests, A/B runs)
   uint32_t num_cus = 0;
   uint32_t num_leaf_prims = 0;   // records in d.leaf_prims (= primitives of the scene)
   // scratch owned by the scene; the last four grow to what a launch asks for and never shrink
@@ -140,9 +141,11 @@ RenderArgs base_args(const VimgDeviceScene* s, const VimgRenderParams* p, int sx
 uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint64_t items, uint64_t in_flight,
                       double per_gen, double most, RenderArgs* a);
 // the kernel the policy sizes a launch for, and the build of it that runs (render_cu_kernel: the statistics
-// build for `stats`, the early-ray build for cu_flex bit 5)
+// build for `stats`, the early-ray build for cu_flex bit 5, a PLAIN build where plain_launch_serves says so)
 const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c);
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
+// whether the launch, as its arguments stand, runs a PLAIN build (plain_build.h)
+bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
 
 }  // namespace vimg
 #pragma GCC visibility pop

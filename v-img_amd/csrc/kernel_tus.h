@@ -13,5 +13,8 @@ RenderKernel vimg_lane_kernel(bool tex, int wps);             // render_kernel<T
 CuKernel vimg_cu_kernel(bool tex, bool deep, int nw);         // render_cu_kernel<TEX, DEEP, 16, 4, false, 0>
 CuKernel vimg_cu_kernel_early(bool tex, bool deep, int nw);   // ... <..., false, 1>: rays queued as soon as they are known
 CuKernel vimg_cu_kernel_diag(bool tex, bool deep, int nw);    // ... <..., true, 2>: statistics launches
+// the PLAIN builds (plain_build.h: launch-constant options compiled in) of the two untextured builds for trees in LDS
+CuKernel vimg_cu_kernel_plain();                              // render_cu_kernel<false, false, 16, 4, false, 0, PLAIN_FOLD>
+CuKernel vimg_cu_kernel_plain_early();                        // ... <..., false, 1, PLAIN_FOLD>
 
 }  // namespace vimg

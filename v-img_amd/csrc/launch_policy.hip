@@ -58,7 +58,8 @@ uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint6
 
 namespace {
 
-CuKernel pick_cu_kernel(const VimgDeviceScene* s, bool deep, int nw, bool diag = false, bool early = false) {
+CuKernel pick_cu_kernel(const VimgDeviceScene* s, bool deep, int nw, bool diag = false, bool early = false, bool plain = false) {
+  if (plain) return early ? vimg_cu_kernel_plain_early() : vimg_cu_kernel_plain();
   return diag ? vimg_cu_kernel_diag(s->textured, deep, nw)
               : (early ? vimg_cu_kernel_early(s->textured, deep, nw) : vimg_cu_kernel(s->textured, deep, nw));
 }
@@ -165,7 +166,9 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   magic_div(2u * slots, &a.cu_magic_w, &a.cu_shift_w);
   c.lds_bytes = node_bytes + stack_bytes + cu_pool_bytes(slots, nw) + leaf_bytes;
   int per_cu = 0;
-  hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of(s, c), int(nw * 64u), c.lds_bytes);
+  // (asked of the build that will run, as far as the policy knows the launch: an item list or statistics come later
+  // and take the general or the statistics build, of the same workgroup shape)
+  hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, launched_kernel_of(s, c, false), int(nw * 64u), c.lds_bytes);
   if (oe != hipSuccess || per_cu < 1) per_cu = 1;
   per_cu = std::min<int>(per_cu, int(16u / nw));
   const uint64_t need_blocks = (items + slots - 1) / slots;
@@ -194,9 +197,16 @@ const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
   return reinterpret_cast<const void*>(vimg_lane_kernel(s->textured, c.wps));
 }
 
+// The one place that decides between a PLAIN build and the general one: the launch as its arguments stand
+// (enqueue_render asks after it has set the item list and the statistics flag) against plain_build.h's list.
+bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
+  return plain_build_serves(plain_launch_of(c.sched == VIMG_SCHED_CU, s->textured, c.deep, c.cu_waves, stats, s->force_general, c.args));
+}
+
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
   if (c.sched != VIMG_SCHED_CU) return kernel_of(s, c);
-  return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves, stats, (c.args.cu_flex & 32u) != 0u));
+  return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves, stats, (c.args.cu_flex & 32u) != 0u,
+                                                      plain_launch_serves(s, c, stats)));
 }
 
 LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
@@ -252,6 +262,10 @@ const char* vimg_hip_launch_kernel(const VimgDeviceScene* s, const VimgRenderPar
                                        {"render_cu_kernel<true>", "render_cu_kernel<true,deep>"}};
   if (p->tile_world == 0 || p->tile_rank >= p->tile_world) return "";
   const LaunchCfg c = make_launch(s, p, -1, -1);
+  // The build whole frames are timed on keeps the name it has always had: that is a PLAIN build now (plain_build.h).
+  // Where the general build of the same scene class runs instead - another integrator, other options, the override
+  // VIMG_HIP_PLAIN=0 - the name says so.  (Builds for textures or trees in global memory have no PLAIN counterpart.)
+  if (c.sched == VIMG_SCHED_CU && !s->textured && !c.deep && !plain_launch_serves(s, c, false)) return "render_cu_kernel<false,general>";
   if (c.sched == VIMG_SCHED_CU) return cu_names[s->textured ? 1 : 0][c.deep ? 1 : 0];
   return lane_names[s->textured ? 1 : 0][c.wps >= 3 ? 1 : 0];
 }

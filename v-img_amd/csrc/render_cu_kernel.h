@@ -43,6 +43,7 @@
 #pragma once
 #include <type_traits>
 
+#include "plain_build.h"
 #include "render_kernels.h"
 
 namespace vimg {
@@ -142,6 +143,28 @@ VD uint32_t lds_load(VIMG_LDS uint32_t* p) { return __hip_atomic_load(p, __ATOMI
 VD int32_t lds_load(VIMG_LDS int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 VD uint32_t cu_uni(uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); }
 
+// Launch-constant options: the constant in a build whose PLAIN mask folds the option, else the argument
+// (plain_build.h has the list and the host's predicate).  The stage bodies read the options through these only.
+static_assert(PLAIN_INTEGRATOR_MIS == uint32_t(VIMG_INTEGRATOR_MIS), "plain_build.h");
+template <uint32_t PLAIN> VD uint32_t opt_integrator(const RenderArgs& A) {
+  if constexpr (PLAIN & PF_INTEGRATOR) return uint32_t(VIMG_INTEGRATOR_MIS); else return A.integrator;
+}
+template <uint32_t PLAIN> VD uint32_t opt_classes(const RenderArgs& A) {
+  if constexpr (PLAIN & PF_CLASSES) return 3u; else return A.pool_classes;
+}
+template <uint32_t PLAIN> VD bool opt_leaf_in_lds(const RenderArgs& A) {
+  if constexpr (PLAIN & PF_LEAF_LDS) return true; else return A.lds_leaf != 0u;
+}
+template <uint32_t PLAIN> VD bool opt_single(const RenderArgs& A) {
+  if constexpr (PLAIN & PF_SINGLE) return false; else return A.single_x >= 0;
+}
+template <uint32_t PLAIN> VD bool opt_has_items(const RenderArgs& A) {
+  if constexpr (PLAIN & PF_ITEMS) return false; else return A.item_list != nullptr;
+}
+template <uint32_t PLAIN> VD uint32_t opt_flex(const RenderArgs& A) {   // (without the early bit: EARLY is a parameter of its own)
+  if constexpr (PLAIN & PF_FLEX) return PLAIN_FLEX_DEFAULT; else return A.cu_flex;
+}
+
 
 // Kernel arguments: ONE struct by value, read through a pointer to the kernel-argument segment that
 // the optimiser cannot see through (cu_kargs: an empty asm on the address).  Every stage fetches
@@ -176,12 +199,13 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] const bool full_stats = DIAG && A.full_stats != 0;   /* (the DIAG build serves statistics launches) */ \
   [[maybe_unused]] const uint32_t stat_inc = full_stats ? 1u : 0u;                                                      \
   [[maybe_unused]] const uint32_t W = static_cast<uint32_t>(g.res_x), H = static_cast<uint32_t>(g.res_y);               \
-  [[maybe_unused]] const bool single = A.single_x >= 0;                                                                 \
-  [[maybe_unused]] const uint32_t total_items = single ? 1u : (A.item_list ? A.item_count : A.num_local_tiles * 64u);  \
+  [[maybe_unused]] const bool single = opt_single<PLAIN>(A);                                                            \
+  [[maybe_unused]] const uint32_t total_items =                                                                         \
+      single ? 1u : (opt_has_items<PLAIN>(A) ? A.item_count : A.num_local_tiles * 64u);                                 \
   [[maybe_unused]] const uint32_t n_seg = A.pool_segments, seg_len = A.pool_seg_len;                                    \
   [[maybe_unused]] const uint32_t total_claims = total_items * n_seg;                                                   \
   [[maybe_unused]] constexpr uint32_t roulette_threshold = 5;                                                           \
-  [[maybe_unused]] const bool material_mode = (A.integrator == VIMG_INTEGRATOR_MATERIAL);                               \
+  [[maybe_unused]] const bool material_mode = (opt_integrator<PLAIN>(A) == VIMG_INTEGRATOR_MATERIAL);                   \
   [[maybe_unused]] const uint32_t P = A.pool_slots;                                                                     \
   [[maybe_unused]] const bool can_walk = wave < A.cu_walkers;                                                           \
   const uint32_t stack_rows_ = cu_stack_rows_of(A.stack_entries, A.stack_lds);                                          \
@@ -209,7 +233,7 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] auto ring_at = [&](uint32_t q, uint32_t t) -> VIMG_LDS uint16_t* {                                   \
     return q >= CQ_WALK ? ring_w + mod_w(t) : ring_v + q * P + mod_v(t);                                                \
   };                                                                                                                    \
-  [[maybe_unused]] const bool leaf_in_lds = A.lds_leaf != 0u;                                                           \
+  [[maybe_unused]] const bool leaf_in_lds = opt_leaf_in_lds<PLAIN>(A);                                                  \
   [[maybe_unused]] const uint32_t box_min = A.pool_boxmin;                                                              \
   /* cold records of the workgroup's slots in global memory: [slot][4] main lines (throughput, result, NEE term, RNG),  \
      then the accumulator plane, then the cone plane (textured build) */                                                \
@@ -248,12 +272,12 @@ VD CuKPtr cu_kargs() {
      ended), else the material class of the vertex (leaf record); lanes 0..3 reserve for the four rings in one add */  \
   [[maybe_unused]] auto hand_to_vertex = [&](bool complete, uint32_t nw, uint32_t slot_) {                              \
     uint32_t cls_ = 0;                                                                                                  \
-    if (complete && (nw & CF_FOUND) && !(nw & CF_KILL_R) && A.integrator >= VIMG_INTEGRATOR_MATERIAL) {                 \
+    if (complete && (nw & CF_FOUND) && !(nw & CF_KILL_R) && opt_integrator<PLAIN>(A) >= VIMG_INTEGRATOR_MATERIAL) {     \
       cls_ = (nw >> CF_CLS_SHIFT) & 3u;                                                                                 \
       if (cls_ == 0 && material_mode) cls_ = 3; /* material_integrator shades emitters too */                           \
       if (cls_ != 0) {                                                                                                  \
-        if (A.pool_classes == 1) cls_ = 1;                                                                              \
-        else if (A.pool_classes == 2) cls_ = (cls_ == 2) ? 2u : 1u;                                                     \
+        if (opt_classes<PLAIN>(A) == 1) cls_ = 1;                                                                       \
+        else if (opt_classes<PLAIN>(A) == 2) cls_ = (cls_ == 2) ? 2u : 1u;                                              \
       }                                                                                                                 \
     }                                                                                                                   \
     const unsigned long long m0_ = __ballot(complete && cls_ == 0), m1_ = __ballot(complete && cls_ == 1),              \
@@ -332,7 +356,7 @@ VD CuKPtr cu_kargs() {
 // ======================================================================== one vertex batch
 // (FIN: the finisher queue, MTC: material the shading
 // is specialised for, -1 = any).  `n` slots; lane i < n holds its slot id in `slot`.
-template <bool TEX, int NW, bool DIAG, int EARLY, bool FIN, int MTC>
+template <bool TEX, int NW, bool DIAG, int EARLY, bool FIN, int MTC, uint32_t PLAIN>
 VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan, uint32_t& n_dead) {
   const CuKPtr K = cu_kargs();
   CU_STAGE_LOCALS(K);
@@ -345,7 +369,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
   // four cycles however few lanes are on, so on a frame short of pixels (where the last pixels' chains
   // of Principled vertices are the frame time) this takes a fifth off the longest stage.
   constexpr bool CAN_SPLIT = !FIN && MTC != int(VIMG_MAT_LAMBERTIAN);
-  const bool split = CAN_SPLIT && n <= 32u && !(A.cu_flex & 16u);
+  const bool split = CAN_SPLIT && n <= 32u && !(opt_flex<PLAIN>(A) & 16u);
   const bool mirror = split && lane >= 32u;
   if (split) slot = static_cast<uint32_t>(__shfl(static_cast<int>(slot), static_cast<int>(lane & 31u)));
   const bool on = (split ? (lane & 31u) : lane) < n;
@@ -434,10 +458,10 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         } else {
           at_vertex = true;
         }
-      } else if (A.integrator != VIMG_INTEGRATOR_MIS) {
+      } else if (opt_integrator<PLAIN>(A) != VIMG_INTEGRATOR_MIS) {
         // shading_normal_integrator / geometric_normal_integrator
         if (hit_any) {
-          f3 nn = (A.integrator == VIMG_INTEGRATOR_G_NORMAL) ? hit.ng : hit.ns;
+          f3 nn = (opt_integrator<PLAIN>(A) == VIMG_INTEGRATOR_G_NORMAL) ? hit.ng : hit.ns;
           result = (nn + 1.0f) / 2.0f;
         } else {
           f3 unit_dir = normalize(ray_d);
@@ -790,7 +814,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         } else {
           const uint32_t seg = claim / total_items;
           item = claim - seg * total_items;
-          if (A.item_list) item = A.item_list[item];   // a masked launch: the claim names an entry of its list
+          if (opt_has_items<PLAIN>(A)) item = A.item_list[item];   // a masked launch: the claim names an entry of its list
           bool valid = true;
           if (single) {
             px = static_cast<uint32_t>(A.single_x), py = static_cast<uint32_t>(A.single_y);
@@ -926,7 +950,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
 // ======================================================================== one walk session
 // Refill idle lanes from the walk ring, step the rays, hand finished ones over; ends when the wave
 // holds no ray and the ring is empty.
-template <bool TEX, bool DEEP, int NW, bool DIAG>
+template <bool TEX, bool DEEP, int NW, bool DIAG, uint32_t PLAIN>
 VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
   const CuKPtr K = cu_kargs();
   CU_STAGE_LOCALS(K);
@@ -1000,7 +1024,7 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
         }
         w_inv = f3{1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z};
         w_exact = (ray.d.x == 0.f) || (ray.d.y == 0.f) || (ray.d.z == 0.f);
-        rc = tri_ray_const(ray.d);
+        rc = tri_ray_const(ray.d, w_inv);
         w_dir_len2 = dot(ray.d, ray.d);
         const float root = slab(load3k(g.root_min), load3k(g.root_max), ray.o, w_inv, ray.min_t, ray.max_t);
         cur = is_inf(root) ? REF_DONE : g.root_ref;
@@ -1182,7 +1206,8 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
 // EARLY: 1 = vertex stages queue their rays as soon as they are known (cu_flex bit 5, by policy on frames
 // short of pixels and on trees in global memory), 0 = at the end of the stage, 2 = by the bit at run time
 // (the statistics build).
-template <bool TEX, bool DEEP, int NW, int WPS, bool DIAG, int EARLY>
+// PLAIN: mask of the launch-constant options this build takes as constants (plain_build.h; 0 = the general build).
+template <bool TEX, bool DEEP, int NW, int WPS, bool DIAG, int EARLY, uint32_t PLAIN = 0u>
 __global__ void __launch_bounds__(NW * 64, WPS)
 render_cu_kernel(const CuKArgs ka) {
   {
@@ -1244,16 +1269,16 @@ render_cu_kernel(const CuKArgs ka) {
       lap(5);
       skip_fin = false, polls = 0, idle_since = 0;
       if (full_stats) iter_wave++;
-      if (A.cu_flex & 4u) __builtin_amdgcn_s_setprio(1);
-      cu_walk<TEX, DEEP, NW, DIAG>(n_closest, n_shadow);
-      if (A.cu_flex & 4u) __builtin_amdgcn_s_setprio(0);
+      if (opt_flex<PLAIN>(A) & 4u) __builtin_amdgcn_s_setprio(1);
+      cu_walk<TEX, DEEP, NW, DIAG, PLAIN>(n_closest, n_shadow);
+      if (opt_flex<PLAIN>(A) & 4u) __builtin_amdgcn_s_setprio(0);
       lap(4);
       continue;
     }
     // a vertex batch: a full one at once; a partial one when the walkers are about to run dry (few
     // rays queued) and it is worth a wave's while (pool_starve slots, or this wave has looked in vain
     // a few times).  Walking waves shade only when they hold no ray (here) and A.cu_flex allows it.
-    const bool may_shade = !can_walk || (A.cu_flex & 1u);
+    const bool may_shade = !can_walk || (opt_flex<PLAIN>(A) & 1u);
     const bool run = may_shade && qmax > 0 &&
                      (qmax >= static_cast<int32_t>(A.pool_vbatch) ||
                       (aw < static_cast<int32_t>(A.cu_lowwater) && (qmax >= static_cast<int32_t>(A.pool_starve) || polls >= A.cu_patience)));
@@ -1273,17 +1298,17 @@ render_cu_kernel(const CuKArgs ka) {
         if (lane == 0) wrec->wait_cyc[cls] += w, wrec->wait_n[cls] += n;
       }
       bool all_pending = false;
-      const bool by_class = A.pool_classes == 3u;
-      if (A.cu_flex & 2u) __builtin_amdgcn_s_setprio(1);
+      const bool by_class = opt_classes<PLAIN>(A) == 3u;
+      if (opt_flex<PLAIN>(A) & 2u) __builtin_amdgcn_s_setprio(1);
       if (cls == 0u)
-        cu_vertex<TEX, NW, DIAG, EARLY, true, -1>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, true, -1, PLAIN>(n, e, all_pending, n_nan, n_dead);
       else if (cls == 1u && by_class)
-        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_LAMBERTIAN)>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_LAMBERTIAN), PLAIN>(n, e, all_pending, n_nan, n_dead);
       else if (cls == 2u && by_class)
-        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_PRINCIPLED)>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_PRINCIPLED), PLAIN>(n, e, all_pending, n_nan, n_dead);
       else
-        cu_vertex<TEX, NW, DIAG, EARLY, false, -1>(n, e, all_pending, n_nan, n_dead);
-      if (A.cu_flex & 2u) __builtin_amdgcn_s_setprio(0);
+        cu_vertex<TEX, NW, DIAG, EARLY, false, -1, PLAIN>(n, e, all_pending, n_nan, n_dead);
+      if (opt_flex<PLAIN>(A) & 2u) __builtin_amdgcn_s_setprio(0);
       skip_fin = all_pending;
       if (!all_pending) polls = 0, idle_since = 0;   // (a batch of waiting slots only is not progress: the watchdog keeps its time)
       lap(cls);

@@ -405,14 +405,15 @@ struct TriRayConst {
 VD f3 permute(f3 v, int kz) {
   return kz == 0 ? f3{v.y, v.z, v.x} : (kz == 1 ? f3{v.z, v.x, v.y} : v);
 }
-VD TriRayConst tri_ray_const(f3 dir) {
+// (`inv` is 1 / dir by component, which every caller has for its slab tests: 1 / d.z is one of them)
+VD TriRayConst tri_ray_const(f3 dir, f3 inv) {
   float ax = absf(dir.x), ay = absf(dir.y), az = absf(dir.z);
   int kz = 0;
   float mx = ax;
   if (ay > mx) { kz = 1; mx = ay; }
   if (az > mx) { kz = 2; mx = az; }
   f3 d = permute(dir, kz);
-  return TriRayConst{-d.x / d.z, -d.y / d.z, 1.f / d.z, kz};
+  return TriRayConst{-d.x / d.z, -d.y / d.z, kz == 0 ? inv.x : (kz == 1 ? inv.y : inv.z), kz};
 }
 VD float diff_of_products(float a, float b, float c, float d) {
   float cd = c * d;
@@ -534,7 +535,7 @@ VD bool traverse(const DScene& g, const Lds& L, TravRay& ray, HitRec& rec, Count
   const bool exact_slab = (ray.d.x == 0.f) || (ray.d.y == 0.f) || (ray.d.z == 0.f);
   float root = slab(load3k(g.root_min), load3k(g.root_max), ray.o, inv, ray.min_t, ray.max_t);
   if (is_inf(root)) return false;
-  const TriRayConst rc = tri_ray_const(ray.d);
+  const TriRayConst rc = tri_ray_const(ray.d, inv);
   const float dir_len2 = dot(ray.d, ray.d);
   uint32_t sp = 0;
   uint32_t cur = g.root_ref;

@@ -461,6 +461,7 @@ int resolve_options(VimgDeviceScene* s, const VimgHipOptions* opts) {
   }
   options_from_env(&s->opt);
   if (const char* e = getenv("VIMG_HIP_QUERY_BLOCKS")) s->query_launch = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("VIMG_HIP_PLAIN")) s->force_general = atoi(e) == 0;   // 0: the general build of render_cu_kernel for every launch
   if (s->opt.scheduler != VIMG_OPT_AUTO && (s->opt.scheduler < VIMG_SCHED_LANE || s->opt.scheduler > VIMG_SCHED_CU))
     return fail(VIMG_E_INVALID, "options: unknown scheduler");
   // the one gate: every launch builder relies on a resident scene's scheduler being AUTO, LANE or CU
