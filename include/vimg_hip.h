@@ -94,8 +94,9 @@ int vimg_hip_scene_upload(const VimgScene* scene, VimgDeviceScene** out);
 int vimg_hip_scene_upload_opts(const VimgScene* scene, const VimgHipOptions* opts, VimgDeviceScene** out);
 int vimg_hip_scene_free(VimgDeviceScene* scene);
 
-/* Changing a resident scene without a new upload: same primitives, materials, textures,
- * lights and resolution; new positions and a new camera (and, below, a new tree over them).
+/* Changing a resident scene without a new upload: the same primitive set, texture sizes
+ * and resolution; new positions, materials, texture contents, emitters, background and camera (and, below, a new
+ * tree).  vimg_hip_scene_update_geometry is the scene's update entry point: one call carries any of the changes.
  *  _update_geometry : new positions, NULL = unchanged.  DEVICE pointers to float32, read on `stream`:
  *      vertices num_vertices x 3 (the whole table, VimgScene order), normals num_vertices x 3 (rows of
  *      meshes without normals are ignored), spheres num_spheres x 4 (centre xyz, radius; the material
@@ -105,18 +106,52 @@ int vimg_hip_scene_free(VimgDeviceScene* scene);
  *      builders' fold order; then blocks until the scene is consistent (the inputs may be reused at once).
  *      A launch afterwards reads exactly what an upload of the host scene with the same positions and a
  *      vimg_host_refit_bvh tree reads.  Values are taken as they come (no finiteness check).
+ *    The fields behind `spheres` (since the material update; struct_size tells the library whether the caller
+ *    has them) change what the upload takes from the material, texture, light and background tables; NULL / 0 =
+ *    unchanged, and a call with all of them zero is the geometry update above.  Applied after the positions, in
+ *    the order images, tables, lights; afterwards a launch reads exactly what an upload of the host scene edited
+ *    the same way (vimg_host_set_materials, _set_texture_colors, _set_texture_image, _set_background) reads,
+ *    vimg_hip_scene_bytes included:
+ *      materials  : the whole table, as many records as uploaded; any field may change, the type included.  The
+ *                   upload's checks apply.  material_flags, the class of every leaf slot, the emission of every
+ *                   emitter (zero when its primitive's material is no DiffuseLight any more: it is still sampled)
+ *                   and the TEX / non-TEX kernel family are derived again.
+ *      textures   : the whole record table.  A record keeps its type; an IMAGE record keeps everything (its size,
+ *                   levels, offsets and wrap modes); CONST may change col_a, CHECKER both colours and cell counts.
+ *      lights     : with set_lights != 0 a new emitter list of num_lights entries (0: a scene without emitters,
+ *                   which, like an upload without emitters, the mis integrator refuses and the others render);
+ *                   prim < num_prims, at most one BACKGROUND entry.  Baked by a kernel from the resident records.
+ *      background : keeps type, env_tex and both CDF offsets; col, radiance_scale and the two matrices may change.
+ *      images     : new level-0 texels of IMAGE textures, from DEVICE memory; the mip chain is filtered again in
+ *                   place, and for the background's env_tex the sampling CDFs too, device to device.
  *  _set_camera : the camera values the upload derives (pixel size, primary-ray cone, lens).  A different
  *      res_x / res_y is VIMG_E_INVALID.
- * Both change the scene's generation: a VimgProgressive whose records were made before refuses its next
- * increment (VIMG_E_INVALID) until vimg_hip_progressive_reset.  Argument errors (NULL, struct_size too
- * small) return VIMG_E_INVALID and leave the scene as it was.  Launches on the scene stay ordered on one
- * stream, as for every launch of a scene. */
+ * Both change the scene's generation, once per successful call: a VimgProgressive whose records were made before
+ * refuses its next increment (VIMG_E_INVALID) until vimg_hip_progressive_reset.  Argument errors (NULL, a
+ * struct_size that is neither 32 - the layout before the material update - nor at least sizeof(VimgGeometryUpdate),
+ * a table the upload would refuse, a record that changes what must stay) return VIMG_E_INVALID before anything is
+ * enqueued or written and leave the scene and its generation as they were.  Launches on the scene stay ordered on
+ * one stream, as for every launch of a scene. */
+typedef struct VimgTextureImage {
+  uint32_t texture;         /* index of a resident IMAGE texture */
+  uint32_t reserved;
+  const void* level0;       /* DEVICE pointer: width * height float32 rgb triples, row 0 = top; 4-byte aligned */
+} VimgTextureImage;
 typedef struct VimgGeometryUpdate {
-  uint32_t struct_size;     /* sizeof(VimgGeometryUpdate) */
+  uint32_t struct_size;     /* sizeof(VimgGeometryUpdate), or 32: the first four fields only */
   const void* vertices;     /* num_vertices x 3, or NULL */
   const void* normals;      /* num_vertices x 3, or NULL */
   const void* spheres;      /* num_spheres x 4, or NULL */
+  /* since the material update; HOST pointers unless said otherwise; NULL / 0 = unchanged */
+  const VimgMaterial* materials;      /* the whole table, num_materials records as uploaded */
+  const VimgTexture* textures;        /* the whole record table, num_textures records */
+  const VimgLight* lights;            /* a new emitter list of num_lights entries, read when set_lights != 0 */
+  uint32_t num_lights, set_lights;    /* (set_lights != 0 with num_lights == 0: a scene without emitters) */
+  const VimgBackground* background;
+  const VimgTextureImage* images;     /* host array of num_images entries; each level0 is a DEVICE pointer */
+  uint32_t num_images, reserved;
 } VimgGeometryUpdate;
+#define VIMG_GEOMETRY_UPDATE_V1_SIZE 32u
 int vimg_hip_scene_update_geometry(VimgDeviceScene* scene, const VimgGeometryUpdate* update, void* stream);
 int vimg_hip_scene_set_camera(VimgDeviceScene* scene, const VimgCamera* camera);
 

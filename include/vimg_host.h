@@ -108,6 +108,25 @@ int vimg_host_set_vertices(VimgHostScene* s, const float* xyz, const float* norm
 int vimg_host_set_spheres(VimgHostScene* s, const float* centre_radius);
 int vimg_host_refit_bvh(VimgHostScene* s);
 
+/* ---- new materials, texture contents and background on the same primitives: the host counterparts of the
+ * material fields of vimg_hip_scene_update_geometry.  A scene edited with these and then uploaded is what a device
+ * scene updated with the same tables holds.  None of them touches the tree (positions are unchanged).
+ *  set_materials      : the whole table, as many records as the scene has; add_material's checks apply.  The emitter
+ *                       list is rebuilt as the construction calls would have built it had the materials been these
+ *                       from the start: surfaces in primitive order, an emissive mesh's triangles last to first,
+ *                       spheres where they stand, a background entry where set_background_* appended it.
+ *  set_texture_colors : CONST: col_a (col_b, w, h ignored); CHECKER: both colours and the cell counts.
+ *  set_texture_image  : a new level 0 of the same size for an IMAGE texture (w*h rgb floats, row 0 = top); the mip
+ *                       chain - and the sampling CDFs when the texture is the env map - are rebuilt where they are,
+ *                       through the installed precompute builders like add_texture_image / set_background_envmap.
+ *  set_background     : colour, matrices (NULL = keep) and radiance scale of the background as it stands: its
+ *                       type, env_tex and membership of the emitter list stay. */
+int vimg_host_set_materials(VimgHostScene* s, const VimgMaterial* materials);
+int vimg_host_set_texture_colors(VimgHostScene* s, uint32_t tex, const float col_a[3], const float col_b[3], uint32_t w, uint32_t h);
+int vimg_host_set_texture_image(VimgHostScene* s, uint32_t tex, const float* rgb);
+int vimg_host_set_background(VimgHostScene* s, const float col[3], const float world_to_env[16], const float env_to_world[16],
+                             float radiance_scale);
+
 /* View valid until the scene is modified or freed.  NULL before vimg_host_build_bvh. */
 const VimgScene* vimg_host_scene_view(const VimgHostScene* s);
 void vimg_host_default_params(const VimgHostScene* s, VimgRenderParams* out);

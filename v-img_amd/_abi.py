@@ -123,9 +123,28 @@ class RenderStats(C.Structure):
         return int(self.closest_rays) + int(self.shadow_rays)
 
 
-class GeometryUpdate(C.Structure):
-    """VimgGeometryUpdate (include/vimg_hip.h): device pointers to float32 tables, NULL = unchanged."""
+class TextureImage(C.Structure):
+    """VimgTextureImage (include/vimg_hip.h): new level-0 texels (a DEVICE pointer) for one resident IMAGE texture."""
+    _fields_ = [("texture", u32), ("reserved", u32), ("level0", C.c_void_p)]
+
+
+class GeometryUpdateV1(C.Structure):
+    """The first 32 bytes of VimgGeometryUpdate, the whole struct before the material update: what an older caller
+    passes (struct_size 32)."""
     _fields_ = [("struct_size", u32), ("vertices", C.c_void_p), ("normals", C.c_void_p), ("spheres", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GeometryUpdateV1)
+
+
+class GeometryUpdate(C.Structure):
+    """VimgGeometryUpdate (include/vimg_hip.h): device pointers to float32 tables, then host pointers to the new
+    material, texture, light and background tables and the image list; NULL / 0 = unchanged."""
+    _fields_ = GeometryUpdateV1._fields_ + [
+        ("materials", C.POINTER(Material)), ("textures", C.POINTER(Texture)), ("lights", C.POINTER(Light)),
+        ("num_lights", u32), ("set_lights", u32), ("background", C.POINTER(Background)),
+        ("images", C.POINTER(TextureImage)), ("num_images", u32), ("reserved", u32)]
 
     def __init__(self, **kw):
         super().__init__(**kw)
@@ -226,6 +245,10 @@ HOST_SYMBOLS = {
     "vimg_host_set_vertices": (C.c_int, [C.c_void_p, Pf32, Pf32]),
     "vimg_host_set_spheres": (C.c_int, [C.c_void_p, Pf32]),
     "vimg_host_refit_bvh": (C.c_int, [C.c_void_p]),
+    "vimg_host_set_materials": (C.c_int, [C.c_void_p, C.POINTER(Material)]),
+    "vimg_host_set_texture_colors": (C.c_int, [C.c_void_p, u32, Pf32, Pf32, u32, u32]),
+    "vimg_host_set_texture_image": (C.c_int, [C.c_void_p, u32, Pf32]),
+    "vimg_host_set_background": (C.c_int, [C.c_void_p, Pf32, Pf32, Pf32, f32]),
     "vimg_host_scene_view": (PScene, [C.c_void_p]),
     "vimg_host_default_params": (None, [C.c_void_p, PParams]),
     "vimg_host_tonemap_to_rgb8": (C.c_int, [Pf32, C.c_int, C.c_int, C.c_int,

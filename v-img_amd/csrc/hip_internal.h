@@ -4,6 +4,7 @@
 //   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel
 //   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
 //   scene_rebuild.hip  a new tree for a resident scene, its cost       bvh_build.hip    the GPU builders and their cores
+//   scene_relight.hip  new materials, texture contents, emitters and background of a resident scene
 //   device_mem.h       fail / HIP_TRY, and DevBuf / DevEvent: the one owner type of device memory, and of events
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +50,14 @@ struct VimgDeviceScene {
   uint32_t n_internal = 0;       // DNode records of the tree; the n_chain chain records follow them
   uint32_t n_chain = 0;
   std::vector<uint32_t> level_begin;        // breadth-first levels of the internal nodes: [level_begin[k], level_begin[k+1])
+  // material updates (scene_relight.hip): host copies of the small tables an update is checked against, and the
+  // places in `tables` of the buffers it writes or swaps
+  std::vector<VimgMaterial> materials;
+  std::vector<VimgTexture> textures;
+  std::vector<VimgLight> lights;
+  uint32_t num_rg_textures = 0;
+  uint64_t num_texels = 0, num_cdf = 0;
+  size_t lights_table = 0, dlights_table = 0;
   // ray queries (vimg_hip_trace_rays, _occluded): the LDS layout and the blocks per CU of each query build, worked
   // out at the first query and again after vimg_hip_scene_rebuild_bvh (which resets query_ready: both depend on
   // max_depth and num_nodes; nothing else changes the tree's shape, and the options never change after upload)
@@ -109,6 +118,42 @@ struct DeviceTree {
   std::vector<uint32_t> level_internal;   // nodes with children on every level that has some, root level first
 };
 int build_tree_device(uint32_t builder /* VIMG_BUILDER_* */, uint32_t n, const float* d_bounds6, DeviceTree* out);
+
+// ---- scene_upload.hip: the upload's checks of the material and the emitter table, shared with the material update
+int validate_materials(const VimgMaterial* materials, uint32_t num_materials, const VimgTexture* textures, uint32_t num_textures,
+                       uint32_t num_rg_textures);
+int validate_lights(const VimgLight* lights, uint32_t num_lights, uint32_t num_prims);
+// whether the tables need the TEX kernels, and Background::is_emissive
+bool tables_textured(const VimgMaterial* materials, uint32_t num_materials, const VimgTexture* textures, const VimgBackground& bg);
+bool background_is_emissive(const VimgBackground& bg);
+
+// ---- scene_relight.hip: the fields of a VimgGeometryUpdate behind `spheres`.  check_ finds every
+// argument error and touches nothing; prepare_ allocates what the call needs (new emitter buffers, the CDF kernels'
+// temporaries) before anything is enqueued; enqueue_ puts copies and kernels on `st`; commit_, after the stream has
+// been synchronised, swaps the new buffers in and takes the host copies.
+struct RelightPlan {
+  bool any = false;                  // the update carries one of the new fields
+  DevBuf new_lights, new_dlights;    // set_lights: built beside the scene's
+  DevBuf sin_elev, lum, row_int, row_tot;   // env-map CDFs: the kernels' temporaries
+  std::vector<float> sin_table;
+};
+int check_relight(const VimgDeviceScene* s, const VimgGeometryUpdate* u);
+int prepare_relight(const VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan);
+int enqueue_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan, hipStream_t st);
+void commit_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan);
+
+// ---- precompute.hip: the launches of the texture pre-pass on device buffers.  level_offset: in texels from
+// `texels`, level 0 filled; the CDFs go where row_cdf (h + 1 floats) and col_cdfs (h x (w + 1)) point
+struct EnvCdfScratch {
+  float* sin_elev;   // h floats: env_sin_table(h), uploaded
+  float* lum;        // w * h
+  float* row_int;    // h
+  float* row_tot;    // 1
+};
+void enqueue_mip_levels(float* texels, const uint64_t* level_offset, uint32_t levels, uint32_t w, uint32_t h, uint32_t wrap_u,
+                        uint32_t wrap_v, hipStream_t st);
+std::vector<float> env_sin_table(uint32_t h);
+void enqueue_env_cdfs(const float* img, uint32_t w, uint32_t h, const EnvCdfScratch& t, float* row_cdf, float* col_cdfs, hipStream_t st);
 
 // ---- vimg_hip.hip: the one path every render takes, shared with progressive_adaptive.hip
 // A progressive launch: p->samples more samples for pixels that have had `base`, their records read from `in`

@@ -44,6 +44,47 @@ int pre_ready() {
 uint32_t pre_grid(size_t n) { return static_cast<uint32_t>(std::min<size_t>((n + 255) / 256, 65536)); }
 }  // namespace
 
+}  // extern "C"
+
+// ---- the launches themselves, on device buffers: the host-buffer entry points below and the image update of a
+// resident scene (scene_relight.hip) both go through these, so both run the same kernels on the same grids
+namespace vimg {
+
+void enqueue_mip_levels(float* texels, const uint64_t* level_offset, uint32_t levels, uint32_t w, uint32_t h, uint32_t wrap_u,
+                        uint32_t wrap_v, hipStream_t st) {
+  uint32_t pw = w, ph = h;
+  for (uint32_t l = 1; l < levels; ++l) {
+    const uint32_t nw = std::max(pw / 2u, 1u), nh = std::max(ph / 2u, 1u);
+    hipLaunchKernelGGL(pre_mip_level_kernel, dim3((nw + 31) / 32, (nh + 7) / 8), dim3(256), 0, st, texels + level_offset[l - 1] * 3, pw, ph,
+                       texels + level_offset[l] * 3, nw, nh, wrap_u, wrap_v);
+    pw = nw, ph = nh;
+  }
+}
+
+std::vector<float> env_sin_table(uint32_t h) {
+  // sin(pi * v) per row, in double as the reference evaluates it (sampling.h:180-181)
+  std::vector<float> sin_elev(h);
+  for (uint32_t y = 0; y < h; ++y) {
+    float v = (static_cast<float>(y) + 0.5f) / static_cast<float>(h);
+    sin_elev[y] = static_cast<float>(std::sin(3.141592653589793238462643383279502884 * v));
+  }
+  return sin_elev;
+}
+
+void enqueue_env_cdfs(const float* img, uint32_t w, uint32_t h, const EnvCdfScratch& t, float* row_cdf, float* col_cdfs, hipStream_t st) {
+  const size_t n = size_t(w) * h;
+  hipLaunchKernelGGL(pre_env_lum_kernel, dim3(pre_grid(n)), dim3(256), 0, st, img, w, h, t.sin_elev, t.lum);
+  // one conditional distribution per image row, then the marginal over the row integrals
+  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(h), dim3(64), 0, st, t.lum, h, w, col_cdfs, t.row_int);
+  hipLaunchKernelGGL(pre_cdf_normalise_kernel, dim3(pre_grid(size_t(h) * (w + 1))), dim3(256), 0, st, col_cdfs, h, w, t.row_int);
+  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(1), dim3(64), 0, st, t.row_int, 1u, h, row_cdf, t.row_tot);
+  hipLaunchKernelGGL(pre_cdf_normalise_kernel, dim3(pre_grid(size_t(h) + 1)), dim3(256), 0, st, row_cdf, 1u, h, t.row_tot);
+}
+
+}  // namespace vimg
+
+extern "C" {
+
 uint64_t vimg_hip_mip_chain_texels(uint32_t w, uint32_t h, uint32_t* num_levels) {
   if (w == 0 || h == 0) {
     if (num_levels) *num_levels = 0;
@@ -73,16 +114,15 @@ int vimg_hip_build_mip_chain(uint32_t w, uint32_t h, const float* level0, uint32
   if (int rc = d.alloc(texels * 3 * sizeof(float))) return rc;
   float* base = d.as<float>();
   HIP_TRY(hipMemcpyAsync(base, level0, size_t(w) * h * 3 * sizeof(float), hipMemcpyHostToDevice, g_stream));
-  uint64_t prev_off = 0;
-  uint32_t pw = w, ph = h;
-  for (uint32_t l = 1; l < levels; ++l) {
-    const uint32_t nw = std::max(pw / 2u, 1u), nh = std::max(ph / 2u, 1u);
-    const uint64_t next_off = prev_off + uint64_t(pw) * ph;
-    hipLaunchKernelGGL(pre_mip_level_kernel, dim3((nw + 31) / 32, (nh + 7) / 8), dim3(256), 0, g_stream,
-                       base + prev_off * 3, pw, ph, base + next_off * 3, nw, nh, wrap_u, wrap_v);
-    prev_off = next_off;
-    pw = nw, ph = nh;
+  uint64_t offsets[VIMG_MAX_MIP_LEVELS] = {0};   // each level behind the one before
+  {
+    uint32_t lw = w, lh = h;
+    for (uint32_t l = 1; l < levels; ++l) {
+      offsets[l] = offsets[l - 1] + uint64_t(lw) * lh;
+      lw = std::max(lw / 2u, 1u), lh = std::max(lh / 2u, 1u);
+    }
   }
+  enqueue_mip_levels(base, offsets, levels, w, h, wrap_u, wrap_v, g_stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_levels, base, texels * 3 * sizeof(float), hipMemcpyDeviceToHost, g_stream));
   HIP_TRY(hipStreamSynchronize(g_stream));
@@ -93,12 +133,7 @@ int vimg_hip_build_env_cdfs(const float* img, uint32_t w, uint32_t h, float* row
   if (!img || !row_cdf || !col_cdfs || w == 0 || h == 0)
     return fail(VIMG_E_INVALID, "build_env_cdfs: bad arguments");
   if (int rc = pre_ready()) return rc;
-  // sin(pi * v) per row, in double as the reference evaluates it (sampling.h:180-181)
-  std::vector<float> sin_elev(h);
-  for (uint32_t y = 0; y < h; ++y) {
-    float v = (static_cast<float>(y) + 0.5f) / static_cast<float>(h);
-    sin_elev[y] = static_cast<float>(std::sin(3.141592653589793238462643383279502884 * v));
-  }
+  const std::vector<float> sin_elev = env_sin_table(h);
   const size_t n = size_t(w) * h;
   DevBuf d_img, d_sin, d_lum, d_cdf, d_rowint, d_rowcdf, d_rowtot;
   if (int rc = d_img.alloc(n * 3 * sizeof(float))) return rc;
@@ -110,17 +145,8 @@ int vimg_hip_build_env_cdfs(const float* img, uint32_t w, uint32_t h, float* row
   if (int rc = d_rowtot.alloc(sizeof(float))) return rc;
   HIP_TRY(hipMemcpyAsync(d_img.p, img, n * 3 * sizeof(float), hipMemcpyHostToDevice, g_stream));
   HIP_TRY(hipMemcpyAsync(d_sin.p, sin_elev.data(), h * sizeof(float), hipMemcpyHostToDevice, g_stream));
-  hipLaunchKernelGGL(pre_env_lum_kernel, dim3(pre_grid(n)), dim3(256), 0, g_stream, d_img.as<float>(), w, h,
-                     d_sin.as<float>(), d_lum.as<float>());
-  // one conditional distribution per image row, then the marginal over the row integrals
-  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(h), dim3(64), 0, g_stream, d_lum.as<float>(), h, w,
-                     d_cdf.as<float>(), d_rowint.as<float>());
-  hipLaunchKernelGGL(pre_cdf_normalise_kernel, dim3(pre_grid(size_t(h) * (w + 1))), dim3(256), 0, g_stream,
-                     d_cdf.as<float>(), h, w, d_rowint.as<float>());
-  hipLaunchKernelGGL(pre_cdf_scan_kernel, dim3(1), dim3(64), 0, g_stream, d_rowint.as<float>(), 1u, h,
-                     d_rowcdf.as<float>(), d_rowtot.as<float>());
-  hipLaunchKernelGGL(pre_cdf_normalise_kernel, dim3(pre_grid(size_t(h) + 1)), dim3(256), 0, g_stream,
-                     d_rowcdf.as<float>(), 1u, h, d_rowtot.as<float>());
+  enqueue_env_cdfs(d_img.as<float>(), w, h, EnvCdfScratch{d_sin.as<float>(), d_lum.as<float>(), d_rowint.as<float>(), d_rowtot.as<float>()},
+                   d_rowcdf.as<float>(), d_cdf.as<float>(), g_stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(col_cdfs, d_cdf.p, size_t(h) * (w + 1) * sizeof(float), hipMemcpyDeviceToHost, g_stream));
   HIP_TRY(hipMemcpyAsync(row_cdf, d_rowcdf.p, (size_t(h) + 1) * sizeof(float), hipMemcpyDeviceToHost, g_stream));

@@ -61,6 +61,51 @@ VHD void bake_light_sphere(const VimgSphere& sp, DLight& L) {
   L.a = v4f{sp.center[0], sp.center[1], sp.center[2], sp.radius};
 }
 
+// ---- what the upload derives from the material table: stated once for the upload (host) and for the
+// material update's kernels (scene_relight.hip)
+// the vertex queue a hit is routed into (DLeafPrim::cls)
+VHD uint32_t bake_material_class(uint32_t type) {
+  return type == VIMG_MAT_DIFFUSE_LIGHT ? 0u : type == VIMG_MAT_LAMBERTIAN ? 1u : type == VIMG_MAT_PRINCIPLED ? 2u : 3u;
+}
+VHD uint32_t bake_material_flags(const VimgMaterial& m, const VimgTexture* textures) {
+  uint32_t f = 0;
+  if (m.type == VIMG_MAT_PRINCIPLED) f |= MATF_NEEDS_FRAME;
+  if (m.tex >= 0 && textures[m.tex].type != VIMG_TEX_CONST) f |= MATF_NEEDS_UV;
+  if (m.mr_tex >= 0 || m.normal_map >= 0) f |= MATF_NEEDS_UV;
+  return f;
+}
+// the material of a primitive (shade: the per-triangle records, which carry the triangle's mesh)
+VHD uint32_t bake_prim_material(const VimgPrim& p, const DTriShade* shade, const VimgMesh* meshes, const VimgSphere* spheres) {
+  return p.type == VIMG_PRIM_TRIANGLE ? meshes[shade[p.index].mesh].material : spheres[p.index].material;
+}
+// one whole DLight: kind, index, the geometric fields and the material's emission (zero when it is no DiffuseLight:
+// Material::emitted of the others)
+VHD DLight bake_light(const VimgLight& l, const VimgPrim* prims, const DTriShade* shade, const float* area_pdf, const VimgMesh* meshes,
+                      const VimgSphere* spheres, const VimgMaterial* materials) {
+  DLight L{};
+  if (l.type == VIMG_LIGHT_BACKGROUND) {
+    L.kind = 0u;
+    return L;
+  }
+  const VimgPrim p = prims[l.prim];
+  L.index = p.index;
+  uint32_t mat;
+  if (p.type == VIMG_PRIM_TRIANGLE) {
+    const VimgMesh& mesh = meshes[shade[p.index].mesh];
+    L.kind = mesh.has_normals ? 2u : 1u;
+    bake_light_tri(shade[p.index], area_pdf[p.index], L);
+    mat = mesh.material;
+  } else {
+    const VimgSphere& sp = spheres[p.index];
+    L.kind = 3u;
+    bake_light_sphere(sp, L);
+    mat = sp.material;
+  }
+  const VimgMaterial& m = materials[mat];
+  if (m.type == VIMG_MAT_DIFFUSE_LIGHT) L.d.x = m.emit[0], L.d.y = m.emit[1], L.d.z = m.emit[2];
+  return L;
+}
+
 // the boxes of a DNode's two children: a = Lmin Lmax.x, b = Lmax.yz Rmin.xy, c = Rmin.z Rmax
 VHD void pack_boxes(DNode& n, const float* lmin, const float* lmax, const float* rmin, const float* rmax) {
   n.a = v4f{lmin[0], lmin[1], lmin[2], lmax[0]};

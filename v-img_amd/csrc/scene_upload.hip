@@ -24,6 +24,55 @@ int upload(VimgDeviceScene* s, DevBuf& b, const T* host, size_t count) {
   return VIMG_OK;
 }
 
+}  // namespace
+
+// the material and the emitter table: checked at upload, and again when an update replaces them
+int vimg::validate_materials(const VimgMaterial* materials, uint32_t num_materials, const VimgTexture* textures, uint32_t num_textures,
+                             uint32_t num_rg_textures) {
+  for (uint32_t i = 0; i < num_materials; ++i) {
+    const VimgMaterial& m = materials[i];
+    if (m.type > VIMG_MAT_PRINCIPLED) return fail(VIMG_E_INVALID, "material: unknown type");
+    auto tex_ok = [&](int32_t t) { return t >= -1 && t < int32_t(num_textures); };
+    if (!tex_ok(m.tex) || !tex_ok(m.normal_map) || m.mr_tex < -1 || m.mr_tex >= int32_t(num_rg_textures))
+      return fail(VIMG_E_INVALID, "material: texture index out of range");
+    if ((m.type == VIMG_MAT_LAMBERTIAN || m.type == VIMG_MAT_PRINCIPLED) && m.tex < 0)
+      return fail(VIMG_E_INVALID, "material: missing colour texture");
+    if (m.normal_map >= 0 && textures[m.normal_map].type != VIMG_TEX_IMAGE)
+      return fail(VIMG_E_INVALID, "material: normal map must be an image");
+  }
+  return VIMG_OK;
+}
+
+int vimg::validate_lights(const VimgLight* lights, uint32_t num_lights, uint32_t num_prims) {
+  for (uint32_t i = 0; i < num_lights; ++i) {
+    const VimgLight& l = lights[i];
+    if (l.type == VIMG_LIGHT_PRIM) {
+      if (l.prim >= num_prims) return fail(VIMG_E_INVALID, "light: prim out of range");
+    } else if (l.type != VIMG_LIGHT_BACKGROUND) {
+      return fail(VIMG_E_INVALID, "light: unknown type");
+    }
+  }
+  return VIMG_OK;
+}
+
+// whether the tables need the TEX kernels (cones, image textures, env map)
+bool vimg::tables_textured(const VimgMaterial* materials, uint32_t num_materials, const VimgTexture* textures, const VimgBackground& bg) {
+  bool textured = (bg.type == VIMG_BG_ENVMAP);
+  for (uint32_t i = 0; i < num_materials; ++i) {
+    const VimgMaterial& m = materials[i];
+    if (m.tex >= 0 && textures[m.tex].type == VIMG_TEX_IMAGE) textured = true;
+    if (m.mr_tex >= 0 || m.normal_map >= 0) textured = true;
+  }
+  return textured;
+}
+
+// Background::is_emissive (reference include/background.h:51-56,176)
+bool vimg::background_is_emissive(const VimgBackground& bg) {
+  return (bg.type == VIMG_BG_ENVMAP) || !(bg.col[0] == 0.f && bg.col[1] == 0.f && bg.col[2] == 0.f);
+}
+
+namespace {
+
 // Shape checks so that no kernel ever indexes outside its tables.
 int validate(const VimgScene* sc) {
   if (!sc) return fail(VIMG_E_INVALID, "scene is null");
@@ -94,26 +143,8 @@ int validate(const VimgScene* sc) {
     if (t.offset + uint64_t(t.width) * t.height > sc->num_rg_texels)
       return fail(VIMG_E_INVALID, "rg texture out of bounds");
   }
-  for (uint32_t i = 0; i < sc->num_materials; ++i) {
-    const VimgMaterial& m = sc->materials[i];
-    if (m.type > VIMG_MAT_PRINCIPLED) return fail(VIMG_E_INVALID, "material: unknown type");
-    auto tex_ok = [&](int32_t t) { return t >= -1 && t < int32_t(sc->num_textures); };
-    if (!tex_ok(m.tex) || !tex_ok(m.normal_map) || m.mr_tex < -1 ||
-        m.mr_tex >= int32_t(sc->num_rg_textures))
-      return fail(VIMG_E_INVALID, "material: texture index out of range");
-    if ((m.type == VIMG_MAT_LAMBERTIAN || m.type == VIMG_MAT_PRINCIPLED) && m.tex < 0)
-      return fail(VIMG_E_INVALID, "material: missing colour texture");
-    if (m.normal_map >= 0 && sc->textures[m.normal_map].type != VIMG_TEX_IMAGE)
-      return fail(VIMG_E_INVALID, "material: normal map must be an image");
-  }
-  for (uint32_t i = 0; i < sc->num_lights; ++i) {
-    const VimgLight& l = sc->lights[i];
-    if (l.type == VIMG_LIGHT_PRIM) {
-      if (l.prim >= sc->num_prims) return fail(VIMG_E_INVALID, "light: prim out of range");
-    } else if (l.type != VIMG_LIGHT_BACKGROUND) {
-      return fail(VIMG_E_INVALID, "light: unknown type");
-    }
-  }
+  if (int rc = validate_materials(sc->materials, sc->num_materials, sc->textures, sc->num_textures, sc->num_rg_textures)) return rc;
+  if (int rc = validate_lights(sc->lights, sc->num_lights, sc->num_prims)) return rc;
   if (sc->background.type == VIMG_BG_ENVMAP) {
     const int32_t t = sc->background.env_tex;
     if (t < 0 || t >= int32_t(sc->num_textures) || sc->textures[t].type != VIMG_TEX_IMAGE)
@@ -324,12 +355,7 @@ std::vector<DLeafPrim> bake_leaves(const VimgScene* sc, const std::vector<DTriSh
     const VimgPrim& p = sc->prims[prim];
     DLeafPrim lp{};
     lp.prim = prim;
-    {
-      const uint32_t mat = p.type == VIMG_PRIM_TRIANGLE ? sc->meshes[sc->tri_mesh[p.index]].material
-                                                        : sc->spheres[p.index].material;
-      const uint32_t t = sc->materials[mat].type;
-      lp.cls = t == VIMG_MAT_DIFFUSE_LIGHT ? 0u : t == VIMG_MAT_LAMBERTIAN ? 1u : t == VIMG_MAT_PRINCIPLED ? 2u : 3u;
-    }
+    lp.cls = bake_material_class(sc->materials[bake_prim_material(p, shade.data(), sc->meshes, sc->spheres)].type);
     if (p.type == VIMG_PRIM_TRIANGLE) {
       bake_leaf_tri(shade[p.index].p, lp);
     } else {
@@ -344,50 +370,15 @@ std::vector<DLeafPrim> bake_leaves(const VimgScene* sc, const std::vector<DTriSh
 // ---- emitters, baked (device_scene.h: DLight)
 std::vector<DLight> bake_lights(const VimgScene* sc, const std::vector<DTriShade>& shade, const std::vector<float>& area_pdf) {
   std::vector<DLight> dlights(sc->num_lights);
-  for (uint32_t i = 0; i < sc->num_lights; ++i) {
-    DLight L{};
-    const VimgLight& l = sc->lights[i];
-    if (l.type == VIMG_LIGHT_BACKGROUND) {
-      L.kind = 0u;
-    } else {
-      const VimgPrim& p = sc->prims[l.prim];
-      L.index = p.index;
-      uint32_t mat;
-      if (p.type == VIMG_PRIM_TRIANGLE) {
-        const VimgMesh& mesh = sc->meshes[sc->tri_mesh[p.index]];
-        L.kind = mesh.has_normals ? 2u : 1u;
-        bake_light_tri(shade[p.index], area_pdf[p.index], L);
-        mat = mesh.material;
-      } else {
-        const VimgSphere& sp = sc->spheres[p.index];
-        L.kind = 3u;
-        bake_light_sphere(sp, L);
-        mat = sp.material;
-      }
-      const VimgMaterial& m = sc->materials[mat];
-      if (m.type == VIMG_MAT_DIFFUSE_LIGHT) L.d.x = m.emit[0], L.d.y = m.emit[1], L.d.z = m.emit[2];   // (Material::emitted of the others: 0)
-    }
-    dlights[i] = L;
-  }
+  for (uint32_t i = 0; i < sc->num_lights; ++i)
+    dlights[i] = bake_light(sc->lights[i], sc->prims, shade.data(), area_pdf.data(), sc->meshes, sc->spheres, sc->materials);
   return dlights;
 }
 
-// ---- material flags / kernel variant
 std::vector<uint32_t> material_flags(const VimgScene* sc, bool* textured) {
   std::vector<uint32_t> mflags(sc->num_materials, 0);
-  *textured = (sc->background.type == VIMG_BG_ENVMAP);
-  for (uint32_t i = 0; i < sc->num_materials; ++i) {
-    const VimgMaterial& m = sc->materials[i];
-    uint32_t f = 0;
-    if (m.type == VIMG_MAT_PRINCIPLED) f |= MATF_NEEDS_FRAME;
-    if (m.tex >= 0 && sc->textures[m.tex].type != VIMG_TEX_CONST) f |= MATF_NEEDS_UV;
-    if (m.tex >= 0 && sc->textures[m.tex].type == VIMG_TEX_IMAGE) *textured = true;
-    if (m.mr_tex >= 0 || m.normal_map >= 0) {
-      f |= MATF_NEEDS_UV;
-      *textured = true;
-    }
-    mflags[i] = f;
-  }
+  for (uint32_t i = 0; i < sc->num_materials; ++i) mflags[i] = bake_material_flags(sc->materials[i], sc->textures);
+  *textured = tables_textured(sc->materials, sc->num_materials, sc->textures, sc->background);
   return mflags;
 }
 
@@ -420,7 +411,9 @@ int upload_tables(VimgDeviceScene* s, const VimgScene* sc, const Tree& t, const 
   UP(rg_textures, sc->rg_textures, sc->num_rg_textures);
   UP(rg_texels, sc->rg_texels, sc->num_rg_texels * 2);
   UP(lights, sc->lights, sc->num_lights);
+  s->lights_table = s->tables.size() - 1;   // (a material update may swap these two)
   UP(dlights, dlights.data(), dlights.size());
+  s->dlights_table = s->tables.size() - 1;
   UP(cdf_pool, sc->cdf_pool, sc->num_cdf);
 #undef UP
 #undef UP_TO
@@ -431,8 +424,15 @@ int upload_tables(VimgDeviceScene* s, const VimgScene* sc, const Tree& t, const 
   return VIMG_OK;
 }
 
-// what a later geometry update needs of the caller's tables: the counts, and the vertex rows that carry normals
+// what a later update needs of the caller's tables: the counts, the vertex rows that carry normals, and the small
+// tables a material update is checked against
 void record_for_updates(VimgDeviceScene* s, const VimgScene* sc) {
+  s->materials.assign(sc->materials, sc->materials + sc->num_materials);
+  s->textures.assign(sc->textures, sc->textures + sc->num_textures);
+  s->lights.assign(sc->lights, sc->lights + sc->num_lights);
+  s->num_rg_textures = sc->num_rg_textures;
+  s->num_texels = sc->num_texels;
+  s->num_cdf = sc->num_cdf;
   s->num_vertices = sc->num_vertices;
   s->num_tris = sc->num_tris;
   s->num_spheres = sc->num_spheres;
@@ -509,10 +509,7 @@ int build_scene(VimgDeviceScene* s, const VimgScene* sc, const VimgHipOptions* o
   record_for_updates(s, sc);
   d.num_lights = sc->num_lights;
   d.background = sc->background;
-  // Background::is_emissive (reference include/background.h:51-56,176)
-  d.background_emissive = (sc->background.type == VIMG_BG_ENVMAP) ||
-                          !(sc->background.col[0] == 0.f && sc->background.col[1] == 0.f &&
-                            sc->background.col[2] == 0.f);
+  d.background_emissive = background_is_emissive(sc->background);
   if (int rc = resolve_options(s, opts)) return rc;
   return alloc_scratch(s);
 }
@@ -551,12 +548,20 @@ int64_t vimg_hip_scene_bytes(const VimgDeviceScene* s) {
   return s ? static_cast<int64_t>(s->total_bytes) : 0;
 }
 
-// ---- changes of a resident scene.  Argument errors are found before anything is enqueued, so
-// they leave the scene as it was; a change that passes them bumps the scene's generation, which a progressive
-// accumulator compares before its next increment.
-int vimg_hip_scene_update_geometry(VimgDeviceScene* s, const VimgGeometryUpdate* u, void* stream) {
-  if (!s || !u) return fail(VIMG_E_INVALID, "update_geometry: null scene or update");
-  if (u->struct_size < sizeof(VimgGeometryUpdate)) return fail(VIMG_E_INVALID, "update_geometry: struct_size too small");
+// ---- changes of a resident scene.  Argument errors are found before anything is enqueued,
+// so they leave the scene as it was; a change that passes them bumps the scene's generation, which a progressive
+// accumulator compares before its next increment.  The scene's update entry point: positions, then (callers
+// whose struct has the fields) images, tables and emitters.
+int vimg_hip_scene_update_geometry(VimgDeviceScene* s, const VimgGeometryUpdate* caller, void* stream) {
+  if (!s || !caller) return fail(VIMG_E_INVALID, "update_geometry: null scene or update");
+  if (caller->struct_size != VIMG_GEOMETRY_UPDATE_V1_SIZE && caller->struct_size < sizeof(VimgGeometryUpdate))
+    return fail(VIMG_E_INVALID, "update_geometry: struct_size is neither the 32 bytes of the first layout nor sizeof(VimgGeometryUpdate)");
+  VimgGeometryUpdate update{};   // the caller's fields; the ones its struct does not have stay 0 = unchanged
+  std::memcpy(&update, caller, std::min<size_t>(caller->struct_size, sizeof(update)));
+  const VimgGeometryUpdate* u = &update;
+  if (int rc = check_relight(s, u)) return rc;
+  RelightPlan plan;
+  if (int rc = prepare_relight(s, u, &plan)) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
   ++s->generation;
   if (u->normals)   // rows of meshes without normals keep what the upload gave them
@@ -576,10 +581,13 @@ int vimg_hip_scene_update_geometry(VimgDeviceScene* s, const VimgGeometryUpdate*
   up.num_levels = static_cast<uint32_t>(s->level_begin.size() - 1);
   up.root_box = s->root_box.as<float>();
   HIP_TRY(enqueue_scene_update(s->d, up, st));
+  if (plan.any)
+    if (int rc = enqueue_relight(s, u, &plan, st)) return rc;
   float box[6];
   HIP_TRY(hipMemcpyAsync(box, s->root_box.p, sizeof(box), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   for (int a = 0; a < 3; ++a) s->d.root_min[a] = box[a], s->d.root_max[a] = box[3 + a];
+  if (plan.any) commit_relight(s, u, &plan);
   return VIMG_OK;
 }
 

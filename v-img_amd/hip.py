@@ -83,6 +83,9 @@ class DeviceScene:
         self.resolution = host_scene.resolution
         v = host_scene.view.contents
         self.num_vertices, self.num_spheres = int(v.num_vertices), int(v.num_spheres)
+        self.num_materials, self.num_textures = int(v.num_materials), int(v.num_textures)
+        self._image_sizes = {i: (int(v.textures[i].height), int(v.textures[i].width)) for i in range(v.num_textures)
+                             if v.textures[i].type == abi.TEX_IMAGE}
 
     @property
     def bytes(self):
@@ -155,6 +158,75 @@ class DeviceScene:
             upd.spheres = self._device_table(spheres, self.num_spheres, 4, "spheres", keep)
         with _Ordered(stream) as sp:
             _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
+
+    @staticmethod
+    def _record_table(records, n, ctype, what):
+        """A ctypes array of n `ctype` records from a ctypes array or a sequence of records."""
+        if len(records) != n:
+            raise ValueError(f"{what}: expected {n} records, got {len(records)}")
+        if isinstance(records, C.Array) and records._type_ is ctype:
+            return records
+        return (ctype * max(n, 1))(*records)
+
+    def _fill_material_update(self, upd, keep, materials, textures, lights, background, images):
+        if materials is not None:
+            arr = self._record_table(materials, self.num_materials, abi.Material, "materials")
+            keep.append(arr)
+            upd.materials = C.cast(arr, C.POINTER(abi.Material))
+        if textures is not None:
+            arr = self._record_table(textures, self.num_textures, abi.Texture, "textures")
+            keep.append(arr)
+            upd.textures = C.cast(arr, C.POINTER(abi.Texture))
+        if lights is not None:
+            arr = self._record_table(lights, len(lights), abi.Light, "lights")
+            keep.append(arr)
+            upd.lights = C.cast(arr, C.POINTER(abi.Light))
+            upd.num_lights, upd.set_lights = len(lights), 1
+        if background is not None:
+            bg = abi.Background.from_buffer_copy(background)
+            keep.append(bg)
+            upd.background = C.pointer(bg)
+        if images:
+            arr = (abi.TextureImage * len(images))()
+            for k, (tex, img) in enumerate(images.items()):
+                if tex not in self._image_sizes:
+                    raise ValueError(f"images: texture {tex} is not an image texture of the scene")
+                h, w = self._image_sizes[tex]
+                arr[k].texture = int(tex)
+                arr[k].level0 = self._device_table(img.reshape(-1, 3) if tuple(img.shape) == (h, w, 3) else img, h * w, 3,
+                                                   f"images[{tex}]", keep)
+            keep.append(arr)
+            upd.images = C.cast(arr, C.POINTER(abi.TextureImage))
+            upd.num_images = len(images)
+
+    def update_materials(self, materials=None, textures=None, lights=None, background=None, images=None, stream=None,
+                         vertices=None, normals=None, spheres=None):
+        """New materials, texture records, emitters, background and image contents for the resident scene (the
+        material fields of vimg_hip_scene_update_geometry); None = unchanged.  ``materials`` / ``textures``: the whole
+        tables (abi.Material / abi.Texture records, as HostScene.materials() / .textures() return them);
+        ``lights``: a new emitter list of abi.Light, ``[]`` for a scene without emitters; ``background``: an
+        abi.Background that keeps type, env_tex and CDF offsets; ``images``: {texture index: [H, W, 3] float32} - a
+        CUDA tensor is read where it is, a numpy array is copied up - whose mip chains (and, for the env map, sampling
+        CDFs) are rebuilt on the GPU.  Positions (as for update_geometry) may ride in the same call.  Afterwards the
+        scene is the upload of the host scene edited the same way; progressive accumulators must be reset."""
+        keep = []
+        upd = abi.GeometryUpdate()
+        if vertices is not None:
+            upd.vertices = self._device_table(vertices, self.num_vertices, 3, "vertices", keep)
+        if normals is not None:
+            upd.normals = self._device_table(normals, self.num_vertices, 3, "normals", keep)
+        if spheres is not None:
+            upd.spheres = self._device_table(spheres, self.num_spheres, 4, "spheres", keep)
+        self._fill_material_update(upd, keep, materials, textures, lights, background, images)
+        with _Ordered(stream) as sp:
+            _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
+
+    def update_from(self, host_scene, stream=None):
+        """The four tables of ``host_scene`` (materials, texture records, emitters, background) as they now stand:
+        after HostScene.set_materials / set_texture_colors / set_background on the scene this one was uploaded from.
+        Image contents are not read from the host: pass them with update_materials(images=...)."""
+        self.update_materials(materials=host_scene.materials(), textures=host_scene.textures(), lights=list(host_scene.lights()),
+                              background=host_scene.background(), stream=stream)
 
     def rebuild_bvh(self, builder="ploc", stream=None):
         """A new tree over the scene's primitives as they now stand (vimg_hip_scene_rebuild_bvh): built by the GPU

@@ -25,6 +25,29 @@ class HostError(RuntimeError):
     pass
 
 
+MATERIAL_KINDS = {"lambertian": abi.MAT_LAMBERTIAN, "dielectric": abi.MAT_DIELECTRIC,
+                  "diffuse_light": abi.MAT_DIFFUSE_LIGHT, "principled": abi.MAT_PRINCIPLED}
+
+
+def make_material(kind, tex=-1, mr_tex=-1, normal_map=-1, emit=(0, 0, 0), ior=1.5,
+                  metallic=0.0, roughness=0.5, spec_trans=0.0, subsurface=0.0, specular=0.5,
+                  spec_tint=0.0, anisotropic=0.0, sheen=0.0, sheen_tint=0.5, clearcoat=0.0,
+                  clearcoat_gloss=1.0, eta=1.5):
+    """The abi.Material record HostScene.add_material stores for these arguments (a record of a table passed to
+    HostScene.set_materials or DeviceScene.update_materials)."""
+    m = abi.Material()
+    m.type = MATERIAL_KINDS[kind]
+    m.tex, m.mr_tex, m.normal_map = tex, mr_tex, normal_map
+    m.emit[0], m.emit[1], m.emit[2] = emit
+    m.ior = ior
+    m.metallic_factor, m.roughness_factor = metallic, roughness
+    m.specular_transmission, m.subsurface, m.specular = spec_trans, subsurface, specular
+    m.specular_tint, m.anisotropic, m.sheen, m.sheen_tint = spec_tint, anisotropic, sheen, \
+        sheen_tint
+    m.clearcoat, m.clearcoat_gloss, m.eta = clearcoat, clearcoat_gloss, eta
+    return m
+
+
 class HostScene:
     """Owns a ``VimgHostScene``; ``.view`` is the POD ``VimgScene`` the render libraries take."""
 
@@ -90,21 +113,9 @@ class HostScene:
         return self._check(self._lib.vimg_host_add_texture_rg(self._h, w, h, _fp(img), wrap_u,
                                                               wrap_v))
 
-    def add_material(self, kind, tex=-1, mr_tex=-1, normal_map=-1, emit=(0, 0, 0), ior=1.5,
-                     metallic=0.0, roughness=0.5, spec_trans=0.0, subsurface=0.0, specular=0.5,
-                     spec_tint=0.0, anisotropic=0.0, sheen=0.0, sheen_tint=0.5, clearcoat=0.0,
-                     clearcoat_gloss=1.0, eta=1.5):
-        m = abi.Material()
-        m.type = {"lambertian": abi.MAT_LAMBERTIAN, "dielectric": abi.MAT_DIELECTRIC,
-                  "diffuse_light": abi.MAT_DIFFUSE_LIGHT, "principled": abi.MAT_PRINCIPLED}[kind]
-        m.tex, m.mr_tex, m.normal_map = tex, mr_tex, normal_map
-        m.emit[0], m.emit[1], m.emit[2] = emit
-        m.ior = ior
-        m.metallic_factor, m.roughness_factor = metallic, roughness
-        m.specular_transmission, m.subsurface, m.specular = spec_trans, subsurface, specular
-        m.specular_tint, m.anisotropic, m.sheen, m.sheen_tint = spec_tint, anisotropic, sheen, \
-            sheen_tint
-        m.clearcoat, m.clearcoat_gloss, m.eta = clearcoat, clearcoat_gloss, eta
+    def add_material(self, kind, **fields):
+        """A new material (the keyword arguments of make_material); returns its index."""
+        m = make_material(kind, **fields)
         return self._check(self._lib.vimg_host_add_material(self._h, C.byref(m)))
 
     def add_mesh(self, vertices, indices, material, normals=None, uv_sets=(), color_uv=abi.NO_UV,
@@ -177,6 +188,70 @@ class HostScene:
         sph = np.array([list(v.spheres[i].center) + [v.spheres[i].radius] for i in range(ns)],
                        dtype=np.float32).reshape(ns, 4)
         return verts, nrm, sph
+
+    # ---- new materials, texture contents and background (DeviceScene.update_materials on the host) ------
+    def _copy_table(self, ptr, n, ctype):
+        out = (ctype * n)()
+        if n:
+            C.memmove(out, ptr, n * C.sizeof(ctype))
+        return out
+
+    def materials(self):
+        """A copy of the material table: a ctypes array of abi.Material (edit it and pass it to set_materials)."""
+        v = self.view.contents
+        return self._copy_table(v.materials, v.num_materials, abi.Material)
+
+    def textures(self):
+        """A copy of the texture records: a ctypes array of abi.Texture."""
+        v = self.view.contents
+        return self._copy_table(v.textures, v.num_textures, abi.Texture)
+
+    def lights(self):
+        """A copy of the emitter list: a ctypes array of abi.Light."""
+        v = self.view.contents
+        return self._copy_table(v.lights, v.num_lights, abi.Light)
+
+    def background(self):
+        """A copy of the background record (abi.Background)."""
+        return abi.Background.from_buffer_copy(self.view.contents.background)
+
+    def set_materials(self, materials):
+        """The whole material table (as many abi.Material records as the scene has).  The emitter list is rebuilt
+        as the construction calls would have built it with these materials from the start."""
+        n = self.view.contents.num_materials
+        if len(materials) != n:
+            raise HostError(f"set_materials: expected {n} records, got {len(materials)}")
+        arr = (abi.Material * n)(*materials) if not isinstance(materials, C.Array) else materials
+        self._check(self._lib.vimg_host_set_materials(self._h, arr))
+
+    def set_texture_colors(self, tex, col_a, col_b=None, width=0, height=0):
+        """A constant texture's colour, or a checkerboard's two colours and cell counts."""
+        a = _f32(col_a)
+        b = _f32(col_b) if col_b is not None else None
+        self._check(self._lib.vimg_host_set_texture_colors(self._h, tex, _fp(a), _fp(b) if b is not None else None,
+                                                           int(width), int(height)))
+
+    def set_texture_image(self, tex, rgb):
+        """A new level 0 ([H, W, 3] float32, the texture's size) for an image texture: the mip chain, and the
+        sampling CDFs when it is the env map, are rebuilt in place."""
+        t = self.view.contents.textures[tex] if 0 <= tex < self.view.contents.num_textures else None
+        if t is None or t.type != abi.TEX_IMAGE:
+            raise HostError(f"set_texture_image: texture {tex} is not an image texture")
+        img = _f32(rgb)
+        if img.shape != (t.height, t.width, 3):
+            raise HostError(f"set_texture_image: expected shape {(t.height, t.width, 3)}, got {img.shape}")
+        self._check(self._lib.vimg_host_set_texture_image(self._h, tex, _fp(img)))
+
+    def set_background(self, col=None, world_to_env=None, env_to_world=None, radiance_scale=None):
+        """Colour, env rotation matrices and radiance scale of the background as it stands (None = keep); its type
+        and its place in the emitter list stay."""
+        c = _f32(col) if col is not None else None
+        w2e = _f32(world_to_env, (16,)) if world_to_env is not None else None
+        e2w = _f32(env_to_world, (16,)) if env_to_world is not None else None
+        scale = self.view.contents.background.radiance_scale if radiance_scale is None else radiance_scale
+        self._check(self._lib.vimg_host_set_background(self._h, _fp(c) if c is not None else None,
+                                                       _fp(w2e) if w2e is not None else None,
+                                                       _fp(e2w) if e2w is not None else None, scale))
 
     def build_bvh_with(self, builder_fn_ptr):
         """Build the BVH with a caller-supplied builder (a C function pointer with the

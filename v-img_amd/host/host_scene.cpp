@@ -3,6 +3,7 @@
 //   quads / lights  : reference src/geometry/mesh_loading.cpp:67-104
 #include "host_scene.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -598,7 +599,10 @@ void vimg_host_set_background_const(VimgHostScene* s, const float rgb[3], int ad
   s->background.type = VIMG_BG_CONST;
   s->background.env_tex = -1;
   std::memcpy(s->background.col, rgb, 12);
-  if (add_to_lights) s->lights.push_back(VimgLight{VIMG_LIGHT_BACKGROUND, 0});
+  if (add_to_lights) {
+    s->lights.push_back(VimgLight{VIMG_LIGHT_BACKGROUND, 0});
+    s->bg_light_at.push_back(static_cast<uint32_t>(s->prims.size()));
+  }
 }
 
 int vimg_host_set_background_envmap(VimgHostScene* s, int env_tex, const float world_to_env[16],
@@ -620,6 +624,7 @@ int vimg_host_set_background_envmap(VimgHostScene* s, int env_tex, const float w
     return -1;
   s->background = bg;
   s->lights.push_back(VimgLight{VIMG_LIGHT_BACKGROUND, 0});
+  s->bg_light_at.push_back(static_cast<uint32_t>(s->prims.size()));
   return 0;
 }
 
@@ -709,6 +714,131 @@ int vimg_host_refit_bvh(VimgHostScene* s) {
   std::vector<V3> centers;
   prim_bounds(*s, bounds, centers);
   refit_bvh(bounds, s->bvh);
+  return 0;
+}
+
+// ---- new materials, texture contents and background on the same primitives (the host counterparts of the
+// material fields of vimg_hip_scene_update_geometry).  None of them touches the tree: positions are unchanged.
+int vimg_host_set_materials(VimgHostScene* s, const VimgMaterial* materials) {
+  if (!s || !materials) {
+    host_set_error("set_materials: null scene or materials");
+    return -1;
+  }
+  const size_t n = s->materials.size();
+  auto tex_ok = [&](int32_t t) { return t >= -1 && t < static_cast<int32_t>(s->textures.size()); };
+  for (size_t i = 0; i < n; ++i) {
+    const VimgMaterial& m = materials[i];
+    if (m.type > VIMG_MAT_PRINCIPLED) {
+      host_set_error("set_materials: unknown material type");
+      return -1;
+    }
+    if (!tex_ok(m.tex) || !tex_ok(m.normal_map) || m.mr_tex < -1 || m.mr_tex >= static_cast<int32_t>(s->rg_textures.size())) {
+      host_set_error("set_materials: texture index out of range");
+      return -1;
+    }
+    if ((m.type == VIMG_MAT_LAMBERTIAN || m.type == VIMG_MAT_PRINCIPLED) && m.tex < 0) {
+      host_set_error("set_materials: lambertian/principled need a colour texture");
+      return -1;
+    }
+    if (m.normal_map >= 0 && s->textures[m.normal_map].type != VIMG_TEX_IMAGE) {
+      host_set_error("set_materials: normal map must be an image texture");
+      return -1;
+    }
+  }
+  s->materials.assign(materials, materials + n);
+  // the emitter list the construction calls would have left with these materials: surfaces in primitive order,
+  // an emissive mesh's triangles last to first, the background entries where set_background_* appended them
+  std::vector<VimgLight> lights;
+  size_t bg = 0;
+  const uint32_t num_prims = static_cast<uint32_t>(s->prims.size());
+  auto backgrounds_up_to = [&](uint32_t prim) {
+    for (; bg < s->bg_light_at.size() && s->bg_light_at[bg] <= prim; ++bg) lights.push_back(VimgLight{VIMG_LIGHT_BACKGROUND, 0});
+  };
+  for (uint32_t i = 0; i < num_prims;) {
+    backgrounds_up_to(i);
+    const VimgPrim& p = s->prims[i];
+    if (p.type == VIMG_PRIM_SPHERE) {
+      if (material_is_emissive(*s, s->spheres[p.index].material)) lights.push_back(VimgLight{VIMG_LIGHT_PRIM, i});
+      ++i;
+      continue;
+    }
+    const uint32_t mesh = s->tri_mesh[p.index];
+    uint32_t nt = 1;   // a mesh's triangles are consecutive primitives
+    while (i + nt < num_prims && s->prims[i + nt].type == VIMG_PRIM_TRIANGLE && s->tri_mesh[s->prims[i + nt].index] == mesh) ++nt;
+    if (material_is_emissive(*s, s->meshes[mesh].material))
+      for (uint32_t t = nt; t > 0; --t) lights.push_back(VimgLight{VIMG_LIGHT_PRIM, i + t - 1});
+    i += nt;
+  }
+  backgrounds_up_to(num_prims);
+  s->lights = std::move(lights);
+  if (s->bvh_built) s->refresh_view();
+  return 0;
+}
+
+int vimg_host_set_texture_colors(VimgHostScene* s, uint32_t tex, const float col_a[3], const float col_b[3], uint32_t w, uint32_t h) {
+  if (!s || tex >= s->textures.size() || !col_a) {
+    host_set_error("set_texture_colors: null scene or colour, or texture out of range");
+    return -1;
+  }
+  VimgTexture& t = s->textures[tex];
+  if (t.type == VIMG_TEX_CONST) {
+    std::memcpy(t.col_a, col_a, 12);
+    return 0;
+  }
+  if (t.type != VIMG_TEX_CHECKER || !col_b) {
+    host_set_error("set_texture_colors: only constant and checker textures have colours (a checker needs both)");
+    return -1;
+  }
+  std::memcpy(t.col_a, col_a, 12);
+  std::memcpy(t.col_b, col_b, 12);
+  t.width = w;
+  t.height = h;
+  return 0;
+}
+
+int vimg_host_set_texture_image(VimgHostScene* s, uint32_t tex, const float* rgb) {
+  if (!s || !rgb || tex >= s->textures.size() || s->textures[tex].type != VIMG_TEX_IMAGE) {
+    host_set_error("set_texture_image: null scene or image, or not an image texture");
+    return -1;
+  }
+  // the chain and the tables are built as add_texture_image / set_background_envmap build them (installed
+  // precompute builders included), into pools of their own, and copied over the old ones: same size, same offsets
+  const VimgTexture old = s->textures[tex];
+  VimgTexture t{};
+  std::vector<float> pool;
+  if (!build_mip_chain(old.width, old.height, rgb, old.wrap_u, old.wrap_v, t, pool)) return -1;
+  if (t.num_levels != old.num_levels) {
+    host_set_error("set_texture_image: the rebuilt chain has another number of levels");
+    return -1;
+  }
+  std::vector<float> cdfs;
+  uint64_t row_off = 0, col_off = 0;
+  const bool env = s->background.type == VIMG_BG_ENVMAP && s->background.env_tex == static_cast<int32_t>(tex);
+  if (env && !build_env_cdfs(pool.data() + t.level_offset[0] * 3, old.width, old.height, cdfs, row_off, col_off)) return -1;
+  uint32_t lw = old.width, lh = old.height;
+  for (uint32_t l = 0; l < old.num_levels; ++l) {
+    std::memcpy(s->texels.data() + old.level_offset[l] * 3, pool.data() + t.level_offset[l] * 3, size_t(lw) * lh * 3 * sizeof(float));
+    lw = std::max(lw / 2u, 1u), lh = std::max(lh / 2u, 1u);
+  }
+  if (env) {
+    std::memcpy(s->cdf_pool.data() + s->background.row_cdf_offset, cdfs.data() + row_off, (size_t(old.height) + 1) * sizeof(float));
+    std::memcpy(s->cdf_pool.data() + s->background.col_cdf_offset, cdfs.data() + col_off,
+                size_t(old.height) * (old.width + 1) * sizeof(float));
+  }
+  return 0;
+}
+
+int vimg_host_set_background(VimgHostScene* s, const float col[3], const float world_to_env[16], const float env_to_world[16],
+                             float radiance_scale) {
+  if (!s) {
+    host_set_error("set_background: null scene");
+    return -1;
+  }
+  if (col) std::memcpy(s->background.col, col, 12);
+  if (world_to_env) std::memcpy(s->background.world_to_env, world_to_env, 64);
+  if (env_to_world) std::memcpy(s->background.env_to_world, env_to_world, 64);
+  s->background.radiance_scale = radiance_scale;
+  s->view.background = s->background;
   return 0;
 }
 

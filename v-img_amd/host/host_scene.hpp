@@ -33,6 +33,7 @@ struct VimgHostScene {
   std::vector<VimgTextureRG> rg_textures;
   std::vector<float> rg_texels;
   std::vector<VimgLight> lights;
+  std::vector<uint32_t> bg_light_at;   // prims.size() at every set_background_* call that appended a background light
   std::vector<float> cdf_pool;
   HostBVH bvh;
   bool bvh_built = false;
