@@ -309,6 +309,11 @@ HIP_SYMBOLS = {
     "vimg_hip_last_error": (C.c_char_p, []),
 }
 
+# what the library exports without declaring it in include/vimg_hip.h: the unit-level test hook (csrc/vimg_hip.hip)
+HIP_TEST_SYMBOLS = {
+    "vimg_hip_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, Pf32, Pf32]),
+}
+
 
 def _bind(lib, table):
     for name, (res, args) in table.items():
@@ -348,5 +353,5 @@ def hip_lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        _hip_lib = _bind(C.CDLL(path), HIP_SYMBOLS)
+        _hip_lib = _bind(_bind(C.CDLL(path), HIP_SYMBOLS), HIP_TEST_SYMBOLS)
     return _hip_lib

@@ -92,6 +92,8 @@ namespace vimg {
 
 extern hipStream_t g_stream;   // vimg_hip.hip (vimg_hip_init)
 extern int g_device;
+// the stream argument of the ABI: NULL = the library's own stream
+inline hipStream_t stream_of(void* stream) { return stream ? static_cast<hipStream_t>(stream) : g_stream; }
 
 inline uint32_t tiles_of(int n) { return (static_cast<uint32_t>(n) + 7u) / 8u; }
 uint32_t local_tiles(const VimgDeviceScene* s, const VimgRenderParams* p);
@@ -168,10 +170,18 @@ struct ProgLaunch {
   bool keep_stats = false;
 };
 int check_params(const VimgDeviceScene* s, const VimgRenderParams* p);
-// Enqueues one render on `st` (counter / queue resets, then the kernel); ev0 / ev1, when given, are recorded
-// right before and right after the kernel itself.
-int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, hipStream_t st, bool full_stats,
-                   bool want_stats, int sx, int sy, hipEvent_t ev0, hipEvent_t ev1, const ProgLaunch* prog);
+int check_render(const VimgDeviceScene* s, const VimgRenderParams* p, const void* d_out);   // check_params, and an output to write
+// One render for enqueue_render: into d_out on `st` (counter / queue resets, then the kernel).  stats: the statistics
+// build, counting into the scene's DeviceStats; (sx, sy): that pixel alone; ev0 / ev1: recorded right around the kernel.
+struct RenderLaunch {
+  float* d_out;
+  hipStream_t st;
+  bool stats = false;
+  int sx = -1, sy = -1;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const ProgLaunch* prog = nullptr;
+};
+int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, const RenderLaunch& r);
 int check_kernel_error(VimgDeviceScene* s);    // reads (and clears) the scene's error word
 uint64_t fetch_shard_pixels(const VimgDeviceScene* s, const VimgRenderParams* p);   // pixels the shard owns
 int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* out);   // (paths = pixels x p->samples)

@@ -17,7 +17,7 @@ int vimg_hip_post_rgb8(const void* d_rgb, int w, int h, int tonemapper, void* d_
     int rc = vimg_hip_init(0);
     if (rc) return rc;
   }
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   const size_t n = size_t(w) * h;
   static unsigned int* d_max = nullptr;   // (deliberately of the process, never freed: per call it would add an allocation to every post step)
   if (!d_max) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_max), sizeof(unsigned int)));

@@ -46,7 +46,7 @@ int vimg_hip_progressive_render_masked(VimgDeviceScene* s, VimgProgressive* a, u
   VimgRenderParams p = a->params;
   p.samples = samples;
   if (int rc = check_params(s, &p)) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   void* d_user_out = d_out;
   if (!d_out) {   // advance only: the render kernels' means go to a buffer of the accumulator's
     const size_t floats = (p.tile_world == 1 ? size_t(s->d.res_x) * s->d.res_y : size_t(a->items)) * 3u;
@@ -63,8 +63,7 @@ int vimg_hip_progressive_render_masked(VimgDeviceScene* s, VimgProgressive* a, u
 
   if (everyone) {
     const ProgLaunch pl{a->samples, old_rec, new_rec};
-    if (int rc = enqueue_render(s, &p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1,
-                                nullptr, nullptr, &pl))
+    if (int rc = enqueue_render(s, &p, {.d_out = static_cast<float*>(d_out), .st = st, .stats = stats != nullptr, .prog = &pl}))
       return rc;
     launches = a->items ? 1 : 0;
     paths = a->valid_items * samples;
@@ -105,8 +104,7 @@ int vimg_hip_progressive_render_masked(VimgDeviceScene* s, VimgProgressive* a, u
       const uint32_t cls = w[ACTL_CLASS], len = w[ACTL_LEN], next = w[ACTL_NEXT];
       if (len == 0) break;   // nothing selected
       const ProgLaunch pl{cls, old_rec, new_rec, a->item_list.as<uint32_t>(), len, launches != 0};
-      if (int rc = enqueue_render(s, &p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1,
-                                  nullptr, nullptr, &pl))
+      if (int rc = enqueue_render(s, &p, {.d_out = static_cast<float*>(d_out), .st = st, .stats = stats != nullptr, .prog = &pl}))
         return rc;
       ++launches;
       paths += uint64_t(len) * samples;
@@ -146,7 +144,7 @@ uint64_t vimg_hip_progressive_launches(const VimgProgressive* a) { return a ? a-
 int vimg_hip_progressive_state(VimgProgressive* a, void* d_sum_rgb, void* d_count, void* d_batches, void* d_m2,
                                void* stream) {
   if (int rc = check_acc(a, "progressive_state")) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   if (!a->items || (!d_sum_rgb && !d_count && !d_batches && !d_m2)) return VIMG_OK;
   hipLaunchKernelGGL(adapt_state_kernel, dim3(blocks_of(a->items, 256u)), dim3(256), 0, st, geom_of(a),
                      (const v4u*)a->rec[a->cur].as<v4u>(), static_cast<float*>(d_sum_rgb), static_cast<uint32_t*>(d_count),
@@ -158,7 +156,7 @@ int vimg_hip_progressive_state(VimgProgressive* a, void* d_sum_rgb, void* d_coun
 int vimg_hip_progressive_error(VimgProgressive* a, void* d_err, void* stream) {
   if (int rc = check_acc(a, "progressive_error")) return rc;
   if (!d_err) return fail(VIMG_E_INVALID, "progressive_error: null output pointer");
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   if (!a->items) return VIMG_OK;
   hipLaunchKernelGGL(adapt_resolve_kernel, dim3(blocks_of(a->items, 256u)), dim3(256), 0, st, geom_of(a),
                      (const v4u*)a->rec[a->cur].as<v4u>(), (float*)nullptr, static_cast<float*>(d_err), (uint8_t*)nullptr,
@@ -173,7 +171,7 @@ int vimg_hip_progressive_select(VimgProgressive* a, float target, uint32_t max_s
   if (!d_mask || !active_out) return fail(VIMG_E_INVALID, "progressive_select: null mask or count pointer");
   if (!(target >= 0.f)) return fail(VIMG_E_INVALID, "progressive_select: the target must be a number >= 0");
   *active_out = 0;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   if (!a->items) return VIMG_OK;
   if (int rc = ensure_scratch(a)) return rc;
   uint32_t* ctl = a->ctl.as<uint32_t>();

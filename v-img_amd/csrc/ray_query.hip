@@ -157,7 +157,7 @@ int ensure_query(VimgDeviceScene* s) {
 int launch_query(VimgDeviceScene* s, int kind, const void* rays, uint32_t n, void* hits, void* info, uint8_t* flags,
                  void* stream) {
   if (int rc = ensure_query(s)) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   const uint64_t chunks = (uint64_t(n) + 63u) / 64u;
   uint64_t grid = (chunks + 3u) / 4u;   // one workgroup per 256 rays
   // Policy: the persistent grid when the top of the tree is staged and the rest read from global memory (config 5
@@ -193,7 +193,7 @@ int vimg_hip_occluded(VimgDeviceScene* s, const void* d_rays, uint64_t n, uint8_
 int vimg_hip_camera_rays(VimgDeviceScene* s, const void* d_samples, uint64_t n, void* d_rays, void* stream) {
   if (int rc = check_query("camera_rays", s, n, d_samples, "samples", d_rays, "rays", true)) return rc;
   if (n == 0) return VIMG_OK;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   HIP_TRY(enqueue_camera_rays(s->d, d_samples, uint32_t(n), d_rays, st));
   return VIMG_OK;
 }

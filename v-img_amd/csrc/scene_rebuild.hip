@@ -186,7 +186,7 @@ int vimg_hip_scene_rebuild_bvh(VimgDeviceScene* s, const VimgRebuildOptions* opt
   }
   if (builder != VIMG_BUILDER_PLOC && builder != VIMG_BUILDER_LBVH) return fail(VIMG_E_INVALID, "rebuild_bvh: unknown builder");
   if (g_device < 0) return fail(VIMG_E_DEVICE, "rebuild_bvh: no device");
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   const uint32_t n = s->num_leaf_prims;
 
   // 1. primitive bounds, after whatever the stream still holds; the builders run on the null stream
@@ -271,7 +271,7 @@ int vimg_hip_scene_rebuild_bvh(VimgDeviceScene* s, const VimgRebuildOptions* opt
 int vimg_hip_scene_bvh_cost(VimgDeviceScene* s, void* stream, double* cost) {
   if (!s || !cost) return fail(VIMG_E_INVALID, "bvh_cost: null scene or result");
   if (g_device < 0) return fail(VIMG_E_DEVICE, "bvh_cost: no device");
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   const uint32_t num_partial = (s->n_internal + kBlock - 1) / kBlock;
   DevBuf d_sums;   // the partial sums, then the result
   if (int rc = d_sums.alloc((size_t(num_partial) + 1) * sizeof(double))) return rc;

@@ -562,7 +562,7 @@ int vimg_hip_scene_update_geometry(VimgDeviceScene* s, const VimgGeometryUpdate*
   if (int rc = check_relight(s, u)) return rc;
   RelightPlan plan;
   if (int rc = prepare_relight(s, u, &plan)) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   ++s->generation;
   if (u->normals)   // rows of meshes without normals keep what the upload gave them
     for (const auto& r : s->normal_rows)

@@ -45,6 +45,12 @@ int check_params(const VimgDeviceScene* s, const VimgRenderParams* p) {
   return VIMG_OK;
 }
 
+int check_render(const VimgDeviceScene* s, const VimgRenderParams* p, const void* d_out) {
+  if (int rc = check_params(s, p)) return rc;
+  if (!d_out) return fail(VIMG_E_INVALID, "null output pointer");
+  return VIMG_OK;
+}
+
 }  // namespace vimg
 
 namespace {
@@ -83,12 +89,11 @@ int ensure_pool(VimgDeviceScene* s, LaunchCfg& c) {
 
 namespace vimg {
 
-// Enqueues one render on `st` (counter / queue resets, then the kernel); ev0 / ev1, when given, are
-// recorded right before and right after the kernel itself.
-int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, hipStream_t st,
-                   bool full_stats, bool want_stats, int sx, int sy, hipEvent_t ev0, hipEvent_t ev1,
-                   const ProgLaunch* prog) {
-  LaunchCfg c = make_launch(s, p, sx, sy);
+int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, const RenderLaunch& r) {
+  const ProgLaunch* prog = r.prog;
+  const hipStream_t st = r.st;
+  float* d_out = r.d_out;
+  LaunchCfg c = make_launch(s, p, r.sx, r.sy);
   if (prog) {
     c.args.sample_base = prog->base;
     c.args.spp_div = static_cast<float>(prog->base + p->samples);   // (the caller keeps the total <= UINT32_MAX)
@@ -98,26 +103,25 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, float* d_out, 
     c.args.item_count = prog->item_count;
   }
   if (int rc = ensure_pool(s, c)) return rc;
-  c.args.full_stats = full_stats ? 1u : 0u;
-  if (c.args.num_local_tiles == 0 && sx < 0) return VIMG_OK;
+  c.args.full_stats = r.stats ? 1u : 0u;
+  if (c.args.num_local_tiles == 0 && r.sx < 0) return VIMG_OK;
   // (the work counter only: the error word behind it is sticky until a blocking call or vimg_hip_check reads it)
   HIP_TRY(hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), st));
-  if (want_stats && !(prog && prog->keep_stats)) HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DeviceStats), st));
-  DeviceStats* stats = want_stats ? s->stats.as<DeviceStats>() : nullptr;
-  const void* kernel = launched_kernel_of(s, c, full_stats);
+  if (r.stats && !(prog && prog->keep_stats)) HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DeviceStats), st));
+  DeviceStats* stats = r.stats ? s->stats.as<DeviceStats>() : nullptr;
+  const void* kernel = launched_kernel_of(s, c, r.stats);
   if (c.lds_bytes > 48u * 1024u)   // ask for the large dynamic-LDS carve-out
     HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(c.lds_bytes)));
+  if (r.ev0) HIP_TRY(hipEventRecord(r.ev0, st));
   if (c.sched == VIMG_SCHED_CU) {
-    if (ev0) HIP_TRY(hipEventRecord(ev0, st));
     CuKArgs ka{s->d, c.args, d_out, stats, s->counter.as<unsigned int>()};
     void* kargs[] = {&ka};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(uint32_t(c.cu_waves) * 64u), kargs, c.lds_bytes, st));
   } else {
-    if (ev0) HIP_TRY(hipEventRecord(ev0, st));
     void* kargs[] = {&s->d, &c.args, &d_out, &stats, &s->counter.p};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(256), kargs, c.lds_bytes, st));
   }
-  if (ev1) HIP_TRY(hipEventRecord(ev1, st));
+  if (r.ev1) HIP_TRY(hipEventRecord(r.ev1, st));
   HIP_TRY(hipGetLastError());
   return VIMG_OK;
 }
@@ -246,11 +250,8 @@ int64_t vimg_hip_shard_pixels(const VimgDeviceScene* s, const VimgRenderParams* 
 }
 
 int vimg_hip_render_async(VimgDeviceScene* s, const VimgRenderParams* p, void* d_out, void* stream) {
-  int rc = check_params(s, p);
-  if (rc) return rc;
-  if (!d_out) return fail(VIMG_E_INVALID, "null output pointer");
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
-  return enqueue_render(s, p, static_cast<float*>(d_out), st, false, false, -1, -1, nullptr, nullptr, nullptr);
+  if (int rc = check_render(s, p, d_out)) return rc;
+  return enqueue_render(s, p, {.d_out = static_cast<float*>(d_out), .st = stream_of(stream)});
 }
 
 int vimg_hip_check(VimgDeviceScene* s) {
@@ -260,12 +261,9 @@ int vimg_hip_check(VimgDeviceScene* s) {
 
 int vimg_hip_render(VimgDeviceScene* s, const VimgRenderParams* p, void* d_out, void* stream,
                     VimgRenderStats* stats) {
-  int rc = check_params(s, p);
-  if (rc) return rc;
-  if (!d_out) return fail(VIMG_E_INVALID, "null output pointer");
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
-  rc = enqueue_render(s, p, static_cast<float*>(d_out), st, stats != nullptr, stats != nullptr, -1, -1, nullptr, nullptr, nullptr);
-  if (rc) return rc;
+  if (int rc = check_render(s, p, d_out)) return rc;
+  hipStream_t st = stream_of(stream);
+  if (int rc = enqueue_render(s, p, {.d_out = static_cast<float*>(d_out), .st = st, .stats = stats != nullptr})) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   if (int rc2 = check_kernel_error(s)) return rc2;
   if (stats) return fetch_stats(s, p, stats);
@@ -328,11 +326,9 @@ int vimg_hip_progressive_free(VimgProgressive* a) {
 // integrator field of the parameters is not used, samples and the tile shard are.
 int vimg_hip_render_heatmap(VimgDeviceScene* s, const VimgRenderParams* p, float factor, void* d_out,
                             void* stream) {
-  int rc = check_params(s, p);
-  if (rc) return rc;
-  if (!d_out) return fail(VIMG_E_INVALID, "null output pointer");
+  if (int rc = check_render(s, p, d_out)) return rc;
   if (factor <= 0) factor = 20.f;   // heatmap.cpp:137-139
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   LaunchCfg c = make_launch_lane(s, p, -1, -1);
   if (c.args.num_local_tiles == 0) return VIMG_OK;
   if (c.lds_bytes > 48u * 1024u)
@@ -348,9 +344,8 @@ int vimg_hip_render_heatmap(VimgDeviceScene* s, const VimgRenderParams* p, float
 
 int vimg_hip_render_to_host(VimgDeviceScene* s, const VimgRenderParams* p, float* out_host,
                             VimgRenderStats* stats) {
-  int rc = check_params(s, p);
+  int rc = check_render(s, p, out_host);
   if (rc) return rc;
-  if (!out_host) return fail(VIMG_E_INVALID, "null output pointer");
   if (p->tile_world != 1) return fail(VIMG_E_INVALID, "render_to_host needs tile_world == 1");
   const size_t floats = size_t(s->d.res_x) * s->d.res_y * 3;
   if ((rc = s->frame.grow(floats * sizeof(float)))) return rc;
@@ -367,7 +362,7 @@ int vimg_hip_trace_pixel(VimgDeviceScene* s, const VimgRenderParams* p, int x, i
   if (!out_host || x < 0 || y < 0 || x >= s->d.res_x || y >= s->d.res_y)
     return fail(VIMG_E_INVALID, "trace_pixel: pixel out of range");
   if ((rc = s->frame.grow(3 * sizeof(float)))) return rc;
-  rc = enqueue_render(s, p, s->frame.as<float>(), g_stream, false, false, x, y, nullptr, nullptr, nullptr);
+  rc = enqueue_render(s, p, {.d_out = s->frame.as<float>(), .st = g_stream, .sx = x, .sy = y});
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(g_stream));
   HIP_TRY(hipMemcpy(out_host, s->frame.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
@@ -381,7 +376,7 @@ int vimg_hip_assemble_shards(const VimgDeviceScene* s, uint32_t world, int64_t s
   const uint64_t max_local = (uint64_t(tx) * ty + world - 1) / world;
   if (shard_stride_pixels < int64_t(max_local * 64))
     return fail(VIMG_E_INVALID, "assemble: shard stride smaller than the largest shard");
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_stream;
+  hipStream_t st = stream_of(stream);
   const uint32_t threads = tx * ty * 64;
   hipLaunchKernelGGL(assemble_kernel, dim3((threads + 255) / 256), dim3(256), 0, st,
                      static_cast<const float*>(d_shards), static_cast<float*>(d_out),
@@ -402,7 +397,7 @@ int vimg_hip_time_renders(VimgDeviceScene* s, const VimgRenderParams* p, void* d
     if (int rc2 = e.create()) return rc2;
   for (int i = 0; i < steps; ++i) {
     // the counter / queue resets are part of a launch's prologue; the events bracket the kernel only
-    if (int rc2 = enqueue_render(s, p, static_cast<float*>(d_out), g_stream, false, false, -1, -1, ev[2 * i].e, ev[2 * i + 1].e, nullptr))
+    if (int rc2 = enqueue_render(s, p, {.d_out = static_cast<float*>(d_out), .st = g_stream, .ev0 = ev[2 * i].e, .ev1 = ev[2 * i + 1].e}))
       return rc2;
   }
   HIP_TRY(hipStreamSynchronize(g_stream));

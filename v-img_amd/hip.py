@@ -12,6 +12,10 @@ from . import _abi as abi
 from .host import HostScene, camera_lookat, make_params
 
 
+# floats per item of DeviceScene.probe, kind -> (in, out): the n_in / n_out tables of vimg_hip_probe (csrc/vimg_hip.hip)
+PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 8: (1, 5)}
+
+
 class HipError(RuntimeError):
     pass
 
@@ -29,14 +33,22 @@ def _check(rc):
 _side = None
 
 
-class _Ordered:
-    """The stream a launch with torch tensors goes to.  `stream=None` means torch's CURRENT stream,
-    never the library's private one (which is non-blocking and would not be ordered against the
-    fill of `out` or against torch consumers of the result).  The legacy null stream has no
-    handle the library could tell from "no stream given", so work for it goes to a side stream
-    that waits for the null stream before the launch and that the null stream waits for after."""
+class _Launch:
+    """The one stream rule of the binding: the stream a call with torch tensors enqueues on, and what
+    orders its tensors against it.  ``stream=None`` means torch's CURRENT stream, never the library's private one
+    (which is non-blocking and would not be ordered against the fill of `out` or against torch consumers of the
+    result).  The legacy null stream has no handle the library could tell from "no stream given", so work for it
+    goes to a side stream that waits for the null stream before the launch and that the null stream waits for after.
 
-    def __init__(self, stream):
+    ``made``: the tensors this call allocated or copied up from numpy, ``used``: the caller's.  Both kinds were
+    made on torch's current stream, so a launch on another stream first waits for the current one when there are
+    ``made`` tensors (it neither reads a copy not yet made nor writes memory the caching allocator handed out while
+    current-stream work on it is still pending), and afterwards records every tensor on the stream that ran it:
+    the allocator must not hand their memory out again before that stream has passed the launch.  ``to_host``:
+    the results go back to numpy on the current stream, which waits for the launch first.  On the current stream
+    itself none of this is needed, and nothing is done."""
+
+    def __init__(self, stream, made=(), used=(), to_host=False):
         import torch
         global _side
         self.cur = stream if stream is not None else torch.cuda.current_stream()
@@ -45,8 +57,15 @@ class _Ordered:
             if _side is None:
                 _side = torch.cuda.Stream()
             self.side = _side
+        self.home = None       # torch's current stream, when the launch goes to another one
+        if stream is not None and (made or used):
+            home = torch.cuda.current_stream()
+            if home.cuda_stream != stream.cuda_stream:
+                self.home, self.made, self.used, self.to_host = home, made, used, to_host
 
     def __enter__(self):
+        if self.home is not None and self.made:
+            self.cur.wait_stream(self.home)
         if self.side is not None:
             self.side.wait_stream(self.cur)
             return C.c_void_p(self.side.cuda_stream)
@@ -55,7 +74,70 @@ class _Ordered:
     def __exit__(self, *exc):
         if self.side is not None:
             self.cur.wait_stream(self.side)
+        if self.home is not None:
+            ran = self.side if self.side is not None else self.cur
+            for t in (*self.made, *self.used):
+                if t is not None and t.numel():
+                    t.record_stream(ran)
+            if self.to_host:
+                self.home.wait_stream(self.cur)
         return False
+
+
+def _upload(a):
+    """A numpy array's device copy (a blocking copy on torch's current stream)."""
+    import torch
+    return torch.from_numpy(a).to("cuda")
+
+
+def _device_tensor(a, what, dtypes, shape, aligned=False, out=False):
+    """(device tensor, came from numpy) for an argument of a launch: a CUDA tensor on the current device as it is,
+    a numpy array copied up (a bool one viewed as uint8).  ``dtypes``: the names allowed ("float32", ...);
+    ``shape``: None leaves a dimension open (the N of [N, 8]); ``aligned``: the data must be 16-byte aligned.
+    Type, dtype and a numpy array's shape are checked before anything is copied.  ``out``: a caller's output
+    buffer - a tensor of exactly dtypes[0] and ``shape``, refused in one sentence."""
+    import torch
+    said = str(tuple("N" if d is None else d for d in shape)).replace("'", "")
+
+    def bad(why):
+        if out:
+            why = f"out must be a contiguous torch.{dtypes[0]} CUDA tensor of shape {said} on the current device"
+        return ValueError(f"{what}: {why}")
+
+    def fits(got):
+        return len(got) == len(shape) and all(w is None or w == g for w, g in zip(shape, got))
+
+    if isinstance(a, np.ndarray) and not out:
+        if a.dtype.name not in dtypes:
+            raise bad(f"dtype must be {' or '.join(dtypes)}, not {a.dtype}")
+        if not fits(a.shape):
+            raise bad(f"shape must be {said}, not {tuple(a.shape)}")
+        a = np.ascontiguousarray(a)
+        t, host = _upload(a.view(np.uint8) if a.dtype == np.bool_ else a), True
+    elif isinstance(a, torch.Tensor):
+        if str(a.dtype)[len("torch."):] not in (dtypes[:1] if out else dtypes):
+            raise bad(f"dtype must be {' or '.join(dtypes)}, not {a.dtype}")
+        if not a.is_cuda or a.device.index != torch.cuda.current_device():
+            raise bad(f"the tensor must be on the current CUDA device, not {a.device}")
+        if not a.is_contiguous():
+            raise bad("the tensor must be contiguous")
+        if not fits(a.shape):
+            raise bad(f"shape must be {said}, not {tuple(a.shape)}")
+        t, host = a, False
+    else:
+        raise bad(f"expected a torch CUDA tensor or a numpy array, not {type(a).__name__}")
+    if aligned and t.numel() and t.data_ptr() % 16:
+        raise ValueError(f"{what}: out must be 16-byte aligned" if out else f"{what}: the tensor's data must be 16-byte aligned")
+    return t, host
+
+
+def _owned(out, fresh, *used):
+    """made / used of the _Launch of a call that allocated its output `out` itself (`fresh`) or was given it."""
+    return dict(made=[out], used=used) if fresh else dict(made=(), used=(out, *used))
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
 def device_count():
@@ -107,57 +189,30 @@ class DeviceScene:
 
         tile_world == 1: returns [H, W, 3] in the reference layout (row 0 = top).
         tile_world  > 1: returns the shard's compact [shard_pixels, 3] buffer."""
-        import torch
-        w, h = self.resolution
-        if out is None:
-            if params.tile_world == 1:
-                out = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
-            else:
-                out = torch.zeros((self.shard_pixels(params), 3), dtype=torch.float32,
-                                  device="cuda")
+        fresh = out is None
+        if fresh:
+            out = self._new_output(params)
         st = abi.RenderStats()
-        with _Ordered(stream) as sp:
+        with _Launch(stream, **_owned(out, fresh)) as sp:
             _check(self._lib.vimg_hip_render(self._h, C.byref(params), C.c_void_p(out.data_ptr()), sp,
                                              C.byref(st) if stats else None))
         return (out, st) if stats else out
 
-    def _device_table(self, a, rows, cols, what, keep):
-        """A float32 [rows, cols] table on this process's GPU: a CUDA tensor as it is, a numpy array copied up."""
+    def _new_output(self, params, zero_slab=True):
+        """A frame [H, W, 3] for these parameters, or the shard's compact slab [shard_pixels, 3] when tile_world > 1
+        (zeroed, when asked: a ragged shard has slots off the image that no launch writes)."""
         import torch
-        if isinstance(a, torch.Tensor):
-            if not a.is_cuda or a.device.index != torch.cuda.current_device():
-                raise ValueError(f"{what}: the tensor must be on the current CUDA device, not {a.device}")
-            if a.dtype != torch.float32:
-                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
-            if not a.is_contiguous():
-                raise ValueError(f"{what}: the tensor must be contiguous")
-            t = a
-        elif isinstance(a, np.ndarray):
-            if a.dtype != np.float32:
-                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
-            t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda")   # (a blocking copy: done before the update reads it)
-        else:
-            raise ValueError(f"{what}: expected a torch CUDA tensor or a numpy array, not {type(a).__name__}")
-        if tuple(t.shape) != (rows, cols):
-            raise ValueError(f"{what}: shape must be ({rows}, {cols}), not {tuple(t.shape)}")
-        keep.append(t)
-        return C.c_void_p(t.data_ptr()) if t.numel() else None
+        w, h = self.resolution
+        if params.tile_world == 1:
+            return torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        return (torch.zeros if zero_slab else torch.empty)((self.shard_pixels(params), 3), dtype=torch.float32, device="cuda")
 
     def update_geometry(self, vertices=None, normals=None, spheres=None, stream=None):
         """New positions for the resident scene (vimg_hip_scene_update_geometry): vertices and normals
         [num_vertices, 3], spheres [num_spheres, 4] (centre, radius), float32; None = unchanged.  The records
         baked from positions and the tree's boxes are rebuilt on the GPU; the call returns when the scene is
         consistent.  Progressive accumulators of the scene must be reset afterwards."""
-        keep = []          # (the tensors stay alive until the blocking call returns)
-        upd = abi.GeometryUpdate()
-        if vertices is not None:
-            upd.vertices = self._device_table(vertices, self.num_vertices, 3, "vertices", keep)
-        if normals is not None:
-            upd.normals = self._device_table(normals, self.num_vertices, 3, "normals", keep)
-        if spheres is not None:
-            upd.spheres = self._device_table(spheres, self.num_spheres, 4, "spheres", keep)
-        with _Ordered(stream) as sp:
-            _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
+        self.update_materials(vertices=vertices, normals=normals, spheres=spheres, stream=stream)
 
     @staticmethod
     def _record_table(records, n, ctype, what):
@@ -168,7 +223,7 @@ class DeviceScene:
             return records
         return (ctype * max(n, 1))(*records)
 
-    def _fill_material_update(self, upd, keep, materials, textures, lights, background, images):
+    def _fill_material_update(self, upd, table, keep, materials, textures, lights, background, images):
         if materials is not None:
             arr = self._record_table(materials, self.num_materials, abi.Material, "materials")
             keep.append(arr)
@@ -193,8 +248,7 @@ class DeviceScene:
                     raise ValueError(f"images: texture {tex} is not an image texture of the scene")
                 h, w = self._image_sizes[tex]
                 arr[k].texture = int(tex)
-                arr[k].level0 = self._device_table(img.reshape(-1, 3) if tuple(img.shape) == (h, w, 3) else img, h * w, 3,
-                                                   f"images[{tex}]", keep)
+                arr[k].level0 = table(img.reshape(-1, 3) if tuple(img.shape) == (h, w, 3) else img, h * w, 3, f"images[{tex}]")
             keep.append(arr)
             upd.images = C.cast(arr, C.POINTER(abi.TextureImage))
             upd.num_images = len(images)
@@ -209,16 +263,20 @@ class DeviceScene:
         CUDA tensor is read where it is, a numpy array is copied up - whose mip chains (and, for the env map, sampling
         CDFs) are rebuilt on the GPU.  Positions (as for update_geometry) may ride in the same call.  Afterwards the
         scene is the upload of the host scene edited the same way; progressive accumulators must be reset."""
-        keep = []
         upd = abi.GeometryUpdate()
-        if vertices is not None:
-            upd.vertices = self._device_table(vertices, self.num_vertices, 3, "vertices", keep)
-        if normals is not None:
-            upd.normals = self._device_table(normals, self.num_vertices, 3, "normals", keep)
-        if spheres is not None:
-            upd.spheres = self._device_table(spheres, self.num_spheres, 4, "spheres", keep)
-        self._fill_material_update(upd, keep, materials, textures, lights, background, images)
-        with _Ordered(stream) as sp:
+        made, used, keep = [], [], []     # device copies of numpy tables, the caller's tensors, the ctypes tables
+
+        def table(a, rows, cols, what):
+            t, host = _device_tensor(a, what, ("float32",), (rows, cols))
+            (made if host else used).append(t)
+            return _ptr(t)
+
+        for name, a, rows, cols in (("vertices", vertices, self.num_vertices, 3), ("normals", normals, self.num_vertices, 3),
+                                    ("spheres", spheres, self.num_spheres, 4)):
+            if a is not None:
+                setattr(upd, name, table(a, rows, cols, name))
+        self._fill_material_update(upd, table, keep, materials, textures, lights, background, images)
+        with _Launch(stream, made, used) as sp:     # (blocking: the tables stay alive until it returns)
             _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
 
     def update_from(self, host_scene, stream=None):
@@ -236,14 +294,14 @@ class DeviceScene:
         if builder not in abi.BUILDERS:
             raise ValueError(f"builder: expected one of {sorted(abi.BUILDERS)}, not {builder!r}")
         opts = abi.RebuildOptions(builder=abi.BUILDERS[builder])
-        with _Ordered(stream) as sp:
+        with _Launch(stream) as sp:
             _check(self._lib.vimg_hip_scene_rebuild_bvh(self._h, C.byref(opts), sp))
 
     def bvh_cost(self, stream=None):
         """Surface-area cost of the scene's tree under the reference's model (vimg_hip_scene_bvh_cost): it rises
         when update_geometry stretches the tree over moved geometry; rebuild_bvh brings it back."""
         cost = C.c_double()
-        with _Ordered(stream) as sp:
+        with _Launch(stream) as sp:
             _check(self._lib.vimg_hip_scene_bvh_cost(self._h, sp, C.byref(cost)))
         return float(cost.value)
 
@@ -258,68 +316,21 @@ class DeviceScene:
         _check(self._lib.vimg_hip_scene_set_camera(self._h, C.byref(cam)))
 
     # ---- ray queries (vimg_hip_trace_rays, _occluded, _camera_rays) ----------------------------------
-    def _query_input(self, a, cols, what):
-        """(device tensor [N, cols] float32, came from numpy): a CUDA tensor on the current device as it is, a numpy
-        array copied up; both 16-byte aligned."""
-        import torch
-        if isinstance(a, torch.Tensor):
-            if not a.is_cuda or a.device.index != torch.cuda.current_device():
-                raise ValueError(f"{what}: the tensor must be on the current CUDA device, not {a.device}")
-            if a.dtype != torch.float32:
-                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
-            if not a.is_contiguous():
-                raise ValueError(f"{what}: the tensor must be contiguous")
-            t, host = a, False
-        elif isinstance(a, np.ndarray):
-            if a.dtype != np.float32:
-                raise ValueError(f"{what}: dtype must be float32, not {a.dtype}")
-            t, host = torch.from_numpy(np.ascontiguousarray(a)).to("cuda"), True
-        else:
-            raise ValueError(f"{what}: expected a torch CUDA tensor or a numpy array, not {type(a).__name__}")
-        if t.dim() != 2 or t.shape[1] != cols:
-            raise ValueError(f"{what}: shape must be (N, {cols}), not {tuple(t.shape)}")
-        if t.numel() and t.data_ptr() % 16:
-            raise ValueError(f"{what}: the tensor's data must be 16-byte aligned")
-        return t, host
+    @staticmethod
+    def _query_io(a, cols, what):
+        """The [N, cols] float32 input of a query, 16-byte aligned: (tensor, N, came from numpy, made, used) - the
+        last two are the lists of the call's _Launch, which _query_output adds the outputs to."""
+        t, host = _device_tensor(a, what, ("float32",), (None, cols), aligned=True)
+        return (t, t.shape[0], host) + (([t], []) if host else ([], [t]))
 
     @staticmethod
-    def _query_output(out, n, cols, dtype, what):
+    def _query_output(out, shape, dtype, what, made, used):
         import torch
         if out is None:
-            return torch.empty((n, cols) if cols else (n,), dtype=dtype, device="cuda")
-        shape = (n, cols) if cols else (n,)
-        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != torch.cuda.current_device()
-                or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous()):
-            raise ValueError(f"{what}: out must be a contiguous {dtype} CUDA tensor of shape {shape} on the current device")
-        if n and cols and out.data_ptr() % 16:
-            raise ValueError(f"{what}: out must be 16-byte aligned")
+            made.append(torch.empty(shape, dtype=getattr(torch, dtype), device="cuda"))
+            return made[-1]
+        used.append(_device_tensor(out, what, (dtype,), shape, aligned=len(shape) > 1, out=True)[0])
         return out
-
-    @staticmethod
-    def _query_stream(stream):
-        """The _Ordered of a query launch.  Its outputs, and the copies of numpy inputs, were made on torch's current
-        stream: a launch on another stream first waits for the current one, so that it neither reads a copy not yet
-        made nor writes memory the caching allocator handed out while current-stream work on it is still pending."""
-        import torch
-        ordered = _Ordered(stream)
-        cur = torch.cuda.current_stream()
-        if ordered.side is None and ordered.cur.cuda_stream != cur.cuda_stream:
-            ordered.cur.wait_stream(cur)
-        return ordered
-
-    @staticmethod
-    def _after_query(ordered, tensors, host):
-        """A launch on another stream than torch's current one reads and writes its tensors asynchronously: the
-        caching allocator must not hand their memory out again before that stream has passed the launch.  Results
-        that go back to numpy wait for the launch first."""
-        import torch
-        used = ordered.side if ordered.side is not None else ordered.cur
-        if used.cuda_stream != torch.cuda.current_stream().cuda_stream:
-            for t in tensors:
-                if t is not None and t.numel():
-                    t.record_stream(used)
-            if host:
-                torch.cuda.current_stream().wait_stream(used)
 
     def trace_rays(self, rays, info=False, out=None, stream=None):
         """Closest hits of ``rays`` ([N, 8] float32 laid out as VimgRay: org xyz, t_min, dir xyz, t_max) against the
@@ -328,18 +339,12 @@ class DeviceScene:
         uv [N, 2], mat [N] int32.  A CUDA tensor is used as it is and the results are views of device buffers,
         ordered on ``stream`` (torch's current one by default); a numpy array is copied up and numpy arrays come
         back.  ``out``: the [N, 4] float32 hit buffer, or (hits, [N, 12] info buffer) with ``info``."""
-        import torch
-        r, host = self._query_input(rays, 8, "rays")
-        n = r.shape[0]
+        r, n, host, made, used = self._query_io(rays, 8, "rays")
         hits_out, info_out = (out if info and out is not None else (out, None))
-        hits = self._query_output(hits_out, n, 4, torch.float32, "trace_rays")
-        rec = self._query_output(info_out, n, 12, torch.float32, "trace_rays info") if info else None
-        ordered = self._query_stream(stream)
-        with ordered as sp:
-            _check(self._lib.vimg_hip_trace_rays(self._h, C.c_void_p(r.data_ptr()) if n else None, n,
-                                                 C.c_void_p(hits.data_ptr()) if n else None,
-                                                 C.c_void_p(rec.data_ptr()) if rec is not None and n else None, sp))
-        self._after_query(ordered, (r, hits, rec), host)
+        hits = self._query_output(hits_out, (n, 4), "float32", "trace_rays", made, used)
+        rec = self._query_output(info_out, (n, 12), "float32", "trace_rays info", made, used) if info else None
+        with _Launch(stream, made, used, to_host=host) as sp:
+            _check(self._lib.vimg_hip_trace_rays(self._h, _ptr(r), n, _ptr(hits), _ptr(rec), sp))
         return RayHits.of(hits, rec, host)
 
     def occluded(self, rays, out=None, stream=None):
@@ -347,14 +352,10 @@ class DeviceScene:
         anything lies in [t_min, t_max].  CUDA tensor in, CUDA tensor out (a view of ``out``, [N] uint8, when
         given); numpy in, numpy out."""
         import torch
-        r, host = self._query_input(rays, 8, "rays")
-        n = r.shape[0]
-        flags = self._query_output(out, n, 0, torch.uint8, "occluded")
-        ordered = self._query_stream(stream)
-        with ordered as sp:
-            _check(self._lib.vimg_hip_occluded(self._h, C.c_void_p(r.data_ptr()) if n else None, n,
-                                               C.c_void_p(flags.data_ptr()) if n else None, sp))
-        self._after_query(ordered, (r, flags), host)
+        r, n, host, made, used = self._query_io(rays, 8, "rays")
+        flags = self._query_output(out, (n,), "uint8", "occluded", made, used)
+        with _Launch(stream, made, used, to_host=host) as sp:
+            _check(self._lib.vimg_hip_occluded(self._h, _ptr(r), n, _ptr(flags), sp))
         res = flags.view(torch.bool)
         return res.cpu().numpy() if host else res
 
@@ -362,15 +363,10 @@ class DeviceScene:
         """The camera's rays (vimg_hip_camera_rays) for ``samples`` [N, 4] float32 {x, y, lens_u, lens_v} (pixel
         coordinates, lens samples): [N, 8] float32 VimgRay records with t_min 1e-4 and t_max +inf - the input of
         trace_rays for picking.  CUDA tensor in, CUDA tensor out; numpy in, numpy out."""
-        import torch
-        smp, host = self._query_input(samples, 4, "samples")
-        n = smp.shape[0]
-        rays = self._query_output(out, n, 8, torch.float32, "camera_rays")
-        ordered = self._query_stream(stream)
-        with ordered as sp:
-            _check(self._lib.vimg_hip_camera_rays(self._h, C.c_void_p(smp.data_ptr()) if n else None, n,
-                                                  C.c_void_p(rays.data_ptr()) if n else None, sp))
-        self._after_query(ordered, (smp, rays), host)
+        smp, n, host, made, used = self._query_io(samples, 4, "samples")
+        rays = self._query_output(out, (n, 8), "float32", "camera_rays", made, used)
+        with _Launch(stream, made, used, to_host=host) as sp:
+            _check(self._lib.vimg_hip_camera_rays(self._h, _ptr(smp), n, _ptr(rays), sp))
         return rays.cpu().numpy() if host else rays
 
     def progressive(self, params):
@@ -380,7 +376,7 @@ class DeviceScene:
         return Progressive(self, params)
 
     def render_async(self, params, out, stream=None):
-        with _Ordered(stream) as sp:
+        with _Launch(stream, used=[out]) as sp:
             _check(self._lib.vimg_hip_render_async(self._h, C.byref(params),
                                                    C.c_void_p(out.data_ptr()), sp))
 
@@ -402,14 +398,10 @@ class DeviceScene:
     def render_heatmap(self, params, factor=-1.0, out=None, stream=None):
         """BVH traversal-cost picture (reference heatmap_img) into a torch CUDA tensor [H, W, 3]
         (or the compact shard slab when params.tile_world > 1)."""
-        import torch
-        w, h = self.resolution
-        if out is None:
-            n = w * h if params.tile_world == 1 else self.shard_pixels(params)
-            out = torch.empty((n, 3), dtype=torch.float32, device="cuda")
-            if params.tile_world == 1:
-                out = out.view(h, w, 3)
-        with _Ordered(stream) as sp:
+        fresh = out is None
+        if fresh:
+            out = self._new_output(params, zero_slab=False)
+        with _Launch(stream, **_owned(out, fresh)) as sp:
             _check(self._lib.vimg_hip_render_heatmap(self._h, C.byref(params), factor,
                                                      C.c_void_p(out.data_ptr()), sp))
         return out
@@ -423,9 +415,10 @@ class DeviceScene:
     def assemble_shards(self, gathered, world, shard_stride_pixels, out=None, stream=None):
         import torch
         w, h = self.resolution
-        if out is None:
+        fresh = out is None
+        if fresh:
             out = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
-        with _Ordered(stream) as sp:
+        with _Launch(stream, **_owned(out, fresh, gathered)) as sp:
             _check(self._lib.vimg_hip_assemble_shards(self._h, world, shard_stride_pixels,
                                                       C.c_void_p(gathered.data_ptr()),
                                                       C.c_void_p(out.data_ptr()), sp))
@@ -440,15 +433,10 @@ class DeviceScene:
 
     def probe(self, kind, inputs):
         """Unit-level test hook (vimg_hip_probe): per item n_in floats in, n_out floats out."""
-        n_io = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 8: (1, 5)}
-        fn = self._lib.vimg_hip_probe
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, abi.Pf32, abi.Pf32]
-        n_in, n_out = n_io[kind]
+        n_in, n_out = PROBE_IO[kind]
         a = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, n_in)
         out = np.zeros((a.shape[0], n_out), dtype=np.float32)
-        _check(fn(self._h, kind, a.shape[0], a.ctypes.data_as(abi.Pf32),
-                  out.ctypes.data_as(abi.Pf32)))
+        _check(self._lib.vimg_hip_probe(self._h, kind, a.shape[0], a.ctypes.data_as(abi.Pf32), out.ctypes.data_as(abi.Pf32)))
         return out
 
     def close(self):
@@ -523,32 +511,6 @@ class Progressive:
         w, ht = self._dev.resolution
         return (ht, w) if self.params.tile_world == 1 else (self._dev.shard_pixels(self.params),)
 
-    def _new_image(self):
-        import torch
-        if self.params.tile_world == 1:
-            return torch.empty(self.pixel_shape + (3,), dtype=torch.float32, device="cuda")
-        return torch.zeros(self.pixel_shape + (3,), dtype=torch.float32, device="cuda")
-
-    def _device_mask(self, mask):
-        """A uint8 (or bool) per-pixel mask on this process's GPU: a CUDA tensor as it is, a numpy array copied up."""
-        import torch
-        if isinstance(mask, np.ndarray):
-            if mask.dtype not in (np.uint8, np.bool_):
-                raise ValueError(f"mask: dtype must be uint8 or bool, not {mask.dtype}")
-            mask = torch.from_numpy(np.ascontiguousarray(mask).view(np.uint8)).to("cuda")
-        elif isinstance(mask, torch.Tensor):
-            if not mask.is_cuda or mask.device.index != torch.cuda.current_device():
-                raise ValueError(f"mask: the tensor must be on the current CUDA device, not {mask.device}")
-            if mask.dtype not in (torch.uint8, torch.bool):
-                raise ValueError(f"mask: dtype must be uint8 or bool, not {mask.dtype}")
-            if not mask.is_contiguous():
-                raise ValueError("mask: the tensor must be contiguous")
-        else:
-            raise ValueError(f"mask: expected a torch CUDA tensor or a numpy array, not {type(mask).__name__}")
-        if tuple(mask.shape) != self.pixel_shape:
-            raise ValueError(f"mask: shape must be {self.pixel_shape}, not {tuple(mask.shape)}")
-        return mask
-
     def render(self, samples, out=None, stats=False, stream=None, mask=None):
         """Adds `samples` samples per pixel and returns the running mean in ``DeviceScene.render``'s shapes
         ([H, W, 3], or the shard's compact [shard_pixels, 3] when tile_world > 1), with this increment's
@@ -557,14 +519,18 @@ class Progressive:
         non-zero get the samples (vimg_hip_progressive_render_masked); every pixel's mean is returned, each
         bit for bit ``DeviceScene.render`` at that pixel's own count."""
         h = self._handle()
-        if out is None:
-            out = self._new_image()
-        ptr = None if out is False else C.c_void_p(out.data_ptr())
+        fresh = out is None
+        if fresh:
+            out = self._dev._new_output(self.params)
+        made, used = ([out], []) if fresh else ([], [] if out is False else [out])
+        if mask is not None:
+            m, host = _device_tensor(mask, "mask", ("uint8", "bool"), self.pixel_shape)
+            (made if host else used).append(m)
         st = abi.RenderStats()
-        m = None if mask is None else self._device_mask(mask)
-        with _Ordered(stream) as sp:
+        with _Launch(stream, made, used) as sp:
             _check(self._lib.vimg_hip_progressive_render_masked(self._dev._h, h, int(samples),
-                                                                None if m is None else C.c_void_p(m.data_ptr()), ptr, sp,
+                                                                None if mask is None else C.c_void_p(m.data_ptr()),
+                                                                None if out is False else C.c_void_p(out.data_ptr()), sp,
                                                                 C.byref(st) if stats else None))
         img = None if out is False else out
         return (img, st) if stats else img
@@ -574,27 +540,26 @@ class Progressive:
         ``sum`` [.., 3] float32 (running sums), ``count`` int64 N, ``batches`` int64 K (increments the pixel
         took part in; both are uint32 in the library, widened here because torch has no such type) and ``m2``
         float32."""
+        return self._read_state(("sum", "count", "batches", "m2"), stream)
+
+    def _read_state(self, fields, stream):
+        """The `fields` of the pixel records, one launch of vimg_hip_progressive_state; the two uint32 ones widened."""
         import torch
         h = self._handle()
         shp = self.pixel_shape
-        t = dict(sum=torch.zeros(shp + (3,), dtype=torch.float32, device="cuda"),
-                 count=torch.zeros(shp, dtype=torch.int32, device="cuda"),
-                 batches=torch.zeros(shp, dtype=torch.int32, device="cuda"),
-                 m2=torch.zeros(shp, dtype=torch.float32, device="cuda"))
-        with _Ordered(stream) as sp:
-            _check(self._lib.vimg_hip_progressive_state(h, *(C.c_void_p(t[k].data_ptr()) for k in ("sum", "count", "batches", "m2")), sp))
-        for k in ("count", "batches"):
-            t[k] = t[k].to(torch.int64) & 0xFFFFFFFF
+        t = {k: torch.zeros(shp + ((3,) if k == "sum" else ()), dtype=torch.float32 if k in ("sum", "m2") else torch.int32,
+                            device="cuda") for k in fields}
+        launch = _Launch(stream, made=list(t.values()))
+        with launch as sp:
+            _check(self._lib.vimg_hip_progressive_state(h, *(_ptr(t.get(k)) for k in ("sum", "count", "batches", "m2")), sp))
+        with torch.cuda.stream(launch.cur if launch.home is not None else None):   # (the launch only enqueues: widen where it runs)
+            for k in t.keys() & {"count", "batches"}:
+                t[k] = t[k].to(torch.int64) & 0xFFFFFFFF
         return t
 
     def counts(self, stream=None):
         """Samples each pixel has had: int64 CUDA tensor in ``pixel_shape`` (uint32 in the library)."""
-        import torch
-        h = self._handle()
-        n = torch.zeros(self.pixel_shape, dtype=torch.int32, device="cuda")
-        with _Ordered(stream) as sp:
-            _check(self._lib.vimg_hip_progressive_state(h, None, C.c_void_p(n.data_ptr()), None, None, sp))
-        return n.to(torch.int64) & 0xFFFFFFFF
+        return self._read_state(("count",), stream)["count"]
 
     def error(self, stream=None):
         """Estimated relative standard error of each pixel's mean luminance (vimg_hip_progressive_error): float32
@@ -602,7 +567,7 @@ class Progressive:
         import torch
         h = self._handle()
         e = torch.zeros(self.pixel_shape, dtype=torch.float32, device="cuda")
-        with _Ordered(stream) as sp:
+        with _Launch(stream, made=[e]) as sp:
             _check(self._lib.vimg_hip_progressive_error(h, C.c_void_p(e.data_ptr()), sp))
         return e
 
@@ -612,12 +577,13 @@ class Progressive:
         (vimg_hip_progressive_select)."""
         import torch
         h = self._handle()
-        if out is None:
+        fresh = out is None
+        if fresh:
             out = torch.zeros(self.pixel_shape, dtype=torch.uint8, device="cuda")
         else:
-            out = self._device_mask(out)
+            out, fresh = _device_tensor(out, "mask", ("uint8", "bool"), self.pixel_shape)
         n = abi.u32(0)
-        with _Ordered(stream) as sp:
+        with _Launch(stream, **_owned(out, fresh)) as sp:
             _check(self._lib.vimg_hip_progressive_select(h, float(target), int(max_samples), C.c_void_p(out.data_ptr()), sp,
                                                          C.byref(n)))
         return out, int(n.value)
@@ -637,7 +603,7 @@ class Progressive:
         if not target >= 0:
             raise ValueError("render_adaptive: target must be >= 0")
         if out is None:
-            out = self._new_image()
+            out = self._dev._new_output(self.params)
         wrote = False
         while self.samples < min_samples:
             self.render(step, out=out, stream=stream)
@@ -660,7 +626,7 @@ class Progressive:
     def reset(self, stream=None):
         """Back to 0 samples: the next increment seeds every pixel again."""
         h = self._handle()
-        with _Ordered(stream):
+        with _Launch(stream):
             _check(self._lib.vimg_hip_progressive_reset(h))
 
     def close(self):
@@ -681,7 +647,7 @@ def post_rgb8(image, tonemapper=1, stream=None):
     import torch
     h, w = image.shape[0], image.shape[1]
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=image.device)
-    with _Ordered(stream) as sp:
+    with _Launch(stream, made=[out], used=[image]) as sp:
         _check(_lib().vimg_hip_post_rgb8(C.c_void_p(image.data_ptr()), w, h, tonemapper,
                                          C.c_void_p(out.data_ptr()), sp))
     return out
