@@ -46,6 +46,10 @@ $(OBJDIR)/%.o: v-img_amd/csrc/%.hip $(HIPHDR) Makefile
 # pass, 80 / 72 without (tools/kres.sh)
 $(OBJDIR)/k_cu.o $(OBJDIR)/k_cu_early.o $(OBJDIR)/k_cu_diag.o $(OBJDIR)/k_cu_plain.o $(OBJDIR)/k_cu_plain_early.o: \
     HIPCFLAGS += -mllvm -disable-machine-licm
+# feature_kernel: the same pass hoists the constants of generate_ray, the hit record and the texture lookup in
+# front of the sample loop: 201 / 182 registers (TEX / not) and two waves per SIMD with it, 99 / 84 and four /
+# five without, no scratch either way
+$(OBJDIR)/k_feature.o: HIPCFLAGS += -mllvm -disable-machine-licm
 $(LIBDIR)/libvimg_hip.so: $(HIPOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIPOBJ) -o $@

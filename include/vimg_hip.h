@@ -228,7 +228,31 @@ int64_t vimg_hip_shard_pixels(const VimgDeviceScene* scene, const VimgRenderPara
  * Limit of one launch: the rings of a compute unit count the rays it queues in 32 bits - about 2^31 per
  * launch, i.e. the whole 1800x800 frame of disney_spheres up to ~60 000 samples per pixel (the reference's
  * scenes ask for 512-2048); beyond it the launch ends with VIMG_E_DEVICE and says so.  More samples than
- * that: render the frame progressively (below), where the limit holds per increment. */
+ * that: render the frame progressively (below), where the limit holds per increment.
+ *
+ * The first-hit feature integrators VIMG_INTEGRATOR_ALBEDO .. _COVERAGE (include/vimg_scene.h) render what a
+ * denoiser or compositor needs beside the image, through this and every other entry point that takes
+ * VimgRenderParams (render_async, render_to_host, trace_pixel, shards, the progressive calls, masked or not).
+ * Their samples are the normal integrators': the pixel's PCG stream seeded with the image index, the jitter
+ * random_x_y_r2(px + py + k), the lens draws, one closest-hit walk of the camera ray over [1e-4, inf) - the rays
+ * of s_normal, and of _camera_rays + _trace_rays given the same samples.  A pixel is the float32 sum of its
+ * samples' values in sample order, divided once by float(samples); a miss contributes 0 0 0.  On a hit:
+ *   ALBEDO    the material's base colour at the hit:
+ *               Lambertian, Principled  their colour texture (VimgMaterial.tex) evaluated as the MIS integrator's
+ *                                       first vertex evaluates it: col_at_ray_hit with the primary ray's direction
+ *                                       and the cone {width |spread * distance|, angle spread + 2 * surface spread}
+ *                                       the camera's cone {0, pixel spread} becomes at the hit (mip level of image
+ *                                       textures; constant and checkerboard textures do not read it)
+ *               Dielectric              1 1 1
+ *               DiffuseLight            its emission colour (VimgMaterial.emit), whichever side is seen
+ *   NORMAL    the shading normal as it is (VimgHitInfo.ns: normal-mapped where the material has a map), not (n+1)/2
+ *   DEPTH     t t t, the distance along the camera ray (VimgRayHit.t)
+ *   POSITION  the hit point (VimgHitInfo.p)
+ *   UV        u v 0 (VimgHitInfo.uv: the colour texture's set, barycentrics on a mesh without one)
+ *   COVERAGE  1 1 1
+ * `depth` is not read, a scene without lights is accepted, and VimgHipOptions.scheduler is not read: these
+ * integrators have one kernel (vimg_hip_launch_kernel names it).  Statistics: paths = closest_rays = pixels x
+ * samples, shadow_rays = 0, and the traversal counts of an s_normal launch of the same frame. */
 int vimg_hip_render(VimgDeviceScene* scene, const VimgRenderParams* params, void* d_out_rgb,
                     void* stream, VimgRenderStats* stats);
 

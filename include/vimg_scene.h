@@ -28,7 +28,11 @@ extern "C" {
 
 /* integrator_func, reference include/integrators.h:24 (heatmap is not on the path) */
 enum { VIMG_INTEGRATOR_S_NORMAL = 0, VIMG_INTEGRATOR_G_NORMAL = 1, VIMG_INTEGRATOR_MATERIAL = 2,
-       VIMG_INTEGRATOR_MIS = 3 };
+       VIMG_INTEGRATOR_MIS = 3,
+       /* first-hit feature integrators of libvimg_hip.so (include/vimg_hip.h, beside vimg_hip_render): not the
+        * reference's, and not read from scene files */
+       VIMG_INTEGRATOR_ALBEDO = 4, VIMG_INTEGRATOR_NORMAL = 5, VIMG_INTEGRATOR_DEPTH = 6,
+       VIMG_INTEGRATOR_POSITION = 7, VIMG_INTEGRATOR_UV = 8, VIMG_INTEGRATOR_COVERAGE = 9 };
 
 /* Surface subclasses, reference include/geometry/{triangle,sphere}.h */
 enum { VIMG_PRIM_TRIANGLE = 0, VIMG_PRIM_SPHERE = 1 };

@@ -16,7 +16,11 @@ MAX_UV_SETS = 4
 MAX_MIP_LEVELS = 15
 
 INTEGRATOR_S_NORMAL, INTEGRATOR_G_NORMAL, INTEGRATOR_MATERIAL, INTEGRATOR_MIS = 0, 1, 2, 3
-INTEGRATORS = {"s_normal": 0, "g_normal": 1, "material": 2, "mis": 3}
+INTEGRATOR_ALBEDO, INTEGRATOR_NORMAL, INTEGRATOR_DEPTH, INTEGRATOR_POSITION, INTEGRATOR_UV, INTEGRATOR_COVERAGE = 4, 5, 6, 7, 8, 9
+INTEGRATORS = {"s_normal": 0, "g_normal": 1, "material": 2, "mis": 3,
+               # first-hit feature integrators of the HIP library (include/vimg_hip.h, beside vimg_hip_render)
+               "albedo": 4, "normal": 5, "depth": 6, "position": 7, "uv": 8, "coverage": 9}
+FEATURES = ("albedo", "normal", "depth", "position", "uv", "coverage")
 PRIM_TRIANGLE, PRIM_SPHERE = 0, 1
 MAT_LAMBERTIAN, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_PRINCIPLED = 0, 1, 2, 3
 TEX_CONST, TEX_CHECKER, TEX_IMAGE = 0, 1, 2

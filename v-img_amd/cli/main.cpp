@@ -5,7 +5,9 @@
 // -m factor heatmap mode (BVH traversal cost, main.cpp:62-65,98-100,250-256), plus
 // -s spp override, -p step progressive rendering (increments of `step` samples, the PNG rewritten
 // after each; the last one is byte-identical to a plain run), -e target adaptive sampling on top of -p (increments
-// only where the estimated relative error of a pixel is above `target`, -s the cap per pixel) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
+// only where the estimated relative error of a pixel is above `target`, -s the cap per pixel), -a prefix (the feature
+// buffers of the frame beside the image: prefix_albedo.png, prefix_normal.png as (n + 1) / 2, prefix_depth.png
+// divided by the image's largest depth, all through the clamp tonemapper) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
 // here on the host (libvimg_host); the render and the post chain go through the C ABI of
 // libvimg_hip.
 #include <algorithm>
@@ -26,7 +28,7 @@ static double now_s() {
 }
 
 int main(int argc, char** argv) {
-  std::string scene_path, out_path = "v_img_amd.png";
+  std::string scene_path, out_path = "v_img_amd.png", aux_prefix;
   int tonemapper = 0, bvh_type = VIMG_BVH_BINNED, px = -1, py = -1;   // clamp, as src/main.cpp:46
   long spp_override = -1, prog_step = 0;
   float heatmap_max = -1.f, err_target = -1.f;
@@ -46,18 +48,23 @@ int main(int argc, char** argv) {
     else if (a == "-e") err_target = static_cast<float>(std::atof(next()));
     else if (a == "-m") heatmap_max = static_cast<float>(std::atof(next()));
     else if (a == "-o") out_path = next();
+    else if (a == "-a") aux_prefix = next();
     else if (a == "-d") {
       if (std::sscanf(next(), "%d %d", &px, &py) != 2) {
         std::fprintf(stderr, "-d needs \"x y\"\n");
         return 2;
       }
     } else {
-      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-o out.png]\n");
+      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-o out.png]\n");
       return 2;
     }
   }
   if (err_target >= 0.f && prog_step <= 0) {   // adaptive sampling is a loop of increments: it needs their size
-    std::fprintf(stderr, "-e target needs -p step\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-o out.png]\n");
+    std::fprintf(stderr, "-e target needs -p step\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-o out.png]\n");
+    return 2;
+  }
+  if (!aux_prefix.empty() && (heatmap_max >= 0.f || px >= 0)) {   // feature buffers go beside a rendered image only
+    std::fprintf(stderr, "-a prefix goes with a rendered image: not with -m or -d\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-o out.png]\n");
     return 2;
   }
   if (scene_path.empty()) {
@@ -197,6 +204,35 @@ int main(int argc, char** argv) {
     return 1;
   }
   std::printf("output image written to %s\n", out_path.c_str());
+  if (!aux_prefix.empty()) {
+    // the first-hit feature integrators at the frame's sample count; the mapping to 8 bits is done here on the host
+    static const struct { uint32_t integrator; const char* name; } aux[3] = {
+        {VIMG_INTEGRATOR_ALBEDO, "albedo"}, {VIMG_INTEGRATOR_NORMAL, "normal"}, {VIMG_INTEGRATOR_DEPTH, "depth"}};
+    std::vector<float> img(n * 3);
+    for (const auto& f : aux) {
+      VimgRenderParams q = params;
+      q.integrator = f.integrator;
+      if (vimg_hip_render(dev, &q, d_rgb, nullptr, nullptr) != VIMG_OK ||
+          hipMemcpy(img.data(), d_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "%s render failed: %s\n", f.name, vimg_hip_last_error());
+        return 1;
+      }
+      if (f.integrator == VIMG_INTEGRATOR_NORMAL)
+        for (float& v : img) v = (v + 1.f) / 2.f;
+      if (f.integrator == VIMG_INTEGRATOR_DEPTH) {
+        const float deepest = *std::max_element(img.begin(), img.end());
+        if (deepest > 0.f)
+          for (float& v : img) v /= deepest;
+      }
+      const std::string path = aux_prefix + "_" + f.name + ".png";
+      if (vimg_host_tonemap_to_rgb8(img.data(), W, H, 0, rgb8.data()) != 0 ||
+          vimg_host_write_png(path.c_str(), rgb8.data(), W, H) != 0) {
+        std::fprintf(stderr, "%s write failed: %s\n", f.name, vimg_host_last_error());
+        return 1;
+      }
+      std::printf("%s written to %s\n", f.name, path.c_str());
+    }
+  }
   (void)hipFree(d_rgb);
   (void)hipFree(d_rgb8);
   vimg_hip_scene_free(dev);

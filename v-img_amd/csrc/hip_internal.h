@@ -1,7 +1,7 @@
 // What the host units of libvimg_hip.so share (none of it is exported: include/vimg_hip.h is the ABI).
 //   vimg_hip.hip       init / options / last_error, the render entry points, enqueue_render
 //   scene_upload.hip   validation, baking and upload of a scene, its changes, its release
-//   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel
+//   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel, feature_kernel
 //   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
 //   scene_rebuild.hip  a new tree for a resident scene, its cost       bvh_build.hip    the GPU builders and their cores
 //   scene_relight.hip  new materials, texture contents, emitters and background of a resident scene
@@ -97,6 +97,8 @@ inline hipStream_t stream_of(void* stream) { return stream ? static_cast<hipStre
 
 inline uint32_t tiles_of(int n) { return (static_cast<uint32_t>(n) + 7u) / 8u; }
 uint32_t local_tiles(const VimgDeviceScene* s, const VimgRenderParams* p);
+// the first-hit feature integrators (feature_kernel.h): one kernel of their own, whatever the scheduler option says
+inline bool is_feature_integrator(uint32_t i) { return i >= VIMG_INTEGRATOR_ALBEDO && i <= VIMG_INTEGRATOR_COVERAGE; }
 inline uint32_t opt_or(int32_t v, uint32_t dflt) { return v == VIMG_OPT_AUTO ? dflt : static_cast<uint32_t>(v); }
 
 struct LaunchCfg {
@@ -106,6 +108,7 @@ struct LaunchCfg {
   int wps;       // register-budget build (waves per SIMD of __launch_bounds__)
   bool deep;     // CU scheduler: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)
   int cu_waves;  // CU scheduler: waves per workgroup (16 or 8)
+  bool feature;  // feature_kernel (integrators ALBEDO .. COVERAGE) in the lane launch's shape: sched is VIMG_SCHED_LANE
   size_t cold_bytes;   // scene-owned scratch of the launch: cold slot records of every workgroup (0: none) ...
   size_t ovf_bytes;    // ... and the stack entries beyond stack_lds (0: the stacks fit)
 };
@@ -190,6 +193,8 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
 LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
 // the lane-bound kernel's launch; also the LDS layout (stacks, then the top of the tree) of probes, the heatmap and queries
 LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
+// feature_kernel's launch (integrators ALBEDO .. COVERAGE): make_launch_lane's layout, its own persistent grid
+LaunchCfg make_launch_feature(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
 RenderArgs base_args(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
 // Splits a pixel's samples into segments handed out as separate work items (sets pool_segments, pool_seg_len;
 // returns the length): about `per_gen` segments per pool generation of the frame, at most `most`

@@ -10,6 +10,7 @@ using RenderKernel = void (*)(const DScene, const RenderArgs, float*, DeviceStat
 using CuKernel = void (*)(const CuKArgs);
 
 RenderKernel vimg_lane_kernel(bool tex, int wps);             // render_kernel<TEX, WPS>
+RenderKernel vimg_feature_kernel(bool tex);                   // feature_kernel<TEX>: integrators ALBEDO .. COVERAGE
 CuKernel vimg_cu_kernel(bool tex, bool deep, int nw);         // render_cu_kernel<TEX, DEEP, 16, 4, false, 0>
 CuKernel vimg_cu_kernel_early(bool tex, bool deep, int nw);   // ... <..., false, 1>: rays queued as soon as they are known
 CuKernel vimg_cu_kernel_diag(bool tex, bool deep, int nw);    // ... <..., true, 2>: statistics launches

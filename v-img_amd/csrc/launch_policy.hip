@@ -1,7 +1,8 @@
 // The launch policy of the product: which kernel a launch runs and with what grid, LDS layout and scheduler
 // parameters.  Policy (AUTO): the CU-wide scheduler (render_cu_kernel) for every launch - whole frames, thin
 // shards, trace_pixel.  The lane-bound kernel runs when asked for by name and for frames wider than the 16-bit
-// pixel coordinates of the slot records.
+// pixel coordinates of the slot records.  The feature integrators (ALBEDO .. COVERAGE) have one kernel,
+// feature_kernel, in the lane launch's shape, whatever the scheduler option says.
 #include <cmath>
 
 #include "hip_internal.h"
@@ -193,6 +194,7 @@ void cu_scratch(const VimgDeviceScene* s, LaunchCfg& c) {
 }  // namespace
 
 const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
+  if (c.feature) return reinterpret_cast<const void*>(vimg_feature_kernel(s->textured));
   if (c.sched == VIMG_SCHED_CU) return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves));
   return reinterpret_cast<const void*>(vimg_lane_kernel(s->textured, c.wps));
 }
@@ -209,8 +211,13 @@ const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, boo
                                                       plain_launch_serves(s, c, stats)));
 }
 
-LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+namespace {
+
+// The lane launch's shape for `feature` or the lane-bound kernel: arguments, LDS layout (stacks, then the top of the
+// tree) and a persistent grid sized by ONE occupancy query, of the kernel that will run
+LaunchCfg lane_shaped_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy, bool feature) {
   LaunchCfg c{};
+  c.feature = feature;
   const VimgHipOptions& o = s->opt;
   const uint64_t items = (sx >= 0) ? 1 : uint64_t(local_tiles(s, p)) * 64u;
   c.sched = VIMG_SCHED_LANE;
@@ -230,7 +237,8 @@ LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, 
   a.lds_nodes = std::min(nodes, s->d.num_nodes);
   c.lds_bytes = ((a.lds_nodes * 56u + 255u) & ~255u) + stack_bytes;
   // persistent grid: as many 4-wave workgroups as the kernel's registers and LDS let a CU hold
-  // (asked of the runtime), never more than the work
+  // (asked of the runtime), never more than the work.  (A masked launch's item list is set after this, by
+  // enqueue_render: its grid is still sized by the shard's items, and a wave without work leaves after one claim.)
   int per_cu = 0;
   hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of(s, c), 256, c.lds_bytes);
   if (oe != hipSuccess || per_cu < 1) per_cu = 1;
@@ -240,7 +248,19 @@ LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, 
   return c;
 }
 
+}  // namespace
+
+LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  return lane_shaped_launch(s, p, sx, sy, false);
+}
+
+// The feature integrators' launch: the lane launch's LDS layout and arguments, the grid by feature_kernel's occupancy
+LaunchCfg make_launch_feature(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  return lane_shaped_launch(s, p, sx, sy, true);
+}
+
 LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  if (is_feature_integrator(p->integrator)) return make_launch_feature(s, p, sx, sy);
   // (the upload admits the schedulers AUTO, LANE and CU only)
   if (s->too_wide || s->opt.scheduler == VIMG_SCHED_LANE) return make_launch_lane(s, p, sx, sy);   // slots pack pixel coordinates in 16 bits
   LaunchCfg c = make_launch_cu(s, p, sx, sy);
@@ -261,6 +281,7 @@ const char* vimg_hip_launch_kernel(const VimgDeviceScene* s, const VimgRenderPar
   static const char* cu_names[2][2] = {{"render_cu_kernel<false>", "render_cu_kernel<false,deep>"},
                                        {"render_cu_kernel<true>", "render_cu_kernel<true,deep>"}};
   if (p->tile_world == 0 || p->tile_rank >= p->tile_world) return "";
+  if (is_feature_integrator(p->integrator)) return s->textured ? "feature_kernel<true>" : "feature_kernel<false>";
   const LaunchCfg c = make_launch(s, p, -1, -1);
   // The build whole frames are timed on keeps the name it has always had: that is a PLAIN build now (plain_build.h).
   // Where the general build of the same scene class runs instead - another integrator, other options, the override

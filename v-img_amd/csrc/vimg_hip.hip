@@ -38,7 +38,7 @@ int check_params(const VimgDeviceScene* s, const VimgRenderParams* p) {
   if (p->samples == 0) return fail(VIMG_E_INVALID, "samples must be > 0");
   if (p->integrator == VIMG_INTEGRATOR_MATERIAL && p->depth == 0)
     return fail(VIMG_E_INVALID, "material integrator with depth 0 renders nothing");
-  if (p->integrator > VIMG_INTEGRATOR_MIS) return fail(VIMG_E_INVALID, "unknown integrator");
+  if (p->integrator > VIMG_INTEGRATOR_COVERAGE) return fail(VIMG_E_INVALID, "unknown integrator");
   if (p->integrator == VIMG_INTEGRATOR_MIS && s->d.num_lights == 0)
     return fail(VIMG_E_INVALID, "mis integrator needs at least one light (the reference's "
                                 "GroupOfEmitters::sample is undefined without one)");

@@ -198,6 +198,28 @@ class DeviceScene:
                                              C.byref(st) if stats else None))
         return (out, st) if stats else out
 
+    def render_features(self, params, features=("albedo", "normal", "depth"), out=None, stream=None):
+        """First-hit feature buffers of the frame (or shard) ``params`` describes: a dict name -> float32 CUDA
+        tensor in ``render``'s shapes, one launch per feature with ``params``' samples and shard
+        (``params.integrator`` is ignored).  ``features``: names out of abi.FEATURES - albedo, normal (the raw
+        shading normal), depth, position, uv, coverage; a miss contributes 0 to each.  ``out``: a dict with a
+        tensor to write for some or all of the names."""
+        unknown = [f for f in features if f not in abi.FEATURES]
+        if unknown:
+            raise ValueError(f"render_features: expected names out of {abi.FEATURES}, not {unknown}")
+        w, h = self.resolution
+        p = abi.RenderParams.from_buffer_copy(params)
+        p.integrator = abi.INTEGRATOR_COVERAGE      # (the caller's integrator is not even checked)
+        shape = (h, w, 3) if p.tile_world == 1 else (self.shard_pixels(p), 3)
+        res = {}
+        for name in features:
+            p.integrator = abi.INTEGRATORS[name]
+            given = None if out is None else out.get(name)
+            if given is not None:
+                given = _device_tensor(given, f"render_features[{name}]", ("float32",), shape, out=True)[0]
+            res[name] = self.render(p, out=given, stats=False, stream=stream)
+        return res
+
     def _new_output(self, params, zero_slab=True):
         """A frame [H, W, 3] for these parameters, or the shard's compact slab [shard_pixels, 3] when tile_world > 1
         (zeroed, when asked: a ragged shard has slots off the image that no launch writes)."""
