@@ -2130,6 +2130,37 @@ int oracle_probe(const VimgScene* scene, int kind, int n, const float* in, float
         o[0] = e.x, o[1] = e.y, o[2] = e.z, o[3] = background_pdf(scene, d);
         break;
       }
+      case ORACLE_PROBE_MATERIAL_INPUTS: {
+        // what eval_pdf_pair / sample_mat read at the hit before any lobe math, through the functions
+        // they call: the colour of col_at_ray_hit, the level of detail its image lookup blends at
+        // (compute_texture_LOD - 2 in col_mipmap_interpolate's clamp; 0 for the other texture types)
+        // and the metallic / roughness pair of principled_prologue
+        const float* p = in + 8 * i;
+        float* o = out + 8 * i;
+        std::fill(o, o + 8, 0.f);
+        HitInfo h;
+        Ray r;
+        if (trace(p, h, r)) {
+          const VimgMaterial& m = scene->materials[h.mat];
+          const RayCone cone{p[6], p[7]};
+          vec3 col{0.f, 0.f, 0.f};
+          float metallic = 0.f, roughness = 0.f, lambda = 0.f;
+          if (m.type == VIMG_MAT_LAMBERTIAN || m.type == VIMG_MAT_PRINCIPLED) {
+            col = col_at_ray_hit(scene, m.tex, r.dir, cone, h);
+            const VimgTexture& t = scene->textures[m.tex];
+            if (t.type == VIMG_TEX_IMAGE)
+              lambda = clampf(compute_texture_LOD(t, r.dir, cone, h) - 2.f, 0.f,
+                              static_cast<float>(t.num_levels - 1));
+          }
+          if (m.type == VIMG_MAT_PRINCIPLED) {
+            PrincipledCommon pc = principled_prologue(scene, m, r.dir, h);
+            metallic = pc.metallic, roughness = pc.roughness;
+          }
+          o[0] = 1.f, o[1] = col.x, o[2] = col.y, o[3] = col.z, o[4] = metallic, o[5] = roughness;
+          o[6] = lambda, o[7] = static_cast<float>(h.mat);
+        }
+        break;
+      }
       default:
         return -1;
     }

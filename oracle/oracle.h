@@ -53,7 +53,9 @@ enum {
   ORACLE_PROBE_BSDF_EVAL = 4,    /* in 12: o3 d3 wo3 cone2 regularize  out 5: hit f3 pdf */
   ORACLE_PROBE_BSDF_SAMPLE = 5,  /* in 8: o3 d3 seed regularize      out 7: hit has wo3 eta spec */
   ORACLE_PROBE_LIGHT_SAMPLE = 6, /* in 4: p3 seed                    out 10: Le3 wi3 pdf dist G */
-  ORACLE_PROBE_BACKGROUND = 7    /* in 5: d3 cone2                   out 4: emit3 pdf */
+  ORACLE_PROBE_BACKGROUND = 7,   /* in 5: d3 cone2                   out 4: emit3 pdf */
+  ORACLE_PROBE_MATERIAL_INPUTS = 9 /* in 8: o3 d3 cone2              out 8: hit col3 metallic roughness lod mat
+                                      (8 is the HIP probe's sincos check, which has no oracle side) */
 };
 int oracle_probe(const VimgScene* scene, int kind, int n, const float* in, float* out);
 

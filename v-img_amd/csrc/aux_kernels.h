@@ -28,8 +28,21 @@ __global__ void assemble_kernel(const float* __restrict__ shards, float* __restr
 // Unit-level entry points used by the parity tests; layouts mirror the checker's probe API.
 enum {
   PROBE_CAMERA_RAY = 1, PROBE_CLOSEST_HIT = 2, PROBE_OCCLUDED = 3, PROBE_BSDF_EVAL = 4,
-  PROBE_BSDF_SAMPLE = 5, PROBE_LIGHT_SAMPLE = 6, PROBE_BACKGROUND = 7, PROBE_SINCOS = 8
+  PROBE_BSDF_SAMPLE = 5, PROBE_LIGHT_SAMPLE = 6, PROBE_BACKGROUND = 7, PROBE_SINCOS = 8,
+  PROBE_MATERIAL_INPUTS = 9
 };
+// ImageTexture::compute_texture_LOD (reference include/texture/texture_RGB.h:138-149) as col_at_ray_hit
+// evaluates it in line.  PROBE_MATERIAL_INPUTS reports it beside the colour that col_at_ray_hit itself
+// returns; it is stated here and not split out of render_kernels.h because calling a helper from there, forced
+// inline as it is, renumbers the scalar registers of render_cu_kernel (about 6000 of its 197 000 assembly lines
+// differ), and the probe must leave the product's code objects as they are.  A comment there points here.
+VD float compute_texture_lod(gptr<VimgTexture> t, f3 ray_in_dir, RayCone cone, const Hit& hit) {
+  float lambda = 0.5f * F_log2((hit.tex_area) / hit.prim_area);
+  lambda += F_log2(absf(cone.cone_width) / absf(dot(ray_in_dir, hit.ng)));
+  lambda += 0.5f * ::log2(static_cast<double>(t->width * t->height));
+  if (is_nan(lambda)) lambda = 0.f;
+  return lambda;
+}
 template <bool TEX>
 __global__ void __launch_bounds__(256)
 probe_kernel(const DScene g, const RenderArgs A, int kind, int n, const float* __restrict__ in,
@@ -147,6 +160,38 @@ probe_kernel(const DScene g, const RenderArgs A, int kind, int n, const float* _
       D_sincos(x, s1, c1);
       o[0] = static_cast<float>(c0), o[1] = static_cast<float>(s0), o[2] = static_cast<float>(c1), o[3] = static_cast<float>(s1);
       o[4] = (__double_as_longlong(c0) == __double_as_longlong(c1) && __double_as_longlong(s0) == __double_as_longlong(s1)) ? 1.f : 0.f;
+      break;
+    }
+    case PROBE_MATERIAL_INPUTS: {
+      // what eval_pdf_pair / sample_mat read at the hit before any lobe math, through the functions they
+      // call: col_at_ray_hit's colour, the level of detail its image lookup blends at (compute_texture_lod above
+      // - 2 in col_mipmap_interpolate's clamp; 0 for the other texture types), principled_prologue's pair
+      const float* p = in + 8 * i;
+      float* o = out + 8 * i;
+      for (int k = 0; k < 8; ++k) o[k] = 0.f;
+      Hit h;
+      TravRay tr;
+      if (trace(p, h, tr)) {
+        gptr<VimgMaterial> m = g.materials + h.mat;
+        const RayCone cone{p[6], p[7]};
+        const uint32_t type = m->type;
+        f3 col{0.f, 0.f, 0.f};
+        float metallic = 0.f, roughness = 0.f, lambda = 0.f;
+        if (type == VIMG_MAT_LAMBERTIAN || type == VIMG_MAT_PRINCIPLED) {
+          col = col_at_ray_hit<TEX>(g, m->tex, tr.d, cone, h);
+          gptr<VimgTexture> t = g.textures + m->tex;
+          if constexpr (TEX) {
+            if (t->type == VIMG_TEX_IMAGE)
+              lambda = clampf(compute_texture_lod(t, tr.d, cone, h) - 2.f, 0.f, static_cast<float>(t->num_levels - 1));
+          }
+        }
+        if (type == VIMG_MAT_PRINCIPLED) {
+          const PrincipledCommon pc = principled_prologue<TEX>(g, m, tr.d, h);
+          metallic = pc.metallic, roughness = pc.roughness;
+        }
+        o[0] = 1.f, o[1] = col.x, o[2] = col.y, o[3] = col.z, o[4] = metallic, o[5] = roughness;
+        o[6] = lambda, o[7] = static_cast<float>(h.mat);
+      }
       break;
     }
     default:

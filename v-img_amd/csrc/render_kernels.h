@@ -305,7 +305,7 @@ VD f3 col_at_ray_hit(const DScene& g, int tex, f3 ray_in_dir, RayCone cone, cons
     uint32_t v_board = static_cast<uint32_t>(__builtin_floorf(hit.uv.y * t->height));
     return ((u_board + v_board) % 2 == 0) ? load3(t->col_a) : load3(t->col_b);
   }
-  if constexpr (TEX) {
+  if constexpr (TEX) {   // the four lambda lines are restated as compute_texture_lod in aux_kernels.h (probe 9): keep both alike
     float lambda = 0.5f * F_log2((hit.tex_area) / hit.prim_area);
     lambda += F_log2(absf(cone.cone_width) / absf(dot(ray_in_dir, hit.ng)));
     lambda += 0.5f * ::log2(static_cast<double>(t->width * t->height));
