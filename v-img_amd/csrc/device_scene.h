@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/vimg_scene.h"
+#include "material_record.h"
 
 namespace vimg {
 
@@ -101,6 +102,7 @@ struct DScene {
   gptr<VimgSphere> spheres;
   gptr<VimgMaterial> materials;
   gptr<uint32_t> material_flags;   // MATF_* per material
+  gptr<DMaterial> dmaterials;      // the same table, baked: 304 B per material (material_record.h, material_terms.h)
   gptr<VimgTexture> textures;
   gptr<float> texels;
   gptr<VimgTextureRG> rg_textures;

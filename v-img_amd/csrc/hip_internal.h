@@ -57,7 +57,7 @@ struct VimgDeviceScene {
   std::vector<VimgLight> lights;
   uint32_t num_rg_textures = 0;
   uint64_t num_texels = 0, num_cdf = 0;
-  size_t lights_table = 0, dlights_table = 0;
+  size_t lights_table = 0, dlights_table = 0, dmaterials_table = 0;
   // ray queries (vimg_hip_trace_rays, _occluded): the LDS layout and the blocks per CU of each query build, worked
   // out at the first query and again after vimg_hip_scene_rebuild_bvh (which resets query_ready: both depend on
   // max_depth and num_nodes; nothing else changes the tree's shape, and the options never change after upload)
@@ -139,6 +139,7 @@ bool background_is_emissive(const VimgBackground& bg);
 struct RelightPlan {
   bool any = false;                  // the update carries one of the new fields
   DevBuf new_lights, new_dlights;    // set_lights: built beside the scene's
+  DevBuf new_dmaterials;             // materials or textures: the baked material records, built beside the scene's
   DevBuf sin_elev, lum, row_int, row_tot;   // env-map CDFs: the kernels' temporaries
   std::vector<float> sin_table;
 };
@@ -146,6 +147,9 @@ int check_relight(const VimgDeviceScene* s, const VimgGeometryUpdate* u);
 int prepare_relight(const VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan);
 int enqueue_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan, hipStream_t st);
 void commit_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan);
+// one DMaterial per material into `out`, from the materials and texture records resident in `d` (the upload's bake
+// and the re-bake of an edit: one kernel, material_terms.h's statements)
+int enqueue_material_bake(const DScene& d, uint32_t num_materials, DMaterial* out, hipStream_t st);
 
 // ---- precompute.hip: the launches of the texture pre-pass on device buffers.  level_offset: in texels from
 // `texels`, level 0 filled; the CDFs go where row_cdf (h + 1 floats) and col_cdfs (h x (w + 1)) point

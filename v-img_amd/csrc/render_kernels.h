@@ -17,6 +17,7 @@
 #pragma once
 #include "device_math.h"
 #include "device_scene.h"
+#include "material_terms.h"
 
 namespace vimg {
 
@@ -905,9 +906,34 @@ VD float fresnel_dielectric(float n_dot_i, float eta) {
 VD float fd_term(f3 n, f3 w, float fd90) {   // FD, disney_diffuse.h:9-11
   return 1.f + (fd90 - 1.f) * pow5(1.f - sel_max(dot(n, w), 0.f));
 }
-VD void regularize_alpha(float& ax, float& ay) {   // MatConst, include/material/material.h:19-23
-  ax = ax < 0.1f ? clampf(2.f * ax, 0.03f, 0.1f) : ax;
-  ay = ay < 0.1f ? clampf(2.f * ay, 0.03f, 0.1f) : ay;
+
+// ---- the baked material record (DMaterial, material_record.h): loads of one group.  The stages load a group
+// where they used to compute it, for a material whose validity bit is set, and run material_terms.h's statements
+// otherwise; the untextured builds never read a metallic-roughness map (principled_prologue), so their scalar
+// group always holds.
+VD DMatCoat load_coat(gptr<DMatCoat> p) {
+  DMatCoat c;
+  c.alpha_g = p->alpha_g, c.ag2 = p->ag2, c.ag2m1 = p->ag2m1, c.pad = 0.f, c.ag2m1_d = p->ag2m1_d, c.pi_log = p->pi_log;
+  return c;
+}
+VD DMatWeights load_weights(gptr<DMatWeights> p) {
+  DMatWeights w;
+  w.choose_diff = p->choose_diff, w.choose_clearcoat = p->choose_clearcoat, w.choose_metal = p->choose_metal;
+  w.choose_glass = p->choose_glass, w.sum2 = p->sum2, w.sum3 = p->sum3, w.sum4 = p->sum4;
+  w.mix_diff = p->mix_diff, w.mix_sheen = p->mix_sheen, w.mix_coat = p->mix_coat, w.mix_metal = p->mix_metal;
+  w.mix_glass = p->mix_glass;
+  return w;
+}
+// A material's record, addressed anew at every site that loads a group: the empty statement keeps the compiler from
+// merging the sites' loads into one at the top of the function, where the loaded terms would stay live across the
+// whole evaluation in a kernel that sits at its register budget.
+VD gptr<DMaterial> dmat_at(const DScene& g, uint32_t mat) {
+  asm volatile("" : "+v"(mat));
+  return g.dmaterials + mat;
+}
+template <bool TEX>
+VD bool dmat_scalars(uint32_t bits) {
+  return !TEX || (bits & DMAT_SCALARS) != 0;
 }
 
 struct PrincipledCommon {
@@ -948,15 +974,32 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
   const f3 dir_in = pc.dir_in;
   const Onb& frame = pc.frame;
   const float metallic = pc.metallic, roughness = pc.roughness;
-  const f3 base_color = col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit);
+  const uint32_t mat = hit.mat;
+  const int reg = regularize ? 1 : 0;
+  float alphax, alphay;
+  f3 base_color;
+  bool scalars, colour;
+  {
+    gptr<DMaterial> dm = dmat_at(g, mat);
+    const uint32_t bits = dm->bits;
+    scalars = dmat_scalars<TEX>(bits), colour = (bits & DMAT_COLOUR) != 0;
+    base_color = colour ? load3(dm->base) : col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit);
+    if (scalars) {
+      alphax = dm->alpha[reg].ax, alphay = dm->alpha[reg].ay;
+    } else {
+      mat_alphas(clampf(roughness, 0.01f, 1.f), m->anisotropic, regularize, alphax, alphay);
+    }
+  }
+  // alphax * alphax, alphay * alphay and kPi * alphax * alphay, where a lobe's D is formed
+  auto alpha_products = [&](float& ax2, float& ay2, double& pi_axay) {
+    if (scalars) {
+      gptr<DMatAlpha> a = dmat_at(g, mat)->alpha + reg;
+      ax2 = a->ax2, ay2 = a->ay2, pi_axay = a->pi_axay;
+    } else {
+      ax2 = alphax * alphax, ay2 = alphay * alphay, pi_axay = kPi * alphax * alphay;
+    }
+  };
   const f3 half_vector = normalize(dir_in + wo);
-  constexpr float alpha_min = 0.0001;
-  const float aspect = sqrt_f(1.f - 0.9f * m->anisotropic);
-  const float roughness_clamp = clampf(roughness, 0.01f, 1.f);
-  const float roughness_square = roughness_clamp * roughness_clamp;
-  float alphax = sel_max(alpha_min, roughness_square / aspect);
-  float alphay = sel_max(alpha_min, roughness_square * aspect);
-  if (regularize) regularize_alpha(alphax, alphay);
   const float g_in = g_w(dir_in, alphax, alphay, frame);
   const float G = g_in * g_w(wo, alphax, alphay, frame);
   const float ng_in = dot(hit.ng, dir_in);
@@ -966,36 +1009,38 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
   f3 eval_glass;
   float pdf_glass;
   {
-    const float mat_eta = m->eta;
     float in_geo_dot = dot(dir_in, hit.ng);
     bool reflect = (in_geo_dot * dot(hit.ng, wo)) >= 0;
-    float eta = in_geo_dot >= 0 ? mat_eta : 1.f / mat_eta;
+    const DMatEta et = mat_eta_terms(m->eta, in_geo_dot >= 0);   // (computed here, like the weights and c_0 below: DESIGN.md 4.17)
+    float ax2, ay2;
+    double pi_axay;
+    alpha_products(ax2, ay2, pi_axay);
+    const float eta = et.eta;
     f3 hv = half_vector;
     if (!reflect) hv = normalize(dir_in + wo * eta);
     float h_dot_in = dot(hv, dir_in);
     float F = fresnel_dielectric(h_dot_in, eta);
     const f3 lh = project_onto_onb(frame, hv);
-    float had = (lh.x * lh.x) / (alphax * alphax) + (lh.y * lh.y) / (alphay * alphay)
-                + (lh.z * lh.z);
-    float D = 1. / (kPi * alphax * alphay * (had * had));
+    float had = (lh.x * lh.x) / ax2 + (lh.y * lh.y) / ay2 + (lh.z * lh.z);
+    float D = 1. / (pi_axay * (had * had));
     float normal_in_dot = dot(frame.w, dir_in);
     if (reflect) {
       eval_glass = base_color * (F * D * G) / (4.f * absf(normal_in_dot));
       pdf_glass = (F * D * g_in) / (4.f * absf(normal_in_dot));
     } else {
-      float eta_factor = 1.f / (eta * eta);
+      float eta_factor = et.inv_eta2;
       float h_dot_out = dot(hv, wo);
       float sqrt_denom = h_dot_in + eta * h_dot_out;
-      eval_glass = f3{sqrt_f(base_color.x), sqrt_f(base_color.y), sqrt_f(base_color.z)}
+      eval_glass = (colour ? load3(dmat_at(g, mat)->sqrt_base) : mat_sqrt3(base_color))
                    * (eta_factor * (1 - F) * D * G * eta * eta * absf(h_dot_out * h_dot_in))
                    / (absf(normal_in_dot) * sqrt_denom * sqrt_denom);
-      float dh_dout = eta * eta * h_dot_out / (sqrt_denom * sqrt_denom);
+      float dh_dout = et.eta2 * h_dot_out / (sqrt_denom * sqrt_denom);
       pdf_glass = (1.f - F) * D * g_in * absf(dh_dout * h_dot_in / normal_in_dot);
     }
   }
-  const float st = m->specular_transmission;
   if (ng_in < 0) {
-    f_out = (1.f - metallic) * st * eval_glass;
+    const float mix_glass = mat_weight_terms(metallic, m->specular_transmission, m->clearcoat, m->sheen).mix_glass;
+    f_out = mix_glass * eval_glass;
     pdf_out = pdf_glass;
     return;
   }
@@ -1013,15 +1058,11 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
   f3 eval_metal{0.f, 0.f, 0.f};
   float pdf_metal = 0.f;
 
-  float alpha_g = (1.f - m->clearcoat_gloss) * 0.1f + m->clearcoat_gloss * 0.001f;
-  alpha_g = regularize && (alpha_g < 0.1f) ? clampf(2.f * alpha_g, 0.03f, 0.1f) : alpha_g;
-
   if (!below) {
-    const float base_lum = luminance(base_color);
-    const f3 c_tint = base_lum > 0 ? base_color / base_lum : splat3(1.f);
+    f3 c_tint{0.f, 0.f, 0.f};
+    if (!colour) c_tint = mat_c_tint(base_color);
     {
-      const float sheen_tint = m->sheen_tint;
-      f3 c_sheen = (splat3(1.f) - splat3(sheen_tint)) + sheen_tint * c_tint;
+      const f3 c_sheen = colour ? load3(dmat_at(g, mat)->c_sheen) : mat_c_sheen(c_tint, m->sheen_tint);
       eval_sheen = c_sheen * pow5(1.f - sel_max(dot(half_vector, wo), 0.f))
                    * sel_max(dot(frame.w, wo), 0.f);
     }
@@ -1048,45 +1089,37 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
       float h_dirout_dot = absf(dot(half_vector, wo));
       float fresnel = R0 + (1. - R0) * pow5(1.f - h_dirout_dot);
       float Gc = g_w(dir_in, 0.25, 0.25, frame) * g_w(wo, 0.25, 0.25, frame);
-      const float ag2 = alpha_g * alpha_g;
+      const DMatCoat cc = scalars ? load_coat(dmat_at(g, mat)->coat + reg) : mat_coat_terms(m->clearcoat_gloss, regularize);
       const f3 lh = project_onto_onb(frame, half_vector);
-      float D = (ag2 - 1.f) / (kPi * F_log(ag2) * (1. + (ag2 - 1.) * lh.z * lh.z));
+      float D = cc.ag2m1 / (cc.pi_log * (1. + cc.ag2m1_d * lh.z * lh.z));
       float clearcoat_eval = (fresnel * D * Gc) / (4.f * absf(dot(frame.w, dir_in)));
       pdf_clearcoat = (D * absf(dot(frame.w, half_vector))) / (4.f * h_dirout_dot);
       eval_clearcoat = splat3(clearcoat_eval);
     }
     {
-      const float spec_tint = m->specular_tint, specular = m->specular, eta = m->eta;
-      f3 k_s = (splat3(1.f) - splat3(spec_tint)) + spec_tint * c_tint;
-      float R0 = ((eta - 1.f) * (eta - 1.f)) / ((eta + 1.f) * (eta + 1.f));
-      f3 c_0 = (specular * R0 * (1.f - metallic)) * k_s + metallic * base_color;
-      f3 fresnel = c_0 + (splat3(1.f) - c_0) * pow5(1.f - dot(half_vector, wo));
+      const f3 k_s = colour ? load3(dmat_at(g, mat)->k_s) : mat_k_s(c_tint, m->specular_tint);
+      const f3 c_0 = mat_c_0(mat_spec_r0(m->specular, mat_r0(m->eta), metallic), k_s, metallic, base_color);
+      const f3 one_minus_c_0 = mat_one_minus(c_0);
+      f3 fresnel = c_0 + one_minus_c_0 * pow5(1.f - dot(half_vector, wo));
       const f3 lh = project_onto_onb(frame, half_vector);
-      float had = (lh.x * lh.x) / (alphax * alphax) + (lh.y * lh.y) / (alphay * alphay)
-                  + (lh.z * lh.z);
-      float D = 1. / (kPi * alphax * alphay * (had * had));
+      float ax2, ay2;
+      double pi_axay;
+      alpha_products(ax2, ay2, pi_axay);
+      float had = (lh.x * lh.x) / ax2 + (lh.y * lh.y) / ay2 + (lh.z * lh.z);
+      float D = 1. / (pi_axay * (had * had));
       float d_mul_denominator = D / (4.f * absf(dot(frame.w, dir_in)));
       eval_metal = fresnel * G * d_mul_denominator;
       pdf_metal = g_in * d_mul_denominator;
     }
   }
-  const float clearcoat = m->clearcoat, sheen = m->sheen;
-  f3 eval_principled = ((1.f - st) * (1.f - metallic) * eval_diff)
-                       + ((1.f - metallic) * sheen * eval_sheen)
-                       + (0.25f * clearcoat * eval_clearcoat)
-                       + ((1.f - st * (1.f - metallic)) * eval_metal)
-                       + ((1.f - metallic) * st * eval_glass);
-  float diffuse_weight = (1.f - metallic) * (1.f - st);
-  float clearcoat_weight = 0.25f * clearcoat;
-  float metal_weight = (1.f - st * (1.f - metallic));
-  float glass_weight = (1.f - metallic) * st;
-  float total_w = diffuse_weight + clearcoat_weight + metal_weight + glass_weight;
-  float choose_diff = diffuse_weight / total_w;
-  float choose_clearcoat = clearcoat_weight / total_w;
-  float choose_metal = metal_weight / total_w;
-  float choose_glass = glass_weight / total_w;
-  pdf_out = choose_diff * pdf_diff + choose_clearcoat * pdf_clearcoat + choose_metal * pdf_metal
-            + choose_glass * pdf_glass;
+  const DMatWeights w = mat_weight_terms(metallic, m->specular_transmission, m->clearcoat, m->sheen);
+  f3 eval_principled = (w.mix_diff * eval_diff)
+                       + (w.mix_sheen * eval_sheen)
+                       + (w.mix_coat * eval_clearcoat)
+                       + (w.mix_metal * eval_metal)
+                       + (w.mix_glass * eval_glass);
+  pdf_out = w.choose_diff * pdf_diff + w.choose_clearcoat * pdf_clearcoat + w.choose_metal * pdf_metal
+            + w.choose_glass * pdf_glass;
   f_out = eval_principled;
 }
 
@@ -1114,48 +1147,38 @@ VD Scatter sample_mat(const DScene& g, const Hit& hit, f3 wi, Rng& rng, bool reg
     const float metallic = pc.metallic;
     float roughness = pc.roughness;
     const float ng_in = dot(hit.ng, dir_in);
+    gptr<DMaterial> dm = g.dmaterials + hit.mat;
+    const bool scalars = dmat_scalars<TEX>(dm->bits);
+    const int reg = regularize ? 1 : 0;
     if (ng_in < 0) {
       lobe = LOBE_GLASS;   // inside the surface: glass only, no lobe draw (principled.cpp:23-26)
     } else {
-      const float st = m->specular_transmission;
-      float diffuse_weight = (1.f - metallic) * (1.f - st);
-      float clearcoat_weight = 0.25f * m->clearcoat;
-      float metal_weight = (1.f - st * (1.f - metallic));
-      float glass_weight = (1.f - metallic) * st;
-      float total_w = diffuse_weight + clearcoat_weight + metal_weight + glass_weight;
-      float choose_diff = diffuse_weight / total_w;
-      float choose_clearcoat = clearcoat_weight / total_w;
-      float choose_metal = metal_weight / total_w;
-      float choose_glass = glass_weight / total_w;
+      const DMatWeights w = scalars ? load_weights(&dm->w) : mat_weight_terms(metallic, m->specular_transmission, m->clearcoat, m->sheen);
       float rnd = rand_float(rng);
-      if (rnd <= choose_diff) {
+      if (rnd <= w.choose_diff) {
         lobe = LOBE_COSINE;   // ng_in >= 0 here, so sample_disney_diffuse's early-out cannot fire
-      } else if (rnd > choose_diff && rnd <= (choose_diff + choose_clearcoat)) {
+      } else if (rnd > w.choose_diff && rnd <= w.sum2) {
         lobe = LOBE_CLEARCOAT;
-      } else if (rnd > (choose_diff + choose_clearcoat)
-                 && rnd <= (choose_diff + choose_clearcoat + choose_metal)) {
+      } else if (rnd > w.sum2 && rnd <= w.sum3) {
         lobe = LOBE_METAL;
-      } else if (rnd > (choose_diff + choose_clearcoat + choose_metal)
-                 && rnd <= (choose_diff + choose_clearcoat + choose_metal + choose_glass)) {
+      } else if (rnd > w.sum3 && rnd <= w.sum4) {
         lobe = LOBE_GLASS;
       }
     }
     if (lobe == LOBE_CLEARCOAT) {
-      const float gloss = m->clearcoat_gloss;
-      alpha_g = (1.f - gloss) * 0.1f + gloss * 0.001f;
-      if (regularize && alpha_g < 0.1f) alpha_g = clampf(2.f * alpha_g, 0.03f, 0.1f);
+      alpha_g = scalars ? dm->coat[reg].alpha_g : mat_alpha_g(m->clearcoat_gloss, regularize);
     } else if (lobe == LOBE_METAL || lobe == LOBE_GLASS) {
-      constexpr float alpha_min = 0.0001;
-      float aspect = sqrt_f(1.f - 0.9f * m->anisotropic);
       // the glass lobe clamps roughness, the metal lobe does not (disney_glass.h:118 vs
       // disney_metal.h:92-96)
-      if (lobe == LOBE_GLASS) roughness = clampf(roughness, 0.01f, 1.f);
-      float roughness_square = roughness * roughness;
-      alphax = sel_max(alpha_min, roughness_square / aspect);
-      alphay = sel_max(alpha_min, roughness_square * aspect);
-      if (regularize) regularize_alpha(alphax, alphay);
-      const float mat_eta = m->eta;
-      eta = ng_in >= 0 ? mat_eta : 1.f / mat_eta;
+      if (scalars) {
+        alphax = lobe == LOBE_GLASS ? dm->alpha[reg].ax : dm->salpha[reg][0];
+        alphay = lobe == LOBE_GLASS ? dm->alpha[reg].ay : dm->salpha[reg][1];
+        eta = dm->eta[ng_in >= 0 ? 0 : 1].eta;
+      } else {
+        if (lobe == LOBE_GLASS) roughness = clampf(roughness, 0.01f, 1.f);
+        mat_alphas(roughness, m->anisotropic, regularize, alphax, alphay);
+        eta = mat_eta_terms(m->eta, ng_in >= 0).eta;
+      }
     }
   }
   if (lobe == LOBE_DIELECTRIC) return dielectric_sample(m, hit, wi, rng);
@@ -1256,7 +1279,9 @@ VD void eval_pdf_pair(const DScene& g, const Hit& hit, f3 wi, f3 wo, RayCone con
   if (type == VIMG_MAT_LAMBERTIAN) {
     // Lambertian::eval_pdf_pair, reference src/material/lambertian.cpp:47-54
     float dot_product = static_cast<float>(sel_max(0.0f, dot(wo, hit.ns)) / kPi);
-    f = col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit) * dot_product;
+    gptr<DMaterial> dm = g.dmaterials + hit.mat;
+    const f3 col = (dm->bits & DMAT_COLOUR) ? load3(dm->base) : col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit);
+    f = col * dot_product;
     pdf = dot_product;
   } else if (type == VIMG_MAT_PRINCIPLED) {
     principled_eval_pdf<TEX>(g, m, wi, wo, hit, cone, regularize, f, pdf);

@@ -6,6 +6,8 @@
 //   scene_relight_flags    one thread per material: material_flags
 //   scene_relight_cls      one thread per leaf slot: the material class of its primitive (a later rebuild of the
 //                          tree carries the classes over from the slots, scene_rebuild.hip)
+//   scene_bake_materials   one thread per material: its DMaterial (material_terms.h), at upload and after every edit
+//                          of materials or texture records, into a buffer beside the live one
 //   scene_relight_lights   one thread per emitter: the whole DLight - kind, index, the triangle's or sphere's
 //                          fields, the material's emission - from the emitter list it is given
 //   (precompute.hip)       an image's mip chain in place, level by level, and the env map's sampling CDFs
@@ -19,6 +21,7 @@
 
 #include "device_math.h"
 #include "hip_internal.h"
+#include "material_terms.h"
 #include "scene_bake.h"
 
 namespace vimg {
@@ -55,6 +58,27 @@ scene_relight_lights(const DScene d, const VimgLight* __restrict__ lights, uint3
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= num_lights) return;
   out[i] = bake_light(lights[i], flat(d.prims), flat(d.tri_shade), flat(d.tri_area_pdf), flat(d.meshes), flat(d.spheres), flat(d.materials));
+}
+
+// Baked on the device, never on the host: F_log is OCML's log here and in the stages, glibc's there.
+__global__ void __launch_bounds__(kBlock) scene_bake_materials(const DScene d, uint32_t num_materials, DMaterial* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_materials) return;
+  const VimgMaterial m = flat(d.materials)[i];
+  const uint32_t bits = dmaterial_bits(m, flat(d.textures));
+  f3 base{0.f, 0.f, 0.f};
+  if (bits & DMAT_COLOUR) {
+    const VimgTexture* t = flat(d.textures) + m.tex;
+    base = f3{t->col_a[0], t->col_a[1], t->col_a[2]};
+  }
+  out[i] = bake_dmaterial(m, bits, base);
+}
+
+int enqueue_material_bake(const DScene& d, uint32_t num_materials, DMaterial* out, hipStream_t st) {
+  if (!num_materials) return VIMG_OK;
+  hipLaunchKernelGGL(scene_bake_materials, blocks_for(num_materials), dim3(kBlock), 0, st, d, num_materials, out);
+  HIP_TRY(hipGetLastError());
+  return VIMG_OK;
 }
 
 namespace {
@@ -124,6 +148,8 @@ int prepare_relight(const VimgDeviceScene* s, const VimgGeometryUpdate* u, Relig
     if (int rc = plan->new_lights.alloc(std::max<size_t>(u->num_lights, 1) * sizeof(VimgLight))) return rc;
     if (int rc = plan->new_dlights.alloc(std::max<size_t>(u->num_lights, 1) * sizeof(DLight))) return rc;
   }
+  if ((u->materials || u->textures) && !s->materials.empty())
+    if (int rc = plan->new_dmaterials.alloc(s->materials.size() * sizeof(DMaterial))) return rc;
   for (uint32_t k = 0; k < u->num_images; ++k)
     if (is_env_image(s->d.background, u->images[k].texture) && !plan->lum.p) {
       const VimgTexture& t = s->textures[u->images[k].texture];
@@ -163,6 +189,8 @@ int enqueue_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan
     hipLaunchKernelGGL(scene_relight_flags, blocks_for(n), dim3(kBlock), 0, st, d, n);
     hipLaunchKernelGGL(scene_relight_cls, blocks_for(s->num_leaf_prims), dim3(kBlock), 0, st, d, s->num_leaf_prims);
   }
+  if (plan->new_dmaterials.p)   // (after both copies: a record reads its material and its colour texture)
+    if (int rc = enqueue_material_bake(d, static_cast<uint32_t>(s->materials.size()), plan->new_dmaterials.as<DMaterial>(), st)) return rc;
   // 3. emitters: the new list into its new buffers, or the resident list again with the new materials' emission
   if (u->set_lights) {
     if (u->num_lights) {
@@ -185,6 +213,11 @@ void commit_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan
   if (u->background) {
     d.background = *u->background;
     d.background_emissive = background_is_emissive(d.background);
+  }
+  if (plan->new_dmaterials.p) {   // (the same size: the scene's bytes stay)
+    DevBuf& dmaterials = s->tables[s->dmaterials_table];
+    dmaterials = std::move(plan->new_dmaterials);
+    d.dmaterials = (decltype(d.dmaterials))dmaterials.p;
   }
   s->textured = tables_textured(s->materials.data(), static_cast<uint32_t>(s->materials.size()), s->textures.data(), d.background);
   if (u->set_lights) {

@@ -417,6 +417,15 @@ int upload_tables(VimgDeviceScene* s, const VimgScene* sc, const Tree& t, const 
   UP(cdf_pool, sc->cdf_pool, sc->num_cdf);
 #undef UP
 #undef UP_TO
+  {   // the baked material records: filled by a kernel, from the materials and texture records now resident
+    DevBuf& b = s->tables.emplace_back();
+    if (int rc = b.alloc(std::max<size_t>(sc->num_materials, 1) * sizeof(DMaterial))) return rc;
+    s->total_bytes += b.bytes;
+    s->dmaterials_table = s->tables.size() - 1;
+    d.dmaterials = (decltype(d.dmaterials))b.p;
+    if (int rc = enqueue_material_bake(d, sc->num_materials, b.as<DMaterial>(), nullptr)) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
   if (!t.chain_leaf.empty()) {   // (refit bookkeeping: not counted in the scene's bytes)
     if (int rc = s->chain_leaf.alloc(t.chain_leaf.size() * sizeof(uint32_t))) return rc;
     HIP_TRY(hipMemcpy(s->chain_leaf.p, t.chain_leaf.data(), s->chain_leaf.bytes, hipMemcpyHostToDevice));
