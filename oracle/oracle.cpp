@@ -2161,6 +2161,27 @@ int oracle_probe(const VimgScene* scene, int kind, int n, const float* in, float
         }
         break;
       }
+      case ORACLE_PROBE_CONES: {
+        // the cone after the closest hit, through the helpers the integrators call with the arguments they
+        // pass (render loops above): the surface term from the cone's width as it stands and the shading
+        // normal, the reflected cone from twice that term and |o - hit_p|, the refracted cone from the term,
+        // eta and the outgoing direction
+        const float* p = in + 12 * i;
+        float* o = out + 8 * i;
+        std::fill(o, o + 8, 0.f);
+        HitInfo h;
+        Ray r;
+        if (trace(p, h, r)) {
+          const RayCone cone{p[6], p[7]};
+          const float hit_dist = length(r.o - h.hit_p);
+          const float ssa = spread_angle_from_curvature(h.mean_curvature, cone.cone_width, r.dir, h.hit_n_s);
+          const RayCone refl = propagate_reflect_cone(cone, ssa * 2.f, hit_dist);
+          const RayCone refr = propagate_refract_cone(cone, r.dir, h.hit_p, ssa, p[8], vec3{p[9], p[10], p[11]});
+          o[0] = 1.f, o[1] = ssa, o[2] = hit_dist, o[3] = refl.cone_width, o[4] = refl.spread_angle;
+          o[5] = refr.cone_width, o[6] = refr.spread_angle;
+        }
+        break;
+      }
       default:
         return -1;
     }

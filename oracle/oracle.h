@@ -54,8 +54,10 @@ enum {
   ORACLE_PROBE_BSDF_SAMPLE = 5,  /* in 8: o3 d3 seed regularize      out 7: hit has wo3 eta spec */
   ORACLE_PROBE_LIGHT_SAMPLE = 6, /* in 4: p3 seed                    out 10: Le3 wi3 pdf dist G */
   ORACLE_PROBE_BACKGROUND = 7,   /* in 5: d3 cone2                   out 4: emit3 pdf */
-  ORACLE_PROBE_MATERIAL_INPUTS = 9 /* in 8: o3 d3 cone2              out 8: hit col3 metallic roughness lod mat
+  ORACLE_PROBE_MATERIAL_INPUTS = 9, /* in 8: o3 d3 cone2             out 8: hit col3 metallic roughness lod mat
                                       (8 is the HIP probe's sincos check, which has no oracle side) */
+  ORACLE_PROBE_CONES = 10        /* in 12: o3 d3 cone2 eta wo3       out 8: hit surface_spread hit_dist
+                                      reflected cone2 refracted cone2 0 */
 };
 int oracle_probe(const VimgScene* scene, int kind, int n, const float* in, float* out);
 

@@ -15,7 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_CAMERA_RAY, PROBE_CLOSEST_HIT, PROBE_OCCLUDED, PROBE_BSDF_EVAL, PROBE_BSDF_SAMPLE, \
     PROBE_LIGHT_SAMPLE, PROBE_BACKGROUND = 1, 2, 3, 4, 5, 6, 7
 PROBE_MATERIAL_INPUTS = 9   # 8 is the HIP probe's sincos check: it has no oracle side
-PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 9: (8, 8)}
+PROBE_CONES = 10            # the cone after the closest hit: surface term, hit distance, reflected and refracted cone
+PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 9: (8, 8), 10: (12, 8)}
 
 _libs = {}
 

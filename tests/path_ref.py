@@ -11,6 +11,7 @@ it models.  Where the reference departs from the textbook the departure is model
   texture_lod                    include/texture/texture_RGB.h:138-149, src/image_texture.cpp:162-172
   dir_to_uv, uv_to_dir, env_*    include/background.h:25-179, include/rng/sampling.h:107-197
   thin_lens_ray, cone_*          src/tl_camera.cpp:6-53, include/ray.h:36-60
+  cone_surface_spread, cone_reflect, cone_refract     include/ray.h:52-174 (Q29-Q32)
   shading_frame                  src/geometry/triangle.cpp:13-153, include/hit_utils.h:32-59
 
 The mip chain itself is prestep_ref.mip_chain (pinned against the host library there)."""
@@ -134,6 +135,81 @@ def cone_spread(vfov_deg, res_y):
 def cone_width_at(spread, t, width0=0.0):
     """Width of a cone of the given spread after a distance t (small-angle form the reference uses)."""
     return np.abs(spread * np.asarray(t, D) + width0)
+
+
+# --------------------------------------------------------------------------- ray cones beyond the first hit
+def cone_surface_spread(curvature, width, d, n):
+    """The angle by which the surface normal turns across the cone's footprint: a cone of width w meets a surface
+    seen under cos = -d . n in a footprint w / cos long, and the normal of a surface of mean curvature H turns by H
+    per unit of length: beta = H w / cos.  Signed: seen from behind (d . n > 0) the same surface curves the other
+    way.  As the reference has it: the width is the cone's width as it stands at the ray's ORIGIN, not grown to the
+    hit (Q29), and |cos| < 1e-5 is replaced by 1e-5 with the sign of cos, a cos of exactly 0 counting as negative."""
+    cos = -np.sum(np.asarray(d, D) * np.asarray(n, D), -1)
+    cos = np.where(np.abs(cos) < 1e-5, np.where(cos > 0, 1e-5, -1e-5), cos)
+    return np.asarray(curvature, D) * np.asarray(width, D) / cos
+
+
+def cone_reflect(width, spread, t, beta):
+    """The cone after travelling t and reflecting: it has grown to |w + spread t| (small-angle form), and a mirror whose
+    normal turns by beta across the footprint turns the two boundary rays apart by 2 beta."""
+    return np.abs(np.asarray(width, D) + np.asarray(spread, D) * np.asarray(t, D)), np.asarray(spread, D) + 2.0 * np.asarray(beta, D)
+
+
+def _wrap_angle(a):
+    return (a + np.pi) % (2.0 * np.pi) - np.pi
+
+
+def cone_refract(width, spread, beta, eta, d, wo, details=False):
+    """The cone after refraction, from the ray-cone construction in the plane of incidence, by angles (all angles
+    counter-clockwise from the x axis; the surface is the line y = 0, its normal +y, x along the tangential part of d):
+
+      - the two boundary rays of the incoming cone start w / 2 to either side of the axis and run at -+ spread / 2 to
+        it until they meet the surface, at x_u and x_l;
+      - there the normal is tilted by -+ beta / 2 (away from each other on a convex surface);
+      - each boundary ray is refracted by Snell's law about its own normal, sin(theta_t) = eta sin(theta_i); a
+        boundary ray beyond the critical angle runs on along the (tilted) surface, theta_t = +-90 degrees;
+      - the new spread is the signed angle between the two refracted rays, the new width their separation measured
+        across the refracted axis wo, where they cross the line through the origin perpendicular to it.
+
+    As the reference has it: the plane's normal is -(eta wo + d) normalised (Q30: for the wo and eta its materials
+    pass that is not the surface normal, which is along d - wo / eta'), eta is used as passed (Q31: the materials pass
+    n_t / n_i, Snell's law in this form wants n_i / n_t), the width is taken as it stands, without spread * t (Q32),
+    the boundary rays are labelled by the sign of the width (a width of 0 counting as negative) and the tilt by which
+    of them meets the surface further along x."""
+    width, spread, beta, eta = (np.asarray(a, D) for a in (width, spread, beta, eta))
+    d, wo = np.asarray(d, D), np.asarray(wo, D)
+    m = eta[..., None] * wo + d
+    N = -m / np.linalg.norm(m, axis=-1, keepdims=True)
+    tang = d - N * np.sum(N * d, -1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        X = tang / np.linalg.norm(tang, axis=-1, keepdims=True)         # 0 / 0 for eta = 1, where wo = d (Q30)
+    phi_i = np.arctan2(np.sum(d * N, -1), np.sum(d * X, -1))
+    phi_o = np.arctan2(np.sum(wo * N, -1), np.sum(wo * X, -1))
+    s = np.where(width > 0, 1.0, -1.0)
+    phi_u, phi_l = phi_i + spread * s * 0.5, phi_i - spread * s * 0.5
+    # the boundary rays' starting points, w / 2 to the left of the axis (u) and to its right (l)
+    sx, sy = -np.sin(phi_i) * width * 0.5, np.cos(phi_i) * width * 0.5
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x_u = sx - sy / np.tan(phi_u)
+        x_l = -sx + sy / np.tan(phi_l)
+    sign = np.where(x_u > x_l, 1.0, -1.0)
+    tilt = -beta * sign * 0.5
+    out, tir = [], []
+    for phi, psi in ((phi_u, np.pi / 2 + tilt), (phi_l, np.pi / 2 - tilt)):
+        theta_i = _wrap_angle(phi - (psi + np.pi))             # from the inward normal to the ray
+        sin_t = eta * np.sin(theta_i)
+        tir.append(np.abs(sin_t) > 1.0)
+        out.append(psi + np.pi + np.arcsin(np.clip(sin_t, -1.0, 1.0)))
+    new_spread = sign * _wrap_angle(out[0] - out[1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lam_u = -x_u * np.sin(out[0]) / np.cos(out[0] - phi_o)
+        lam_l = -x_l * np.sin(out[1]) / np.cos(out[1] - phi_o)
+    new_width = lam_u - lam_l
+    if details:
+        return new_width, new_spread, dict(tir_u=tir[0], tir_l=tir[1], phi_i=phi_i, phi_o=phi_o, x_u=x_u, x_l=x_l,
+                                           out_u=out[0], out_l=out[1], normal=N,
+                                           tangential=np.linalg.norm(tang, axis=-1))
+    return new_width, new_spread
 
 
 # ------------------------------------------------------------------------------------------- env map

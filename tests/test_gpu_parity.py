@@ -822,6 +822,14 @@ def test_precompute_mip_chain_is_byte_identical_to_the_host_build(w, h, wrap_u, 
         assert (lw, lh) == (max(w >> l, 1), max(h >> l, 1))
     want = host_texels[base:base + gpu.shape[0]]
     assert np.array_equal(gpu.view(np.uint32), want.view(np.uint32))
+    # and against the independent restatement (tests/prestep_ref.py), not only the product's own host loops
+    import prestep_ref as R
+    ref = R.mip_chain(img, wrap_u, wrap_v)
+    assert len(ref) == len(levels)
+    for l, (off, lw, lh) in enumerate(levels):
+        assert ref[l].shape == (lh, lw, 3)
+        got = gpu[off:off + lw * lh].reshape(lh, lw, 3)
+        assert np.array_equal(got.view(np.uint32), ref[l].view(np.uint32)), (l, np.abs(got - ref[l]).max())
 
 
 @pytest.mark.parametrize("w,h", [(32, 16), (200, 100), (65, 3), (1, 1), (2048, 1024)])
@@ -855,6 +863,11 @@ def test_precompute_env_cdfs_are_byte_identical_to_the_host_build(w, h):
     row_g, col_g = hip.build_env_cdfs(img)
     assert np.array_equal(row_g.view(np.uint32), row_h.view(np.uint32))
     assert np.array_equal(col_g.view(np.uint32), col_h.view(np.uint32))
+    # and against the independent restatement (tests/prestep_ref.py), not only the product's own host loops
+    import prestep_ref as R
+    row_r, col_r = R.env_cdfs(img)
+    assert np.array_equal(row_g.view(np.uint32), row_r.view(np.uint32))
+    assert np.array_equal(col_g.view(np.uint32), col_r.view(np.uint32))
     # and through the hook: the host library assembling a scene with the GPU builders installed
     hip.install_gpu_precompute(True)
     try:

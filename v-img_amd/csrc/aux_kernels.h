@@ -29,7 +29,7 @@ __global__ void assemble_kernel(const float* __restrict__ shards, float* __restr
 enum {
   PROBE_CAMERA_RAY = 1, PROBE_CLOSEST_HIT = 2, PROBE_OCCLUDED = 3, PROBE_BSDF_EVAL = 4,
   PROBE_BSDF_SAMPLE = 5, PROBE_LIGHT_SAMPLE = 6, PROBE_BACKGROUND = 7, PROBE_SINCOS = 8,
-  PROBE_MATERIAL_INPUTS = 9
+  PROBE_MATERIAL_INPUTS = 9, PROBE_CONES = 10
 };
 // ImageTexture::compute_texture_LOD (reference include/texture/texture_RGB.h:138-149) as col_at_ray_hit
 // evaluates it in line.  PROBE_MATERIAL_INPUTS reports it beside the colour that col_at_ray_hit itself
@@ -191,6 +191,27 @@ probe_kernel(const DScene g, const RenderArgs A, int kind, int n, const float* _
         }
         o[0] = 1.f, o[1] = col.x, o[2] = col.y, o[3] = col.z, o[4] = metallic, o[5] = roughness;
         o[6] = lambda, o[7] = static_cast<float>(h.mat);
+      }
+      break;
+    }
+    case PROBE_CONES: {
+      // the cone after the closest hit, through the helpers the integrators call with the arguments they pass
+      // (render_kernels.h, render_cu_kernel.h): the surface term from the cone's width as it stands and the shading
+      // normal, the reflected cone from twice that term and |o - hit_p|, the refracted cone from the term, eta and
+      // the outgoing direction.  (`trace` asks for the full hit record, curvature included, in either build.)
+      const float* p = in + 12 * i;
+      float* o = out + 8 * i;
+      for (int k = 0; k < 8; ++k) o[k] = 0.f;
+      Hit h;
+      TravRay tr;
+      if (trace(p, h, tr)) {
+        const RayCone cone{p[6], p[7]};
+        const float hit_dist = length(tr.o - h.p);
+        const float ssa = spread_angle_from_curvature(h.curvature, cone.cone_width, tr.d, h.ns);
+        const RayCone refl = propagate_reflect_cone(cone, ssa * 2.f, hit_dist);
+        const RayCone refr = propagate_refract_cone(cone, tr.d, ssa, p[8], f3{p[9], p[10], p[11]});
+        o[0] = 1.f, o[1] = ssa, o[2] = hit_dist, o[3] = refl.cone_width, o[4] = refl.spread_angle;
+        o[5] = refr.cone_width, o[6] = refr.spread_angle;
       }
       break;
     }

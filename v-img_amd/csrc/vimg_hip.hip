@@ -408,9 +408,9 @@ int vimg_hip_time_renders(VimgDeviceScene* s, const VimgRenderParams* p, void* d
 
 // Unit-level probe (declared here, not in vimg_hip.h: it is a test hook, not part of the seam).
 int vimg_hip_probe(VimgDeviceScene* s, int kind, int n, const float* in_host, float* out_host) {
-  static const int n_in[10] = {0, 4, 6, 7, 12, 8, 4, 5, 1, 8};
-  static const int n_out[10] = {0, 8, 28, 1, 5, 7, 10, 4, 5, 8};
-  if (!s || kind < 1 || kind > 9 || n <= 0 || !in_host || !out_host)
+  static const int n_in[11] = {0, 4, 6, 7, 12, 8, 4, 5, 1, 8, 12};
+  static const int n_out[11] = {0, 8, 28, 1, 5, 7, 10, 4, 5, 8, 8};
+  if (!s || kind < 1 || kind > 10 || n <= 0 || !in_host || !out_host)
     return fail(VIMG_E_INVALID, "probe: bad arguments");
   DevBuf d_in, d_out;
   if (int rc = d_in.alloc(size_t(n) * n_in[kind] * sizeof(float))) return rc;

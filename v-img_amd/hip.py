@@ -13,7 +13,7 @@ from .host import HostScene, camera_lookat, make_params
 
 
 # floats per item of DeviceScene.probe, kind -> (in, out): the n_in / n_out tables of vimg_hip_probe (csrc/vimg_hip.hip)
-PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 8: (1, 5), 9: (8, 8)}
+PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 8: (1, 5), 9: (8, 8), 10: (12, 8)}
 
 
 class HipError(RuntimeError):
