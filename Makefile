@@ -1,5 +1,6 @@
-# Build of the three shared libraries (no cmake: plain make + hipcc/g++).
+# Build of the four shared libraries (no cmake: plain make + hipcc/g++).
 #   v-img_amd/lib/libvimg_hip.so   hand-written gfx950 kernels + C ABI   (the product)
+#   v-img_amd/lib/libvimg_filter.so  scene-free filters over device frames (the a-trous denoiser)
 #   v-img_amd/lib/libvimg_host.so  host side: scene loading, SAH BVH, post (the product's host)
 #   oracle/liboracle.so            CPU restatement of the reference path  (test infrastructure)
 ROOT    := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
@@ -22,9 +23,10 @@ ORAFLAGS  := -std=c++20 -O3 -march=x86-64-v3 -fPIC -shared -ffp-contract=off -pt
 HIPFLAGS  := --offload-arch=$(ARCH) -std=c++20 -O3 -fPIC -shared -ffp-contract=off -fno-slp-vectorize \
              -fno-fast-math -Iinclude -Wall -Wno-unused-function
 
-all: host hip oracle oracle-avx2 cli
+all: host hip filter oracle oracle-avx2 cli
 host: $(LIBDIR)/libvimg_host.so
 hip: $(LIBDIR)/libvimg_hip.so
+filter: $(LIBDIR)/libvimg_filter.so
 oracle: oracle/liboracle.so
 cli: v-img_amd/bin/vimg-amd
 
@@ -54,10 +56,18 @@ $(LIBDIR)/libvimg_hip.so: $(HIPOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIPOBJ) -o $@
 
-# C++ host program (the counterpart of the reference's main): links both libraries by rpath
-v-img_amd/bin/vimg-amd: v-img_amd/cli/main.cpp $(LIBDIR)/libvimg_host.so $(LIBDIR)/libvimg_hip.so Makefile
+# the filter library: its own sources (v-img_amd/filter, NOT the csrc wildcard of libvimg_hip.so), its own header, the
+# same HIPFLAGS - its bit-level contract rests on -ffp-contract=off, -fno-fast-math and hipcc's correctly rounded
+# divide.  No -disable-machine-licm: its kernels have no loop left after unrolling
+FILTERSRC := $(wildcard v-img_amd/filter/*.hip)
+$(LIBDIR)/libvimg_filter.so: $(FILTERSRC) include/vimg_filter.h include/vimg_hip.h include/vimg_scene.h Makefile
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) $(FILTERSRC) -o $@
+
+# C++ host program (the counterpart of the reference's main): links the three product libraries by rpath
+v-img_amd/bin/vimg-amd: v-img_amd/cli/main.cpp $(LIBDIR)/libvimg_host.so $(LIBDIR)/libvimg_hip.so $(LIBDIR)/libvimg_filter.so Makefile
 	@mkdir -p v-img_amd/bin
-	$(HIPCC) -std=c++20 -O2 -Iinclude v-img_amd/cli/main.cpp -L$(LIBDIR) -lvimg_host -lvimg_hip \
+	$(HIPCC) -std=c++20 -O2 -Iinclude v-img_amd/cli/main.cpp -L$(LIBDIR) -lvimg_host -lvimg_hip -lvimg_filter \
 	  -Wl,-rpath,'$$ORIGIN/../lib' -o $@
 
 oracle/liboracle.so: $(ORASRC) $(ORAHDR) Makefile
@@ -79,4 +89,4 @@ oracle/liboracle_avx2.so: $(ORASRC) $(ORAHDR) Makefile
 clean:
 	rm -rf $(LIBDIR)/*.so oracle/*.so build/hip
 
-.PHONY: all host hip oracle oracle-avx2 cli clean
+.PHONY: all host hip filter oracle oracle-avx2 cli clean

@@ -1,4 +1,4 @@
-"""ctypes mirror of include/vimg_scene.h, include/vimg_host.h and include/vimg_hip.h.
+"""ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h and include/vimg_filter.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -319,6 +319,32 @@ HIP_TEST_SYMBOLS = {
 }
 
 
+class FilterFrames(C.Structure):
+    """VimgFilterFrames (include/vimg_filter.h): the frames of one picture, DEVICE pointers to float32 triples."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("color", C.c_void_p),
+                ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(FilterFrames)
+
+
+class AtrousParams(C.Structure):
+    """VimgAtrousParams (include/vimg_filter.h); vimg_filter_atrous_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("iterations", u32), ("sigma_color", f32), ("sigma_normal", f32),
+                ("sigma_plane", f32), ("albedo_floor", f32)]
+
+
+# the list of symbols include/vimg_filter.h declares: libvimg_filter.so, a library of its own beside libvimg_hip.so
+FILTER_SYMBOLS = {
+    "vimg_filter_atrous_defaults": (None, [C.POINTER(AtrousParams)]),
+    "vimg_filter_atrous_workspace": (C.c_uint64, [u32, u32]),
+    "vimg_filter_atrous": (C.c_int, [C.POINTER(FilterFrames), C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.c_void_p]),
+    "vimg_filter_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -329,6 +355,7 @@ def _bind(lib, table):
 
 _host_lib = None
 _hip_lib = None
+_filter_lib = None
 
 
 def host_lib():
@@ -359,3 +386,20 @@ def hip_lib():
             pass
         _hip_lib = _bind(_bind(C.CDLL(path), HIP_SYMBOLS), HIP_TEST_SYMBOLS)
     return _hip_lib
+
+
+def filter_lib():
+    """The filter library (include/vimg_filter.h).  As with the render path there is no CPU fallback: a missing
+    library raises."""
+    global _filter_lib
+    if _filter_lib is None:
+        path = os.path.join(LIB_DIR, "libvimg_filter.so")
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: run `make filter` (or __graft_entry__.build()); "
+                               "there is no CPU fallback for the filter")
+        try:                   # one HIP runtime per process, torch's: see hip_lib
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        _filter_lib = _bind(C.CDLL(path), FILTER_SYMBOLS)
+    return _filter_lib

@@ -7,7 +7,9 @@
 // after each; the last one is byte-identical to a plain run), -e target adaptive sampling on top of -p (increments
 // only where the estimated relative error of a pixel is above `target`, -s the cap per pixel), -a prefix (the feature
 // buffers of the frame beside the image: prefix_albedo.png, prefix_normal.png as (n + 1) / 2, prefix_depth.png
-// divided by the image's largest depth, all through the clamp tonemapper) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
+// divided by the image's largest depth, all through the clamp tonemapper), -n iterations (the picture written is the
+// a-trous filtered frame: libvimg_filter on the frame and its albedo / normal / position / depth feature frames at the
+// frame's sample count, with the library's other defaults; with -p every preview and the final file) and -o output path.  Scene loading, the SAH BVH build and PNG writing happen
 // here on the host (libvimg_host); the render and the post chain go through the C ABI of
 // libvimg_hip.
 #include <algorithm>
@@ -20,6 +22,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "vimg_filter.h"
 #include "vimg_hip.h"
 #include "vimg_host.h"
 
@@ -30,7 +33,7 @@ static double now_s() {
 int main(int argc, char** argv) {
   std::string scene_path, out_path = "v_img_amd.png", aux_prefix;
   int tonemapper = 0, bvh_type = VIMG_BVH_BINNED, px = -1, py = -1;   // clamp, as src/main.cpp:46
-  long spp_override = -1, prog_step = 0;
+  long spp_override = -1, prog_step = 0, filter_iterations = 0;
   float heatmap_max = -1.f, err_target = -1.f;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -49,22 +52,36 @@ int main(int argc, char** argv) {
     else if (a == "-m") heatmap_max = static_cast<float>(std::atof(next()));
     else if (a == "-o") out_path = next();
     else if (a == "-a") aux_prefix = next();
+    else if (a == "-n") {
+      // 1..12 as the library has it: 0, a negative value or no number at all must not write the unfiltered frame
+      char* end = nullptr;
+      const char* v = next();
+      filter_iterations = std::strtol(v, &end, 10);
+      if (end == v || *end != '\0' || filter_iterations < 1 || filter_iterations > long(VIMG_ATROUS_MAX_ITERATIONS)) {
+        std::fprintf(stderr, "-n iterations must be 1..%u, not \"%s\"\n", VIMG_ATROUS_MAX_ITERATIONS, v);
+        return 2;
+      }
+    }
     else if (a == "-d") {
       if (std::sscanf(next(), "%d %d", &px, &py) != 2) {
         std::fprintf(stderr, "-d needs \"x y\"\n");
         return 2;
       }
     } else {
-      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-o out.png]\n");
+      std::fprintf(stderr, "usage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-n iterations] [-o out.png]\n");
       return 2;
     }
   }
   if (err_target >= 0.f && prog_step <= 0) {   // adaptive sampling is a loop of increments: it needs their size
-    std::fprintf(stderr, "-e target needs -p step\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-o out.png]\n");
+    std::fprintf(stderr, "-e target needs -p step\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-n iterations] [-o out.png]\n");
     return 2;
   }
   if (!aux_prefix.empty() && (heatmap_max >= 0.f || px >= 0)) {   // feature buffers go beside a rendered image only
-    std::fprintf(stderr, "-a prefix goes with a rendered image: not with -m or -d\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-o out.png]\n");
+    std::fprintf(stderr, "-a prefix goes with a rendered image: not with -m or -d\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-n iterations] [-o out.png]\n");
+    return 2;
+  }
+  if (filter_iterations != 0 && (heatmap_max >= 0.f || px >= 0)) {   // as -a: the filter needs a rendered image
+    std::fprintf(stderr, "-n iterations goes with a rendered image: not with -m or -d\nusage: vimg-amd -f scene.json [-c 0..3] [-b 0|1] [-m factor] [-s spp] [-p step [-e target]] [-d \"x y\"] [-a prefix] [-n iterations] [-o out.png]\n");
     return 2;
   }
   if (scene_path.empty()) {
@@ -126,6 +143,52 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "hipMalloc failed\n");
     return 1;
   }
+  // -n: the guides of the frame, rendered once (they do not depend on the increments of -p), and the filter in
+  // place on d_rgb.  The filter only enqueues on the null stream, so the frame is waited for before the post chain.
+  float* d_guides[4] = {nullptr, nullptr, nullptr, nullptr};
+  void* d_work = nullptr;
+  auto denoise = [&]() -> bool {
+    if (filter_iterations == 0) return true;
+    static const uint32_t guide[4] = {VIMG_INTEGRATOR_ALBEDO, VIMG_INTEGRATOR_NORMAL, VIMG_INTEGRATOR_POSITION,
+                                      VIMG_INTEGRATOR_DEPTH};
+    const uint64_t work_bytes = vimg_filter_atrous_workspace(uint32_t(W), uint32_t(H));
+    if (!d_work) {
+      if (hipMalloc(&d_work, work_bytes) != hipSuccess) {
+        std::fprintf(stderr, "hipMalloc failed\n");
+        return false;
+      }
+      for (int g = 0; g < 4; ++g) {
+        VimgRenderParams q = params;
+        q.integrator = guide[g];
+        if (hipMalloc(reinterpret_cast<void**>(&d_guides[g]), n * 3 * sizeof(float)) != hipSuccess ||
+            vimg_hip_render(dev, &q, d_guides[g], nullptr, nullptr) != VIMG_OK) {
+          std::fprintf(stderr, "feature render failed: %s\n", vimg_hip_last_error());
+          return false;
+        }
+      }
+    }
+    VimgFilterFrames fr{};
+    fr.struct_size = sizeof fr;
+    fr.width = uint32_t(W);
+    fr.height = uint32_t(H);
+    fr.color = d_rgb;
+    fr.albedo = d_guides[0];
+    fr.normal = d_guides[1];
+    fr.position = d_guides[2];
+    fr.depth = d_guides[3];
+    VimgAtrousParams ap;
+    vimg_filter_atrous_defaults(&ap);
+    ap.iterations = static_cast<uint32_t>(filter_iterations);
+    if (vimg_filter_atrous(&fr, &ap, d_rgb, d_work, work_bytes, nullptr) != VIMG_OK) {
+      std::fprintf(stderr, "filter failed: %s\n", vimg_filter_last_error());
+      return false;
+    }
+    if (hipStreamSynchronize(nullptr) != hipSuccess) {
+      std::fprintf(stderr, "filter failed on the device\n");
+      return false;
+    }
+    return true;
+  };
   VimgRenderStats st;
   double t3 = now_s();
   if (heatmap) {
@@ -168,6 +231,7 @@ int main(int argc, char** argv) {
         return 1;
       }
       done += k;
+      if (!denoise()) return 1;
       if (vimg_hip_post_rgb8(d_rgb, W, H, tonemapper, d_rgb8, nullptr) != VIMG_OK ||
           hipMemcpy(rgb8.data(), d_rgb8, n * 3, hipMemcpyDeviceToHost) != hipSuccess ||
           vimg_host_write_png(out_path.c_str(), rgb8.data(), W, H) != 0) {
@@ -182,6 +246,7 @@ int main(int argc, char** argv) {
     }
     if (d_mask) (void)hipFree(d_mask);
     vimg_hip_progressive_free(acc);
+    filter_iterations = 0;   // (d_rgb is the last preview: filtered already)
   } else {
     if (vimg_hip_render(dev, &params, d_rgb, nullptr, &st) != VIMG_OK) {
       std::fprintf(stderr, "render failed: %s\n", vimg_hip_last_error());
@@ -193,6 +258,7 @@ int main(int argc, char** argv) {
                 t4 - t3, rays / (t4 - t3) / 1e6, rays / double(st.paths),
                 static_cast<unsigned long long>(st.nan_samples));
   }
+  if (!heatmap && !denoise()) return 1;
   if (vimg_hip_post_rgb8(d_rgb, W, H, tonemapper, d_rgb8, nullptr) != VIMG_OK) {
     std::fprintf(stderr, "post failed: %s\n", vimg_hip_last_error());
     return 1;
@@ -233,6 +299,8 @@ int main(int argc, char** argv) {
       std::printf("%s written to %s\n", f.name, path.c_str());
     }
   }
+  for (float* g : d_guides) (void)hipFree(g);
+  (void)hipFree(d_work);
   (void)hipFree(d_rgb);
   (void)hipFree(d_rgb8);
   vimg_hip_scene_free(dev);

@@ -168,6 +168,7 @@ class DeviceScene:
         self.num_materials, self.num_textures = int(v.num_materials), int(v.num_textures)
         self._image_sizes = {i: (int(v.textures[i].height), int(v.textures[i].width)) for i in range(v.num_textures)
                              if v.textures[i].type == abi.TEX_IMAGE}
+        self.generation = 0      # counts the edits of the resident scene: what a cached feature frame was rendered from
 
     @property
     def bytes(self):
@@ -219,6 +220,19 @@ class DeviceScene:
                 given = _device_tensor(given, f"render_features[{name}]", ("float32",), shape, out=True)[0]
             res[name] = self.render(p, out=given, stats=False, stream=stream)
         return res
+
+    def render_denoised(self, params, out=None, stream=None, **filter_kw):
+        """``render`` followed by the a-trous filter (vimg_amd.filter.atrous, include/vimg_filter.h) guided by the
+        frame's own feature frames: exactly render(params) + render_features(params, ("albedo", "normal",
+        "position", "depth")) + filter.atrous(..., **filter_kw).  Returns the filtered [H, W, 3] image (``out`` when
+        given); whole frames only."""
+        from . import filter as flt
+        if params.tile_world != 1:
+            raise ValueError("render_denoised: the filter reads whole frames, not shards (tile_world must be 1)")
+        noisy = self.render(params, stats=False, stream=stream)
+        guides = self.render_features(params, flt.GUIDES, stream=stream)
+        return flt.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
+                          stream=stream, **filter_kw)
 
     def _new_output(self, params, zero_slab=True):
         """A frame [H, W, 3] for these parameters, or the shard's compact slab [shard_pixels, 3] when tile_world > 1
@@ -298,6 +312,7 @@ class DeviceScene:
             if a is not None:
                 setattr(upd, name, table(a, rows, cols, name))
         self._fill_material_update(upd, table, keep, materials, textures, lights, background, images)
+        self.generation += 1
         with _Launch(stream, made, used) as sp:     # (blocking: the tables stay alive until it returns)
             _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
 
@@ -316,6 +331,7 @@ class DeviceScene:
         if builder not in abi.BUILDERS:
             raise ValueError(f"builder: expected one of {sorted(abi.BUILDERS)}, not {builder!r}")
         opts = abi.RebuildOptions(builder=abi.BUILDERS[builder])
+        self.generation += 1
         with _Launch(stream) as sp:
             _check(self._lib.vimg_hip_scene_rebuild_bvh(self._h, C.byref(opts), sp))
 
@@ -335,6 +351,7 @@ class DeviceScene:
             cam = look_from
         else:
             cam = camera_lookat(look_from, look_at, up, vfov_deg, self.resolution, aperture_radius, focal_dist)
+        self.generation += 1
         _check(self._lib.vimg_hip_scene_set_camera(self._h, C.byref(cam)))
 
     # ---- ray queries (vimg_hip_trace_rays, _occluded, _camera_rays) ----------------------------------
@@ -511,6 +528,7 @@ class Progressive:
         h = C.c_void_p()
         _check(self._lib.vimg_hip_progressive_create(dev._h, C.byref(self.params), C.byref(h)))
         self._h = h
+        self._guides = None          # ((scene generation, feature samples), the four feature frames) of the last preview
 
     def _handle(self):
         if not self._h:
@@ -556,6 +574,25 @@ class Progressive:
                                                                 C.byref(st) if stats else None))
         img = None if out is False else out
         return (img, st) if stats else img
+
+    def preview(self, samples, out=None, stream=None, feature_samples=4, **filter_kw):
+        """``render(samples)`` followed by the a-trous filter (vimg_amd.filter.atrous) on the running mean: the
+        denoised picture of the frame so far.  The accumulator is advanced exactly as by ``render`` and keeps the
+        unfiltered sums, so later increments and renders give the bits they would have given.  The guides -
+        render_features(("albedo", "normal", "position", "depth")) at ``feature_samples`` samples - do not depend on
+        the increments: they are rendered once and kept until the scene is edited (DeviceScene.generation).
+        Whole frames only.  ``filter_kw``: the parameters of filter.atrous."""
+        from . import filter as flt
+        if self.params.tile_world != 1:
+            raise ValueError("preview: the filter reads whole frames, not shards (tile_world must be 1)")
+        noisy = self.render(samples, stream=stream)
+        key = (self._dev.generation, int(feature_samples))
+        if self._guides is None or self._guides[0] != key:
+            p = abi.RenderParams.from_buffer_copy(self.params)
+            p.samples = int(feature_samples)
+            self._guides = (key, self._dev.render_features(p, flt.GUIDES, stream=stream))
+        g = self._guides[1]
+        return flt.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=out, stream=stream, **filter_kw)
 
     def state(self, stream=None):
         """The per-pixel records (vimg_hip_progressive_state) as CUDA tensors in ``pixel_shape``: a dict with
