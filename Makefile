@@ -1,6 +1,7 @@
-# Build of the four shared libraries (no cmake: plain make + hipcc/g++).
+# Build of the five shared libraries (no cmake: plain make + hipcc/g++).
 #   v-img_amd/lib/libvimg_hip.so   hand-written gfx950 kernels + C ABI   (the product)
 #   v-img_amd/lib/libvimg_filter.so  scene-free filters over device frames (the a-trous denoiser)
+#   v-img_amd/lib/libvimg_temporal.so  scene-free temporal accumulation over device frames (reprojection)
 #   v-img_amd/lib/libvimg_host.so  host side: scene loading, SAH BVH, post (the product's host)
 #   oracle/liboracle.so            CPU restatement of the reference path  (test infrastructure)
 ROOT    := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
@@ -23,10 +24,11 @@ ORAFLAGS  := -std=c++20 -O3 -march=x86-64-v3 -fPIC -shared -ffp-contract=off -pt
 HIPFLAGS  := --offload-arch=$(ARCH) -std=c++20 -O3 -fPIC -shared -ffp-contract=off -fno-slp-vectorize \
              -fno-fast-math -Iinclude -Wall -Wno-unused-function
 
-all: host hip filter oracle oracle-avx2 cli
+all: host hip filter temporal oracle oracle-avx2 cli
 host: $(LIBDIR)/libvimg_host.so
 hip: $(LIBDIR)/libvimg_hip.so
 filter: $(LIBDIR)/libvimg_filter.so
+temporal: $(LIBDIR)/libvimg_temporal.so
 oracle: oracle/liboracle.so
 cli: v-img_amd/bin/vimg-amd
 
@@ -64,6 +66,14 @@ $(LIBDIR)/libvimg_filter.so: $(FILTERSRC) include/vimg_filter.h include/vimg_hip
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(FILTERSRC) -o $@
 
+# the temporal library, built the way the filter library is: its own sources (v-img_amd/temporal), its own header, the
+# same HIPFLAGS for the same reason (a bit-level contract), the HIP runtime and nothing of the other two libraries.
+# No -disable-machine-licm: its one kernel has no loop left after unrolling
+TEMPORALSRC := $(wildcard v-img_amd/temporal/*.hip)
+$(LIBDIR)/libvimg_temporal.so: $(TEMPORALSRC) include/vimg_temporal.h include/vimg_hip.h include/vimg_scene.h Makefile
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) $(TEMPORALSRC) -o $@
+
 # C++ host program (the counterpart of the reference's main): links the three product libraries by rpath
 v-img_amd/bin/vimg-amd: v-img_amd/cli/main.cpp $(LIBDIR)/libvimg_host.so $(LIBDIR)/libvimg_hip.so $(LIBDIR)/libvimg_filter.so Makefile
 	@mkdir -p v-img_amd/bin
@@ -89,4 +99,4 @@ oracle/liboracle_avx2.so: $(ORASRC) $(ORAHDR) Makefile
 clean:
 	rm -rf $(LIBDIR)/*.so oracle/*.so build/hip
 
-.PHONY: all host hip filter oracle oracle-avx2 cli clean
+.PHONY: all host hip filter temporal oracle oracle-avx2 cli clean

@@ -1,4 +1,5 @@
-"""ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h and include/vimg_filter.h.
+"""ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h and
+include/vimg_temporal.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -345,6 +346,34 @@ FILTER_SYMBOLS = {
 }
 
 
+class TemporalFrames(C.Structure):
+    """VimgTemporalFrames (include/vimg_temporal.h): the current picture, DEVICE pointers to float32 triples."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("color", C.c_void_p),
+                ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(TemporalFrames)
+
+
+class TemporalParams(C.Structure):
+    """VimgTemporalParams (include/vimg_temporal.h); vimg_temporal_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("max_history", f32), ("current_weight", f32),
+                ("sigma_normal", f32), ("sigma_plane", f32)]
+
+
+TEMPORAL_HISTORY_PER_PIXEL = 48
+
+# the list of symbols include/vimg_temporal.h declares: libvimg_temporal.so, the third scene-free library
+TEMPORAL_SYMBOLS = {
+    "vimg_temporal_defaults": (None, [C.POINTER(TemporalParams)]),
+    "vimg_temporal_history_bytes": (C.c_uint64, [u32, u32]),
+    "vimg_temporal_accumulate": (C.c_int, [C.POINTER(TemporalFrames), C.c_void_p, Pf32, C.POINTER(TemporalParams), C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "vimg_temporal_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -356,6 +385,7 @@ def _bind(lib, table):
 _host_lib = None
 _hip_lib = None
 _filter_lib = None
+_temporal_lib = None
 
 
 def host_lib():
@@ -403,3 +433,19 @@ def filter_lib():
             pass
         _filter_lib = _bind(C.CDLL(path), FILTER_SYMBOLS)
     return _filter_lib
+
+
+def temporal_lib():
+    """The temporal accumulation library (include/vimg_temporal.h).  No CPU fallback: a missing library raises."""
+    global _temporal_lib
+    if _temporal_lib is None:
+        path = os.path.join(LIB_DIR, "libvimg_temporal.so")
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: run `make temporal` (or __graft_entry__.build()); "
+                               "there is no CPU fallback for temporal accumulation")
+        try:                   # one HIP runtime per process, torch's: see hip_lib
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        _temporal_lib = _bind(C.CDLL(path), TEMPORAL_SYMBOLS)
+    return _temporal_lib

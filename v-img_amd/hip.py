@@ -168,6 +168,7 @@ class DeviceScene:
         self.num_materials, self.num_textures = int(v.num_materials), int(v.num_textures)
         self._image_sizes = {i: (int(v.textures[i].height), int(v.textures[i].width)) for i in range(v.num_textures)
                              if v.textures[i].type == abi.TEX_IMAGE}
+        self.camera = abi.Camera.from_buffer_copy(v.camera)      # the camera of the next launch (set_camera replaces it)
         self.generation = 0      # counts the edits of the resident scene: what a cached feature frame was rendered from
 
     @property
@@ -233,6 +234,18 @@ class DeviceScene:
         guides = self.render_features(params, flt.GUIDES, stream=stream)
         return flt.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
                           stream=stream, **filter_kw)
+
+    def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, **temporal_kw):
+        """A preview that survives a moving camera (vimg_amd.temporal.TemporalPreview, include/vimg_temporal.h): its
+        ``frame()`` renders ``samples`` more samples of the scene as it now stands and returns the [H, W, 3] picture -
+        after set_camera or an edit blended with the last picture reprojected into the new camera, while nothing
+        changes the plain progressive stream blended with that history - filtered by filter.atrous when ``denoise``, its sigma_color divided by the square root of the frames accumulated.
+        ``temporal_kw``: max_history, sigma_normal, sigma_plane, ``filter_kw`` (a dict for filter.atrous),
+        ``scale_sigma_color`` (False: the filter's sigma_color as it is).  Whole
+        frames only."""
+        from . import temporal
+        return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
+                                        **temporal_kw)
 
     def _new_output(self, params, zero_slab=True):
         """A frame [H, W, 3] for these parameters, or the shard's compact slab [shard_pixels, 3] when tile_world > 1
@@ -353,6 +366,7 @@ class DeviceScene:
             cam = camera_lookat(look_from, look_at, up, vfov_deg, self.resolution, aperture_radius, focal_dist)
         self.generation += 1
         _check(self._lib.vimg_hip_scene_set_camera(self._h, C.byref(cam)))
+        self.camera = abi.Camera.from_buffer_copy(cam)
 
     # ---- ray queries (vimg_hip_trace_rays, _occluded, _camera_rays) ----------------------------------
     @staticmethod

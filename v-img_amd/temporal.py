@@ -1,0 +1,219 @@
+"""Temporal accumulation over frames in device memory: ctypes mirror of include/vimg_temporal.h
+(libvimg_temporal.so, gfx950).
+
+The third scene-free library: the last preview is reprojected into a moved camera by the `position`
+frame and blended with the current frame where normal and position say it is the same surface.  The binding shares the
+render binding's tensor check and stream rule (hip._device_tensor, hip._Launch).  There is no CPU fallback.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _abi as abi
+from .hip import HipError, _Launch, _device_tensor
+
+FRAMES = ("color", "normal", "position", "depth")
+PARAMS = ("max_history", "current_weight", "sigma_normal", "sigma_plane")
+
+
+def _lib():
+    return abi.temporal_lib()
+
+
+def _check(rc):
+    if rc < 0:
+        raise HipError(f"[{rc}] " + _lib().vimg_temporal_last_error().decode())
+    return rc
+
+
+def temporal_params(max_history=None, current_weight=None, sigma_normal=None, sigma_plane=None):
+    """An abi.TemporalParams: the library's defaults (vimg_temporal_defaults; include/vimg_temporal.h names them) with
+    the given values in place of them."""
+    p = abi.TemporalParams()
+    _lib().vimg_temporal_defaults(C.byref(p))
+    for name, v in zip(PARAMS, (max_history, current_weight, sigma_normal, sigma_plane)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def history_bytes(width, height):
+    return int(_lib().vimg_temporal_history_bytes(width, height))
+
+
+def world_to_pixel(camera):
+    """The 12 float32 of vimg_temporal_accumulate's matrix (row-major 3 x 4) for an abi.Camera: a world-space point
+    goes to (hx, hy, hw) with column hx / hw and row hy / hw in FRAME ARRAY coordinates - column = the renderer's
+    sample x, row = res_y - sample y, because vimg_hip_render stores sample row y at array row H - 1 - y.  The pinhole
+    through the lens centre (with aperture_radius > 0 this is the mapping of the lens centre), the inverse of the
+    rigid cam_to_world, the image plane of the reference's TLCam (height 2 tan(vfov / 2), width ratio times that, rays
+    along -z).  Computed in float64 and rounded once."""
+    c2w = np.array(list(camera.cam_to_world), dtype=np.float64).reshape(4, 4).T      # glm column-major
+    rot, org = c2w[:3, :3], c2w[:3, 3]
+    w2c = np.concatenate([rot.T, -(rot.T @ org)[:, None]], axis=1)                    # camera-space point = w2c [P; 1]
+    w, h = float(camera.res_x), float(camera.res_y)
+    ph = 2.0 * math.tan(math.radians(float(camera.vfov_deg)) / 2.0)
+    pw = (w / h) * ph
+    m = np.stack([(w / pw) * w2c[0] - (w / 2.0) * w2c[2],        # sample x = w (x_dir / pw + 1/2),  x_dir = Pc.x / -Pc.z
+                  -(h / ph) * w2c[1] - (h / 2.0) * w2c[2],       # row = h - sample y = h (1/2 - y_dir / ph)
+                  -w2c[2]])
+    return m.astype(np.float32).reshape(12)
+
+
+class History:
+    """One history of vimg_temporal_accumulate: ``tensor`` [3, H, W, 4] float32 (planes A = {rgb, length},
+    G0 = {normal, depth}, G1 = {position, 0}; a CUDA tensor, or a numpy array after a call with numpy frames) and
+    ``world_to_pixel``, the matrix of the camera its frame was rendered under (None: unknown, the history cannot be
+    reprojected).  ``color`` [H, W, 3] and ``length`` [H, W] are views."""
+
+    def __init__(self, tensor, world_to_pixel=None):
+        if len(tensor.shape) != 4 or tensor.shape[0] != 3 or tensor.shape[3] != 4:
+            raise ValueError(f"History: shape must be (3, H, W, 4), not {tuple(tensor.shape)}")
+        self.tensor = tensor
+        self.world_to_pixel = None if world_to_pixel is None else np.ascontiguousarray(world_to_pixel, dtype=np.float32).reshape(12)
+
+    @property
+    def color(self):
+        return self.tensor[0, :, :, :3]
+
+    @property
+    def length(self):
+        return self.tensor[0, :, :, 3]
+
+
+def accumulate(color, normal, position, depth, history=None, world_to_pixel=None, out=None, next_history=None, stream=None,
+               **params):
+    """One step of temporal accumulation (vimg_temporal_accumulate): the current ``color`` frame with its first-hit
+    frames ``normal``, ``position``, ``depth`` - all [H, W, 3] float32, as DeviceScene.render and render_features
+    return them - blended with ``history``, the History of the frame before (None: no history), which is looked up
+    where ``history.world_to_pixel`` sends each pixel's position.  Returns the next History; ``world_to_pixel`` is the
+    matrix of the CURRENT camera (temporal.world_to_pixel(camera)), which the result remembers for the next step.
+    CUDA tensors are read where they are; numpy arrays are copied up, and with a numpy ``color`` the History holds a
+    numpy array.  ``out``: a [H, W, 3] float32 CUDA tensor that gets the accumulated colour as packed triples, which
+    may be ``color`` itself; ``next_history``: the [3, H, W, 4] float32 CUDA tensor to write (not the one ``history``
+    holds), allocated when None.  ``params``: max_history, current_weight, sigma_normal, sigma_plane, default the
+    library's (include/vimg_temporal.h).  The call only enqueues, on ``stream`` or torch's current stream."""
+    import torch
+    shape = getattr(color, "shape", None)
+    if shape is None or len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"temporal color: shape must be (H, W, 3), not {None if shape is None else tuple(shape)}")
+    unknown = sorted(set(params) - set(PARAMS))
+    if unknown:
+        raise TypeError(f"temporal: unknown parameters {unknown}; expected some of {PARAMS}")
+    h, w = int(shape[0]), int(shape[1])
+    p = temporal_params(**params)
+    made, used, t = [], [], {}
+    for name, a in zip(FRAMES, (color, normal, position, depth)):
+        t[name], host = _device_tensor(a, f"temporal {name}", ("float32",), (h, w, 3))
+        (made if host else used).append(t[name])
+    to_host = not isinstance(color, torch.Tensor)
+    prev = matrix = None
+    if history is not None:
+        if not isinstance(history, History):
+            raise ValueError("temporal: history must be a temporal.History")
+        if history.world_to_pixel is None:
+            raise ValueError("temporal: the history does not know its world_to_pixel matrix")
+        prev, host = _device_tensor(history.tensor, "temporal history", ("float32",), (3, h, w, 4), aligned=True)
+        (made if host else used).append(prev)
+        matrix = (abi.f32 * 12)(*history.world_to_pixel.tolist())
+    if next_history is None:
+        next_history = torch.empty((3, h, w, 4), dtype=torch.float32, device="cuda")
+        made.append(next_history)
+    else:
+        used.append(_device_tensor(next_history, "temporal next_history", ("float32",), (3, h, w, 4), aligned=True, out=True)[0])
+    if out is not None:
+        used.append(_device_tensor(out, "temporal", ("float32",), (h, w, 3), out=True)[0])
+    frames = abi.TemporalFrames(width=w, height=h, **{k: v.data_ptr() for k, v in t.items()})
+    with _Launch(stream, made, used, to_host=to_host) as sp:
+        _check(_lib().vimg_temporal_accumulate(C.byref(frames), None if prev is None else C.c_void_p(prev.data_ptr()), matrix,
+                                               C.byref(p), C.c_void_p(next_history.data_ptr()),
+                                               None if out is None else C.c_void_p(out.data_ptr()), sp))
+    return History(next_history.cpu().numpy() if to_host else next_history, world_to_pixel)
+
+
+class TemporalPreview:
+    """The preview of a resident scene whose camera moves (DeviceScene.temporal_preview): one Progressive, two history
+    buffers and the a-trous workspace.  ``frame()`` returns the [H, W, 3] preview of the scene as it now stands.
+
+    When the scene changed since the last frame (DeviceScene.generation: set_camera, update_*, rebuild_bvh) the
+    accumulator is reset, the guides are rendered again, ``samples`` samples are rendered and blended with the last
+    frame's history, reprojected by the last camera's matrix, at current_weight 1.  When nothing changed the
+    accumulator goes on - it stays bit for bit what a Progressive alone would hold - and the running mean of its k
+    increments is blended, at current_weight k, with the history frozen at the last change: the picture converges to
+    the plain progressive image without a pop.  With ``denoise`` the a-trous filter runs on the accumulated colour for
+    the output only; the history keeps unfiltered radiance.  The filter's sigma_color (``filter_kw``'s, or the filter
+    library's default) is divided by sqrt(n), n = the frames accumulated since the last reset(), at most max_history:
+    its colour term measures colour differences against the noise it expects, and the noise of n accumulated frames is
+    1 / sqrt(n) of one frame's, so the filter does less as the history does more (the first frame is filtered as
+    Progressive.preview filters it).  It is one factor for the picture: pixels that have just started over are filtered
+    as lightly as the rest.  ``scale_sigma_color=False`` passes sigma_color as it is.
+
+    Limits: history from before a geometry or material edit is reprojected all the same and fades at 1 / max_history
+    per frame (``reset()`` drops it); a thin lens is treated as its pinhole; see include/vimg_temporal.h."""
+
+    def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=True,
+                 **temporal_kw):
+        import torch
+        from . import filter as flt
+        if params.tile_world != 1:
+            raise ValueError("temporal_preview: reprojection reads whole frames, not shards (tile_world must be 1)")
+        if int(samples) < 1 or int(feature_samples) < 1:
+            raise ValueError("temporal_preview: samples and feature_samples must be at least 1")
+        unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"})
+        if unknown:
+            raise TypeError(f"temporal_preview: unknown parameters {unknown}")
+        self._dev, self.samples, self.denoise, self.feature_samples = dev, int(samples), bool(denoise), int(feature_samples)
+        self.temporal_kw, self.filter_kw, self.scale_sigma_color = dict(temporal_kw), dict(filter_kw or {}), bool(scale_sigma_color)
+        self.acc = dev.progressive(params)
+        w, h = dev.resolution
+        self._buffers = [torch.empty((3, h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        self._workspace = torch.empty((flt.atrous_workspace_bytes(w, h),), dtype=torch.uint8, device="cuda") if denoise else None
+        self._features = flt.GUIDES if denoise else ("normal", "position", "depth")
+        self._sigma_color = float(self.filter_kw.pop("sigma_color", None) or flt.atrous_params().sigma_color) if denoise else None
+        self._max_history = float(temporal_params(max_history=temporal_kw.get("max_history")).max_history)
+        self.reset()
+
+    def reset(self):
+        """Drops the history: the next frame() starts over, as the first one did."""
+        self._frozen = None        # the History of the last frame before the last change, or None
+        self.history = None        # the History of the last frame(): unfiltered radiance, lengths, guides
+        self._write = 0            # which buffer the frames since the last change write
+        self._generation = None
+        self._guides = None
+        self._k = 0
+        self._frames = 0           # frames accumulated since the reset: the nominal history length of the next output
+
+    def frame(self, out=None, stream=None):
+        """The preview of the scene as it now stands: ``samples`` more samples, accumulated; [H, W, 3] float32 CUDA
+        tensor (``out`` when given)."""
+        from . import filter as flt
+        dev, acc = self._dev, self.acc
+        if self._generation != dev.generation:
+            acc.reset(stream=stream)
+            p = abi.RenderParams.from_buffer_copy(acc.params)
+            p.samples = self.feature_samples
+            self._guides = dev.render_features(p, self._features, stream=stream)
+            if self.history is not None:           # the last frame's history freezes; the other buffer is written from now on
+                self._frozen, self._write = self.history, 1 - self._write
+            self._generation, self._k = dev.generation, 0
+        mean = acc.render(self.samples, stream=stream)
+        self._k += 1
+        g = self._guides
+        target = mean if out is None else out
+        self.history = accumulate(mean, g["normal"], g["position"], g["depth"], history=self._frozen,
+                                  world_to_pixel=world_to_pixel(dev.camera), out=target, next_history=self._buffers[self._write],
+                                  stream=stream, current_weight=self._k, **self.temporal_kw)
+        self._frames += 1
+        if self.denoise:
+            n = min(float(self._frames), self._max_history) if self.scale_sigma_color else 1.0
+            sigma_color = self._sigma_color / math.sqrt(n)
+            flt.atrous(target, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=target, workspace=self._workspace,
+                       stream=stream, sigma_color=sigma_color, **self.filter_kw)
+        return target
+
+    def close(self):
+        self.acc.close()
+
+
+__all__ = ["accumulate", "temporal_params", "history_bytes", "world_to_pixel", "History", "TemporalPreview", "FRAMES"]

@@ -1,0 +1,213 @@
+// libvimg_temporal.so: the temporal accumulation of include/vimg_temporal.h.
+//
+// One kernel over a history of three float4 planes [3][h][w]:
+//   A    {r, g, b, L}         accumulated radiance, history length (0: no surface)
+//   G0   {n.x, n.y, n.z, z}
+//   G1   {P.x, P.y, P.z, 0}
+// Launch shape as in the filter library: one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of
+// one row.  The current frame's reads (packed triples) and all writes are contiguous per wave; the up to four history
+// taps are gathers wherever the old camera saw the pixel's surface point, a whole float4 of plane A and xyz of the guide planes.  The tail is a
+// bounds test.  The matrix and the parameters travel as kernel arguments.
+//
+// The arithmetic is the header's contract, operation for operation: built with -ffp-contract=off and without
+// fast-math, so + - * / round once each, and the select forms below are the contract's comparisons (a NaN compares
+// false), never fmaxf / fminf.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+
+#include "vimg_temporal.h"
+
+namespace vimg_temporal {
+
+constexpr int WAVE_X = 64, ROWS = 4;    // blockDim: a wave per row segment, four rows per workgroup
+
+struct Constants {
+  float m[12];     // prev_world_to_pixel, row-major 3 x 4
+  float max_history, current_weight, sigma_normal, sigma_plane;
+};
+
+// `color` and `out` may be the same buffer: neither is __restrict__, and a lane reads its colour before it writes
+__global__ __launch_bounds__(WAVE_X * ROWS) void temporal_accumulate_kernel(
+    uint32_t w, uint32_t h, const float* color, const float* __restrict__ normal, const float* __restrict__ position,
+    const float* __restrict__ depth, const float4* __restrict__ prev, Constants k, float4* __restrict__ next, float* out) {
+  const int x = int(blockIdx.x * WAVE_X + threadIdx.x), y = int(blockIdx.y * ROWS + threadIdx.y);
+  if (uint32_t(x) >= w || uint32_t(y) >= h) return;
+  const size_t n = size_t(w) * h, p = size_t(y) * w + size_t(x), t = 3 * p;
+  const float z = depth[t];
+  const float cr = color[t], cg = color[t + 1], cb = color[t + 2];
+  const float nx = normal[t], ny = normal[t + 1], nz = normal[t + 2];
+  const float px = position[t], py = position[t + 1], pz = position[t + 2];
+  next[n + p] = make_float4(nx, ny, nz, z);
+  next[2 * n + p] = make_float4(px, py, pz, 0.f);
+
+  float4 a = make_float4(cr, cg, cb, 0.f);      // not live: a miss or a NaN depth
+  if (z > 0.f) {
+    a.w = 1.f;                                  // live without history
+    if (prev) {
+      const float hx = ((k.m[0] * px + k.m[1] * py) + k.m[2] * pz) + k.m[3];
+      const float hy = ((k.m[4] * px + k.m[5] * py) + k.m[6] * pz) + k.m[7];
+      const float hw = ((k.m[8] * px + k.m[9] * py) + k.m[10] * pz) + k.m[11];
+      if (hw > 0.f) {
+        const float fx = hx / hw - 0.5f, fy = hy / hw - 0.5f;
+        if (fx > -1.f && fx < float(w) && fy > -1.f && fy < float(h)) {
+          const float x0 = floorf(fx), y0 = floorf(fy);      // -1 .. w - 1, -1 .. h - 1: exact as int
+          const float tx = fx - x0, ty = fy - y0;
+          const float ux = 1.f - tx, uy = 1.f - ty;
+          const float b[4] = {ux * uy, tx * uy, ux * ty, tx * ty};
+          const int ix = int(x0), iy = int(y0);
+          const float sz = k.sigma_plane * z;
+          const float plane = sz * sz;
+          float sumb = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int qx = ix + (i & 1), qy = iy + (i >> 1);
+            if (uint32_t(qx) >= w || uint32_t(qy) >= h) continue;
+            if (!(b[i] > 0.f)) continue;
+            const size_t q = size_t(qy) * w + size_t(qx);
+            const float4 hq = prev[q];
+            if (!(hq.w > 0.f)) continue;
+            const float4 nq = prev[n + q];
+            const float dn = 1.f - ((nx * nq.x + ny * nq.y) + nz * nq.z);
+            if (!(dn < k.sigma_normal)) continue;
+            const float4 pq = prev[2 * n + q];
+            const float ex = pq.x - px, ey = pq.y - py, ez = pq.z - pz;
+            const float d = (nx * ex + ny * ey) + nz * ez;
+            if (!(d * d < plane)) continue;
+            sumb = sumb + b[i];
+            sr = sr + b[i] * hq.x;
+            sg = sg + b[i] * hq.y;
+            sb = sb + b[i] * hq.z;
+            sl = sl + b[i] * hq.w;
+          }
+          if (sumb > 0.f) {
+            const float hr = sr / sumb, hg = sg / sumb, hb = sb / sumb, len = sl / sumb;
+            float cnt = len + k.current_weight;
+            if (cnt > k.max_history) cnt = k.max_history;
+            float al = k.current_weight / cnt;
+            if (al > 1.f) al = 1.f;
+            a = make_float4(hr + (cr - hr) * al, hg + (cg - hg) * al, hb + (cb - hb) * al, cnt);
+          }
+        }
+      }
+    }
+  }
+  next[p] = a;
+  if (out) {
+    out[t] = a.x;
+    out[t + 1] = a.y;
+    out[t + 2] = a.z;
+  }
+}
+
+thread_local char g_error[256] = "";
+
+static int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(g_error, sizeof g_error, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+static bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+}  // namespace vimg_temporal
+
+using namespace vimg_temporal;
+
+extern "C" {
+
+void vimg_temporal_defaults(VimgTemporalParams* params) {
+  if (!params) return;
+  params->struct_size = sizeof(VimgTemporalParams);
+  params->reserved = 0;
+  params->max_history = 32.f;      // the header's "Defaults": checked by error figures measured on the GPU
+  params->current_weight = 1.f;
+  params->sigma_normal = 0.1f;
+  params->sigma_plane = 0.00005f;
+}
+
+uint64_t vimg_temporal_history_bytes(uint32_t width, uint32_t height) {
+  return uint64_t(VIMG_TEMPORAL_HISTORY_PER_PIXEL) * width * height;
+}
+
+int vimg_temporal_accumulate(const VimgTemporalFrames* f, const void* d_prev_history, const float prev_world_to_pixel[12],
+                             const VimgTemporalParams* a, void* d_next_history, void* d_out_rgb, void* stream) {
+  if (!f) return fail(VIMG_E_INVALID, "temporal: null frames");
+  if (!a) return fail(VIMG_E_INVALID, "temporal: null params");
+  if (f->struct_size < sizeof(VimgTemporalFrames))
+    return fail(VIMG_E_INVALID, "temporal: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgTemporalFrames));
+  if (a->struct_size < sizeof(VimgTemporalParams))
+    return fail(VIMG_E_INVALID, "temporal: params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(VimgTemporalParams));
+  if (f->width == 0 || f->height == 0 || f->width > VIMG_TEMPORAL_MAX_EXTENT || f->height > VIMG_TEMPORAL_MAX_EXTENT)
+    return fail(VIMG_E_INVALID, "temporal: width and height must be 1..%u, not %u x %u", VIMG_TEMPORAL_MAX_EXTENT, f->width, f->height);
+  if (!f->color || !f->normal || !f->position || !f->depth)
+    return fail(VIMG_E_INVALID, "temporal: null %s frame", !f->color ? "color" : !f->normal ? "normal" : !f->position ? "position" : "depth");
+  if (!d_next_history) return fail(VIMG_E_INVALID, "temporal: null next history");
+  if (!(a->max_history >= 1.f) || !std::isfinite(a->max_history))
+    return fail(VIMG_E_INVALID, "temporal: max_history must be >= 1 and finite, not %g", double(a->max_history));
+  if (!(a->current_weight >= 1.f) || !std::isfinite(a->current_weight))
+    return fail(VIMG_E_INVALID, "temporal: current_weight must be >= 1 and finite, not %g", double(a->current_weight));
+  if (!(a->sigma_normal > 0.f) || !std::isfinite(a->sigma_normal))
+    return fail(VIMG_E_INVALID, "temporal: sigma_normal must be > 0 and finite, not %g", double(a->sigma_normal));
+  if (!(a->sigma_plane > 0.f) || !std::isfinite(a->sigma_plane))
+    return fail(VIMG_E_INVALID, "temporal: sigma_plane must be > 0 and finite, not %g", double(a->sigma_plane));
+  if (reinterpret_cast<uintptr_t>(d_next_history) % 16)
+    return fail(VIMG_E_INVALID, "temporal: the next history must be 16-byte aligned");
+  Constants k{};
+  if (d_prev_history) {
+    if (reinterpret_cast<uintptr_t>(d_prev_history) % 16)
+      return fail(VIMG_E_INVALID, "temporal: the previous history must be 16-byte aligned");
+    if (!prev_world_to_pixel)
+      return fail(VIMG_E_INVALID, "temporal: a previous history needs its world-to-pixel matrix");
+  }
+  if (prev_world_to_pixel)
+    for (int i = 0; i < 12; ++i) {
+      if (!std::isfinite(prev_world_to_pixel[i]))
+        return fail(VIMG_E_INVALID, "temporal: world-to-pixel entry %d is not finite (%g)", i, double(prev_world_to_pixel[i]));
+      k.m[i] = prev_world_to_pixel[i];
+    }
+  const uint32_t w = f->width, h = f->height;
+  const uint64_t hist = vimg_temporal_history_bytes(w, h), frame = uint64_t(12) * w * h;
+  if (d_prev_history && overlaps(d_next_history, hist, d_prev_history, hist))
+    return fail(VIMG_E_INVALID, "temporal: the next history overlaps the previous one");
+  const void* frames[4] = {f->color, f->normal, f->position, f->depth};
+  const char* names[4] = {"color", "normal", "position", "depth"};
+  for (int i = 0; i < 4; ++i)
+    if (overlaps(d_next_history, hist, frames[i], frame))
+      return fail(VIMG_E_INVALID, "temporal: the next history overlaps the %s frame", names[i]);
+  if (d_out_rgb) {      // other lanes gather from prev and read the guides; only the colour frame itself may be the output
+    if (d_prev_history && overlaps(d_out_rgb, frame, d_prev_history, hist))
+      return fail(VIMG_E_INVALID, "temporal: the output overlaps the previous history");
+    if (overlaps(d_out_rgb, frame, d_next_history, hist))
+      return fail(VIMG_E_INVALID, "temporal: the output overlaps the next history");
+    for (int i = 0; i < 4; ++i)
+      if (overlaps(d_out_rgb, frame, frames[i], frame) && !(i == 0 && d_out_rgb == f->color))
+        return fail(VIMG_E_INVALID, i == 0 ? "temporal: the output overlaps the %s frame without being it"
+                                           : "temporal: the output overlaps the %s frame", names[i]);
+  }
+  k.max_history = a->max_history;
+  k.current_weight = a->current_weight;
+  k.sigma_normal = a->sigma_normal;
+  k.sigma_plane = a->sigma_plane;
+
+  const dim3 block(WAVE_X, ROWS), grid((w + WAVE_X - 1) / WAVE_X, (h + ROWS - 1) / ROWS);
+  // an error left by an earlier HIP call of this thread is not this call's and is cleared first
+  (void)hipGetLastError();
+  temporal_accumulate_kernel<<<grid, block, 0, static_cast<hipStream_t>(stream)>>>(
+      w, h, static_cast<const float*>(f->color), static_cast<const float*>(f->normal), static_cast<const float*>(f->position),
+      static_cast<const float*>(f->depth), static_cast<const float4*>(d_prev_history), k, static_cast<float4*>(d_next_history),
+      static_cast<float*>(d_out_rgb));
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? int(VIMG_OK) : fail(VIMG_E_DEVICE, "temporal: launch failed: %s", hipGetErrorString(e));
+}
+
+const char* vimg_temporal_last_error(void) { return g_error; }
+
+}  // extern "C"
