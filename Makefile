@@ -1,7 +1,7 @@
 # Build of the five shared libraries (no cmake: plain make + hipcc/g++).
 #   v-img_amd/lib/libvimg_hip.so   hand-written gfx950 kernels + C ABI   (the product)
-#   v-img_amd/lib/libvimg_filter.so  scene-free filters over device frames (the a-trous denoiser)
-#   v-img_amd/lib/libvimg_temporal.so  scene-free temporal accumulation over device frames (reprojection)
+#   v-img_amd/lib/libvimg_filter.so  scene-free filters over device frames (the a-trous denoiser)       } the frame
+#   v-img_amd/lib/libvimg_temporal.so  scene-free temporal accumulation over device frames (reprojection) } libraries
 #   v-img_amd/lib/libvimg_host.so  host side: scene loading, SAH BVH, post (the product's host)
 #   oracle/liboracle.so            CPU restatement of the reference path  (test infrastructure)
 ROOT    := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
@@ -16,6 +16,7 @@ HIPSRC  := $(wildcard v-img_amd/csrc/*.hip)
 HIPHDR  := $(wildcard v-img_amd/csrc/*.h) $(wildcard include/*.h)
 ORASRC  := $(wildcard oracle/*.cpp)
 ORAHDR  := $(wildcard oracle/*.h) $(wildcard include/*.h)
+FRAMELIBS := filter temporal
 
 # -ffp-contract=off everywhere: +,-,*,/,sqrt must round identically on CPU and GPU; fused
 # multiply-adds appear only where the reference writes std::fma.
@@ -24,11 +25,9 @@ ORAFLAGS  := -std=c++20 -O3 -march=x86-64-v3 -fPIC -shared -ffp-contract=off -pt
 HIPFLAGS  := --offload-arch=$(ARCH) -std=c++20 -O3 -fPIC -shared -ffp-contract=off -fno-slp-vectorize \
              -fno-fast-math -Iinclude -Wall -Wno-unused-function
 
-all: host hip filter temporal oracle oracle-avx2 cli
+all: host hip $(FRAMELIBS) oracle oracle-avx2 cli
 host: $(LIBDIR)/libvimg_host.so
 hip: $(LIBDIR)/libvimg_hip.so
-filter: $(LIBDIR)/libvimg_filter.so
-temporal: $(LIBDIR)/libvimg_temporal.so
 oracle: oracle/liboracle.so
 cli: v-img_amd/bin/vimg-amd
 
@@ -58,21 +57,17 @@ $(LIBDIR)/libvimg_hip.so: $(HIPOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIPOBJ) -o $@
 
-# the filter library: its own sources (v-img_amd/filter, NOT the csrc wildcard of libvimg_hip.so), its own header, the
-# same HIPFLAGS - its bit-level contract rests on -ffp-contract=off, -fno-fast-math and hipcc's correctly rounded
-# divide.  No -disable-machine-licm: its kernels have no loop left after unrolling
-FILTERSRC := $(wildcard v-img_amd/filter/*.hip)
-$(LIBDIR)/libvimg_filter.so: $(FILTERSRC) include/vimg_filter.h include/vimg_hip.h include/vimg_scene.h Makefile
+# the frame libraries, one per name in FRAMELIBS: libvimg_<name>.so from its own sources
+# v-img_amd/<name>/*.hip (NOT the csrc wildcard of libvimg_hip.so), the shared host skeleton v-img_amd/frames/*.h and
+# the public headers; each links the HIP runtime and nothing of the other libraries.  The same HIPFLAGS: their
+# bit-level contracts rest on -ffp-contract=off, -fno-fast-math and hipcc's correctly rounded divide.  No
+# -disable-machine-licm: their kernels have no loop left after unrolling
+FRAMEHDR  := $(wildcard v-img_amd/frames/*.h) $(wildcard include/*.h)
+$(FRAMELIBS): %: $(LIBDIR)/libvimg_%.so
+.SECONDEXPANSION:
+$(FRAMELIBS:%=$(LIBDIR)/libvimg_%.so): $(LIBDIR)/libvimg_%.so: $$(wildcard v-img_amd/$$*/*.hip) $(FRAMEHDR) Makefile
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) $(FILTERSRC) -o $@
-
-# the temporal library, built the way the filter library is: its own sources (v-img_amd/temporal), its own header, the
-# same HIPFLAGS for the same reason (a bit-level contract), the HIP runtime and nothing of the other two libraries.
-# No -disable-machine-licm: its one kernel has no loop left after unrolling
-TEMPORALSRC := $(wildcard v-img_amd/temporal/*.hip)
-$(LIBDIR)/libvimg_temporal.so: $(TEMPORALSRC) include/vimg_temporal.h include/vimg_hip.h include/vimg_scene.h Makefile
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) $(TEMPORALSRC) -o $@
+	$(HIPCC) $(HIPFLAGS) $(filter %.hip,$^) -o $@
 
 # C++ host program (the counterpart of the reference's main): links the three product libraries by rpath
 v-img_amd/bin/vimg-amd: v-img_amd/cli/main.cpp $(LIBDIR)/libvimg_host.so $(LIBDIR)/libvimg_hip.so $(LIBDIR)/libvimg_filter.so Makefile
@@ -99,4 +94,4 @@ oracle/liboracle_avx2.so: $(ORASRC) $(ORAHDR) Makefile
 clean:
 	rm -rf $(LIBDIR)/*.so oracle/*.so build/hip
 
-.PHONY: all host hip filter temporal oracle oracle-avx2 cli clean
+.PHONY: all host hip $(FRAMELIBS) oracle oracle-avx2 cli clean

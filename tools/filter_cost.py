@@ -23,26 +23,12 @@ import numpy as np
 import torch
 import scenes
 from vimg_amd import filter as flt, hip
+from _timing import timed
 
 # bytes per pixel: pack reads 4 or 5 frames of 12 B and writes 3 planes of 16 B; an iteration reads its own 3 x 16 B
 # and up to 24 taps x 3 x 16 B (through L2: neighbouring lanes and rows share them) and writes 16 B; unpack reads 16 B
 # + the albedo and writes 12 B
 BYTES = {"pack": 5 * 12 + 3 * 16, "iteration": 25 * 3 * 16 + 16, "unpack": 16 + 12 + 12}
-
-
-def timed(fn, steps):
-    """Median and best of `steps` calls of fn in ms, device events around each, after two warm-up calls."""
-    for _ in range(2):
-        fn()
-    ms = []
-    for _ in range(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms))
 
 
 def kernel_times(fn, steps, iterations):

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 import scenes
 from vimg_amd import filter as flt, hip, temporal
+from _timing import timed, wall
 
 ORBIT_STEPS, DEGREES = 8, 1.5
 MAX_HISTORY, SIGMA_NORMAL, SIGMA_PLANE = (2, 4, 8, 16, 32), (0.02, 0.1, 0.5), (0.00001, 0.00002, 0.00005, 0.0001, 0.0002, 0.0005, 0.002, 0.01)
@@ -47,21 +48,6 @@ def orbit_camera(name, i):
     a, r = math.radians(DEGREES * i), eye0 - pivot
     eye = pivot + np.array([r[0] * math.cos(a) + r[2] * math.sin(a), r[1], -r[0] * math.sin(a) + r[2] * math.cos(a)])
     return eye, eye + (at0 - eye0), (0.0, 1.0, 0.0), vfov
-
-
-def timed(fn, steps):
-    """Median and best of `steps` calls of fn in ms, device events around each, after two warm-up calls."""
-    for _ in range(2):
-        fn()
-    ms = []
-    for _ in range(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms))
 
 
 def rse(x, ref):
@@ -99,18 +85,6 @@ if not args.no_cost:
         acc = dev.progressive(p)
         row["mis_4spp_increment_ms"] = timed(lambda: acc.render(4, out=rgb), args.steps)
         acc.close()
-
-        def wall(fn, steps):
-            """Median of `steps` synchronised calls by the host clock, in ms, after two warm-up calls."""
-            import time
-            ms = []
-            for i in range(steps + 2):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fn(i)
-                torch.cuda.synchronize()
-                ms.append(1e3 * (time.perf_counter() - t0))
-            return float(np.median(ms[2:]))
 
         pv = dev.temporal_preview(p, samples=4)
 

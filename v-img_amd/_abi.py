@@ -128,22 +128,26 @@ class RenderStats(C.Structure):
         return int(self.closest_rays) + int(self.shadow_rays)
 
 
+class _Sized:
+    """Mixin of the structs that open with ``struct_size``: it is filled at construction."""
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(type(self))
+
+
 class TextureImage(C.Structure):
     """VimgTextureImage (include/vimg_hip.h): new level-0 texels (a DEVICE pointer) for one resident IMAGE texture."""
     _fields_ = [("texture", u32), ("reserved", u32), ("level0", C.c_void_p)]
 
 
-class GeometryUpdateV1(C.Structure):
+class GeometryUpdateV1(_Sized, C.Structure):
     """The first 32 bytes of VimgGeometryUpdate, the whole struct before the material update: what an older caller
     passes (struct_size 32)."""
     _fields_ = [("struct_size", u32), ("vertices", C.c_void_p), ("normals", C.c_void_p), ("spheres", C.c_void_p)]
 
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        self.struct_size = C.sizeof(GeometryUpdateV1)
 
-
-class GeometryUpdate(C.Structure):
+class GeometryUpdate(_Sized, C.Structure):
     """VimgGeometryUpdate (include/vimg_hip.h): device pointers to float32 tables, then host pointers to the new
     material, texture, light and background tables and the image list; NULL / 0 = unchanged."""
     _fields_ = GeometryUpdateV1._fields_ + [
@@ -151,22 +155,14 @@ class GeometryUpdate(C.Structure):
         ("num_lights", u32), ("set_lights", u32), ("background", C.POINTER(Background)),
         ("images", C.POINTER(TextureImage)), ("num_images", u32), ("reserved", u32)]
 
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        self.struct_size = C.sizeof(GeometryUpdate)
-
 
 BUILDER_PLOC, BUILDER_LBVH = 0, 1
 BUILDERS = {"ploc": BUILDER_PLOC, "lbvh": BUILDER_LBVH}
 
 
-class RebuildOptions(C.Structure):
+class RebuildOptions(_Sized, C.Structure):
     """VimgRebuildOptions (include/vimg_hip.h): the builder of vimg_hip_scene_rebuild_bvh."""
     _fields_ = [("struct_size", u32), ("builder", u32)]
-
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        self.struct_size = C.sizeof(RebuildOptions)
 
 
 class Ray(C.Structure):
@@ -320,14 +316,10 @@ HIP_TEST_SYMBOLS = {
 }
 
 
-class FilterFrames(C.Structure):
+class FilterFrames(_Sized, C.Structure):
     """VimgFilterFrames (include/vimg_filter.h): the frames of one picture, DEVICE pointers to float32 triples."""
     _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("color", C.c_void_p),
                 ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p)]
-
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        self.struct_size = C.sizeof(FilterFrames)
 
 
 class AtrousParams(C.Structure):
@@ -346,14 +338,10 @@ FILTER_SYMBOLS = {
 }
 
 
-class TemporalFrames(C.Structure):
+class TemporalFrames(_Sized, C.Structure):
     """VimgTemporalFrames (include/vimg_temporal.h): the current picture, DEVICE pointers to float32 triples."""
     _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("color", C.c_void_p),
                 ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p)]
-
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        self.struct_size = C.sizeof(TemporalFrames)
 
 
 class TemporalParams(C.Structure):
@@ -382,70 +370,52 @@ def _bind(lib, table):
     return lib
 
 
-_host_lib = None
-_hip_lib = None
-_filter_lib = None
-_temporal_lib = None
+# library -> (file, symbol tables, make target, tail of the "missing" message, import torch first).  Torch first: one
+# HIP runtime per process.  The torch wheel ships its own libamdhip64 / ROCr, and a second copy in the same process
+# cannot open the GPU; importing torch first makes the loader resolve our DT_NEEDED to the copy torch already mapped.
+_LIBRARIES = {
+    "host": ("libvimg_host.so", (HOST_SYMBOLS,), "host", "", False),
+    "hip": ("libvimg_hip.so", (HIP_SYMBOLS, HIP_TEST_SYMBOLS), "hip", "; there is no CPU fallback for the render path", True),
+    "filter": ("libvimg_filter.so", (FILTER_SYMBOLS,), "filter", "; there is no CPU fallback for the filter", True),
+    "temporal": ("libvimg_temporal.so", (TEMPORAL_SYMBOLS,), "temporal", "; there is no CPU fallback for temporal accumulation", True),
+}
+_loaded = {}
+
+
+def _load(name, path=None):
+    """The library ``name`` of _LIBRARIES, loaded and bound once.  A missing library raises: there is no fallback."""
+    lib = _loaded.get(name)
+    if lib is None:
+        file, tables, target, tail, torch_first = _LIBRARIES[name]
+        path = path or os.path.join(LIB_DIR, file)
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: run `make {target}` (or __graft_entry__.build()){tail}")
+        if torch_first:
+            try:
+                import torch  # noqa: F401
+            except ImportError:
+                pass
+        lib = C.CDLL(path)
+        for table in tables:
+            _bind(lib, table)
+        _loaded[name] = lib
+    return lib
 
 
 def host_lib():
-    global _host_lib
-    if _host_lib is None:
-        path = os.path.join(LIB_DIR, "libvimg_host.so")
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} is missing: run `make host` (or __graft_entry__.build())")
-        _host_lib = _bind(C.CDLL(path), HOST_SYMBOLS)
-    return _host_lib
+    return _load("host")
 
 
 def hip_lib():
-    """The HIP extension.  No CPU fallback exists: a missing library raises."""
-    global _hip_lib
-    if _hip_lib is None:
-        # VIMG_HIP_LIB selects another build of the same library (A/B measurements only)
-        path = os.environ.get("VIMG_HIP_LIB") or os.path.join(LIB_DIR, "libvimg_hip.so")
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} is missing: run `make hip` (or __graft_entry__.build()); "
-                               "there is no CPU fallback for the render path")
-        # One HIP runtime per process: the torch wheel ships its own libamdhip64 / ROCr, and a
-        # second copy in the same process cannot open the GPU.  Importing torch first makes the
-        # loader resolve our DT_NEEDED libamdhip64.so.7 to the copy torch already mapped.
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        _hip_lib = _bind(_bind(C.CDLL(path), HIP_SYMBOLS), HIP_TEST_SYMBOLS)
-    return _hip_lib
+    """The HIP extension; VIMG_HIP_LIB selects another build of the same library (A/B measurements only)."""
+    return _load("hip", os.environ.get("VIMG_HIP_LIB"))
 
 
 def filter_lib():
-    """The filter library (include/vimg_filter.h).  As with the render path there is no CPU fallback: a missing
-    library raises."""
-    global _filter_lib
-    if _filter_lib is None:
-        path = os.path.join(LIB_DIR, "libvimg_filter.so")
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} is missing: run `make filter` (or __graft_entry__.build()); "
-                               "there is no CPU fallback for the filter")
-        try:                   # one HIP runtime per process, torch's: see hip_lib
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        _filter_lib = _bind(C.CDLL(path), FILTER_SYMBOLS)
-    return _filter_lib
+    """The filter library (include/vimg_filter.h)."""
+    return _load("filter")
 
 
 def temporal_lib():
-    """The temporal accumulation library (include/vimg_temporal.h).  No CPU fallback: a missing library raises."""
-    global _temporal_lib
-    if _temporal_lib is None:
-        path = os.path.join(LIB_DIR, "libvimg_temporal.so")
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} is missing: run `make temporal` (or __graft_entry__.build()); "
-                               "there is no CPU fallback for temporal accumulation")
-        try:                   # one HIP runtime per process, torch's: see hip_lib
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        _temporal_lib = _bind(C.CDLL(path), TEMPORAL_SYMBOLS)
-    return _temporal_lib
+    """The temporal accumulation library (include/vimg_temporal.h)."""
+    return _load("temporal")

@@ -4,23 +4,20 @@
 //   C0, C1   the demodulated colour, ping-pong            {r, g, b, -}
 //   G0       {n.x, n.y, n.z, z}   (z > 0: the pixel is live)
 //   G1       {P.x, P.y, P.z, 0}
-// Launch shape: one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of one row and every
-// plane load of a tap is one contiguous 1 KiB request per wave, whatever the step.  The tail is a bounds test.
+// Launch shape (frames/frame_lib.h): one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of one
+// row and every plane load of a tap is one contiguous 1 KiB request per wave, whatever the step.
 //
 // The arithmetic is the header's contract, operation for operation: built with -ffp-contract=off and without
 // fast-math, so + - * / round once each, and the select forms below are the contract's comparisons (a NaN compares
 // false), never fmaxf / fminf.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-
 #include "vimg_filter.h"
+
+#define FRAME_LIB "atrous"
+#include "../frames/frame_lib.h"
 
 namespace vimg_filter {
 
-constexpr int WAVE_X = 64, ROWS = 4;    // blockDim: a wave per row segment, four rows per workgroup
+using namespace vimg_frames;
 
 struct Planes {
   float4* c0;
@@ -28,12 +25,6 @@ struct Planes {
   float4* g0;
   float4* g1;
 };
-
-__device__ inline bool pixel_of(uint32_t w, uint32_t h, int& x, int& y) {
-  x = int(blockIdx.x * WAVE_X + threadIdx.x);
-  y = int(blockIdx.y * ROWS + threadIdx.y);
-  return uint32_t(x) < w && uint32_t(y) < h;
-}
 
 __device__ inline float floored(float a, float floor) { return a > floor ? a : floor; }
 
@@ -131,19 +122,6 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void atrous_unpack_kernel(
   out[t + 2] = b;
 }
 
-thread_local char g_error[256] = "";
-
-static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-// > 0 and not NaN; finite unless `may_be_inf`
-static bool good_sigma(float v, bool may_be_inf) { return v > 0.f && (may_be_inf || std::isfinite(v)); }
-
 }  // namespace vimg_filter
 
 using namespace vimg_filter;
@@ -166,27 +144,14 @@ uint64_t vimg_filter_atrous_workspace(uint32_t width, uint32_t height) {
 
 int vimg_filter_atrous(const VimgFilterFrames* f, const VimgAtrousParams* a, void* d_out_rgb, void* d_workspace,
                        uint64_t workspace_bytes, void* stream) {
-  if (!f) return fail(VIMG_E_INVALID, "atrous: null frames");
-  if (!a) return fail(VIMG_E_INVALID, "atrous: null params");
-  if (f->struct_size < sizeof(VimgFilterFrames))
-    return fail(VIMG_E_INVALID, "atrous: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgFilterFrames));
-  if (a->struct_size < sizeof(VimgAtrousParams))
-    return fail(VIMG_E_INVALID, "atrous: params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(VimgAtrousParams));
-  if (f->width == 0 || f->height == 0 || f->width > VIMG_FILTER_MAX_EXTENT || f->height > VIMG_FILTER_MAX_EXTENT)
-    return fail(VIMG_E_INVALID, "atrous: width and height must be 1..%u, not %u x %u", VIMG_FILTER_MAX_EXTENT, f->width, f->height);
-  if (!f->color || !f->normal || !f->position || !f->depth)
-    return fail(VIMG_E_INVALID, "atrous: null %s frame", !f->color ? "color" : !f->normal ? "normal" : !f->position ? "position" : "depth");
+  if (const int rc = check_head(f, a, VIMG_FILTER_MAX_EXTENT)) return rc;
   if (!d_out_rgb) return fail(VIMG_E_INVALID, "atrous: null output");
   if (a->iterations < 1 || a->iterations > VIMG_ATROUS_MAX_ITERATIONS)
     return fail(VIMG_E_INVALID, "atrous: iterations must be 1..%u, not %u", VIMG_ATROUS_MAX_ITERATIONS, a->iterations);
-  if (!good_sigma(a->sigma_color, true))
-    return fail(VIMG_E_INVALID, "atrous: sigma_color must be > 0 (it may be +inf), not %g", double(a->sigma_color));
-  if (!good_sigma(a->sigma_normal, false))
-    return fail(VIMG_E_INVALID, "atrous: sigma_normal must be > 0 and finite, not %g", double(a->sigma_normal));
-  if (!good_sigma(a->sigma_plane, false))
-    return fail(VIMG_E_INVALID, "atrous: sigma_plane must be > 0 and finite, not %g", double(a->sigma_plane));
-  if (!good_sigma(a->albedo_floor, false))
-    return fail(VIMG_E_INVALID, "atrous: albedo_floor must be > 0 and finite, not %g", double(a->albedo_floor));
+  if (const int rc = check_float("sigma_color", a->sigma_color, 0.f, true, true)) return rc;
+  if (const int rc = check_float("sigma_normal", a->sigma_normal, 0.f, true, false)) return rc;
+  if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
+  if (const int rc = check_float("albedo_floor", a->albedo_floor, 0.f, true, false)) return rc;
   if (!d_workspace) return fail(VIMG_E_INVALID, "atrous: null workspace");
   const uint64_t need = vimg_filter_atrous_workspace(f->width, f->height);
   if (workspace_bytes < need)
@@ -199,17 +164,11 @@ int vimg_filter_atrous(const VimgFilterFrames* f, const VimgAtrousParams* a, voi
   const size_t n = size_t(w) * h;
   float4* base = static_cast<float4*>(d_workspace);
   const Planes pl{base, base + n, base + 2 * n, base + 3 * n};
-  const dim3 block(WAVE_X, ROWS), grid((w + WAVE_X - 1) / WAVE_X, (h + ROWS - 1) / ROWS);
+  const dim3 block = pixel_block(), grid = pixel_grid(w, h);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* albedo = static_cast<const float*>(f->albedo);
 
-  // a launch's refusal is read right after it, so nothing is enqueued behind a stage that did not start; an error left
-  // by an earlier HIP call of this thread is not this call's and is cleared first
-  (void)hipGetLastError();
-  auto launched = [](const char* stage) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? int(VIMG_OK) : fail(VIMG_E_DEVICE, "atrous: %s launch failed: %s", stage, hipGetErrorString(e));
-  };
+  clear_stale_error();
   atrous_pack_kernel<<<grid, block, 0, s>>>(w, h, static_cast<const float*>(f->color), static_cast<const float*>(f->normal),
                                             static_cast<const float*>(f->position), static_cast<const float*>(f->depth), albedo,
                                             a->albedo_floor, pl.c0, pl.g0, pl.g1);

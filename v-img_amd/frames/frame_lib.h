@@ -1,0 +1,95 @@
+// The host skeleton of a frame library (libvimg_filter.so, libvimg_temporal.so): the error slot, the
+// argument checks every frame library starts with, the launch shape and the launch check.  Internal: not installed,
+// not in include/.  A unit #defines FRAME_LIB ("atrous") before it includes this: it opens every sentence made here.
+// Everything is in an anonymous namespace: each library gets its own copy, and above all its own error slot.  One
+// inline variable of default visibility would be one weak symbol in two libraries, which the dynamic linker may
+// merge - vimg_filter_last_error() would then return the temporal library's message.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+#include "vimg_hip.h"
+
+#ifndef FRAME_LIB
+#error "define FRAME_LIB, the prefix of the library's error sentences, before including frame_lib.h"
+#endif
+
+namespace vimg_frames {
+namespace {
+
+// ---- the error slot: the message of this thread's last failed call ------------------------------------------------
+thread_local char g_error[256] = "";
+
+__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(g_error, sizeof g_error, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+// ---- argument checks: VIMG_OK, or VIMG_E_INVALID with the sentence set ---------------------------------------------
+// What every frame library checks first, in this order.  The frames structs open with the same eight fields
+// (VimgFilterFrames, VimgTemporalFrames: offsets 0 .. 40): one check, and one binding helper in Python, serves them all.
+template <class Frames, class Params>
+int check_head(const Frames* f, const Params* a, uint32_t max_extent) {
+  static_assert(offsetof(Frames, struct_size) == 0 && offsetof(Frames, width) == 4 && offsetof(Frames, height) == 8 &&
+                    offsetof(Frames, reserved) == 12 && offsetof(Frames, color) == 16 && offsetof(Frames, normal) == 24 &&
+                    offsetof(Frames, position) == 32 && offsetof(Frames, depth) == 40,
+                "a frame library's frames struct opens with the shared eight fields");
+  static_assert(offsetof(Params, struct_size) == 0, "a params struct opens with its struct_size");
+  if (!f) return fail(VIMG_E_INVALID, FRAME_LIB ": null frames");
+  if (!a) return fail(VIMG_E_INVALID, FRAME_LIB ": null params");
+  if (f->struct_size < sizeof(Frames))
+    return fail(VIMG_E_INVALID, FRAME_LIB ": frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(Frames));
+  if (a->struct_size < sizeof(Params))
+    return fail(VIMG_E_INVALID, FRAME_LIB ": params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(Params));
+  if (f->width == 0 || f->height == 0 || f->width > max_extent || f->height > max_extent)
+    return fail(VIMG_E_INVALID, FRAME_LIB ": width and height must be 1..%u, not %u x %u", max_extent, f->width, f->height);
+  if (!f->color || !f->normal || !f->position || !f->depth)
+    return fail(VIMG_E_INVALID, FRAME_LIB ": null %s frame", !f->color ? "color" : !f->normal ? "normal" : !f->position ? "position" : "depth");
+  return VIMG_OK;
+}
+
+// a parameter field: above `low` (`strict`) or at least `low`, never NaN, finite unless `may_be_inf`
+int check_float(const char* name, float v, float low, bool strict, bool may_be_inf) {
+  if ((strict ? v > low : v >= low) && (may_be_inf || std::isfinite(v))) return VIMG_OK;
+  return fail(VIMG_E_INVALID, FRAME_LIB ": %s must be %s %g%s, not %g", name, strict ? ">" : ">=", double(low),
+              may_be_inf ? " (it may be +inf)" : " and finite", double(v));
+}
+
+bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+// ---- the launch shape: one lane per pixel, a wave is 64 consecutive pixels of one row, the tail is a bounds test ----
+constexpr int WAVE_X = 64, ROWS = 4;    // blockDim: a wave per row segment, four rows per workgroup
+
+__device__ inline bool pixel_of(uint32_t w, uint32_t h, int& x, int& y) {
+  x = int(blockIdx.x * WAVE_X + threadIdx.x);
+  y = int(blockIdx.y * ROWS + threadIdx.y);
+  return uint32_t(x) < w && uint32_t(y) < h;
+}
+
+inline dim3 pixel_block() { return dim3(WAVE_X, ROWS); }
+inline dim3 pixel_grid(uint32_t w, uint32_t h) { return dim3((w + WAVE_X - 1) / WAVE_X, (h + ROWS - 1) / ROWS); }
+
+// ---- the launch check: a refusal is read right after the launch, so nothing is enqueued behind a stage that did not
+// start; an error left by an earlier HIP call of this thread is not this call's and is cleared before the first launch
+inline void clear_stale_error() { (void)hipGetLastError(); }
+
+inline int launched(const char* stage = nullptr) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return VIMG_OK;
+  return stage ? fail(VIMG_E_DEVICE, FRAME_LIB ": %s launch failed: %s", stage, hipGetErrorString(e))
+               : fail(VIMG_E_DEVICE, FRAME_LIB ": launch failed: %s", hipGetErrorString(e));
+}
+
+}  // namespace
+}  // namespace vimg_frames

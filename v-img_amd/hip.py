@@ -24,10 +24,16 @@ def _lib():
     return abi.hip_lib()
 
 
-def _check(rc):
-    if rc < 0:
-        raise HipError(f"[{rc}] " + _lib().vimg_hip_last_error().decode())
-    return rc
+def _checker(lib, last_error):
+    """The return-code check of the library ``lib()`` (abi.hip_lib, ...), whose message function ``last_error`` names."""
+    def check(rc):
+        if rc < 0:
+            raise HipError(f"[{rc}] " + getattr(lib(), last_error)().decode())
+        return rc
+    return check
+
+
+_check = _checker(_lib, "vimg_hip_last_error")
 
 
 _side = None
@@ -97,11 +103,13 @@ def _device_tensor(a, what, dtypes, shape, aligned=False, out=False):
     Type, dtype and a numpy array's shape are checked before anything is copied.  ``out``: a caller's output
     buffer - a tensor of exactly dtypes[0] and ``shape``, refused in one sentence."""
     import torch
-    said = str(tuple("N" if d is None else d for d in shape)).replace("'", "")
+
+    def said():      # (only a refusal spells the shape out)
+        return str(tuple("N" if d is None else d for d in shape)).replace("'", "")
 
     def bad(why):
         if out:
-            why = f"out must be a contiguous torch.{dtypes[0]} CUDA tensor of shape {said} on the current device"
+            why = f"out must be a contiguous torch.{dtypes[0]} CUDA tensor of shape {said()} on the current device"
         return ValueError(f"{what}: {why}")
 
     def fits(got):
@@ -111,7 +119,7 @@ def _device_tensor(a, what, dtypes, shape, aligned=False, out=False):
         if a.dtype.name not in dtypes:
             raise bad(f"dtype must be {' or '.join(dtypes)}, not {a.dtype}")
         if not fits(a.shape):
-            raise bad(f"shape must be {said}, not {tuple(a.shape)}")
+            raise bad(f"shape must be {said()}, not {tuple(a.shape)}")
         a = np.ascontiguousarray(a)
         t, host = _upload(a.view(np.uint8) if a.dtype == np.bool_ else a), True
     elif isinstance(a, torch.Tensor):
@@ -122,7 +130,7 @@ def _device_tensor(a, what, dtypes, shape, aligned=False, out=False):
         if not a.is_contiguous():
             raise bad("the tensor must be contiguous")
         if not fits(a.shape):
-            raise bad(f"shape must be {said}, not {tuple(a.shape)}")
+            raise bad(f"shape must be {said()}, not {tuple(a.shape)}")
         t, host = a, False
     else:
         raise bad(f"expected a torch CUDA tensor or a numpy array, not {type(a).__name__}")
@@ -131,9 +139,59 @@ def _device_tensor(a, what, dtypes, shape, aligned=False, out=False):
     return t, host
 
 
-def _owned(out, fresh, *used):
-    """made / used of the _Launch of a call that allocated its output `out` itself (`fresh`) or was given it."""
-    return dict(made=[out], used=used) if fresh else dict(made=(), used=(out, *used))
+class _Tensors:
+    """The tensors of one call, collected as they are taken and sorted into the ``made`` / ``used`` of its _Launch:
+    ``made`` is what the call copied up from numpy or allocated, ``used`` what the caller handed in.  ``to_host``:
+    numpy in, numpy out - the call's input came from numpy, so ``result`` takes its output back there."""
+
+    def __init__(self, to_host=False):
+        self.made, self.used, self.to_host = [], [], to_host
+
+    def take(self, a, what, dtypes, shape, aligned=False):
+        """An input, through _device_tensor: a numpy array's device copy is made, a CUDA tensor is used."""
+        t, host = _device_tensor(a, what, dtypes, shape, aligned)
+        (self.made if host else self.used).append(t)
+        return t
+
+    def own(self, t):          # a tensor this call allocated
+        self.made.append(t)
+        return t
+
+    def use(self, t):          # a caller's tensor, as it is
+        self.used.append(t)
+        return t
+
+    def output(self, out, what, dtype, shape, aligned=False):
+        """The output of the call: allocated when ``out`` is None, else the caller's buffer, which must be exactly a
+        torch.``dtype`` CUDA tensor of ``shape`` (_device_tensor's out=True)."""
+        if out is None:
+            import torch
+            return self.own(torch.empty(shape, dtype=getattr(torch, dtype), device="cuda"))
+        return self.use(_device_tensor(out, what, (dtype,), shape, aligned, out=True)[0])
+
+    def launch(self, stream):
+        return _Launch(stream, self.made, self.used, to_host=self.to_host)
+
+    def result(self, t):
+        return t.cpu().numpy() if self.to_host else t
+
+
+class FrameCall(_Tensors):
+    """The tensors of one call of the frame library ``what`` ("atrous", "temporal") on frames of ``color``'s shape."""
+
+    def __init__(self, what, color):
+        import torch
+        super().__init__(to_host=not isinstance(color, torch.Tensor))
+        shape = getattr(color, "shape", None)
+        if shape is None or len(shape) != 3 or shape[2] != 3:
+            raise ValueError(f"{what} color: shape must be (H, W, 3), not {None if shape is None else tuple(shape)}")
+        self.what, self.h, self.w = what, int(shape[0]), int(shape[1])
+
+    def frames(self, names, arrays, optional=()):
+        """name -> device tensor of the [H, W, 3] float32 frames; a None one out of ``optional`` is left out."""
+        shape = (self.h, self.w, 3)
+        return {name: self.take(a, f"{self.what} {name}", ("float32",), shape)
+                for name, a in zip(names, arrays) if not (a is None and name in optional)}
 
 
 def _ptr(t):
@@ -191,11 +249,10 @@ class DeviceScene:
 
         tile_world == 1: returns [H, W, 3] in the reference layout (row 0 = top).
         tile_world  > 1: returns the shard's compact [shard_pixels, 3] buffer."""
-        fresh = out is None
-        if fresh:
-            out = self._new_output(params)
+        c = _Tensors()
+        out = c.own(self._new_output(params)) if out is None else c.use(out)
         st = abi.RenderStats()
-        with _Launch(stream, **_owned(out, fresh)) as sp:
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_render(self._h, C.byref(params), C.c_void_p(out.data_ptr()), sp,
                                              C.byref(st) if stats else None))
         return (out, st) if stats else out
@@ -313,12 +370,10 @@ class DeviceScene:
         CDFs) are rebuilt on the GPU.  Positions (as for update_geometry) may ride in the same call.  Afterwards the
         scene is the upload of the host scene edited the same way; progressive accumulators must be reset."""
         upd = abi.GeometryUpdate()
-        made, used, keep = [], [], []     # device copies of numpy tables, the caller's tensors, the ctypes tables
+        c, keep = _Tensors(), []     # the device tables (copies of numpy ones, the caller's tensors), the ctypes tables
 
         def table(a, rows, cols, what):
-            t, host = _device_tensor(a, what, ("float32",), (rows, cols))
-            (made if host else used).append(t)
-            return _ptr(t)
+            return _ptr(c.take(a, what, ("float32",), (rows, cols)))
 
         for name, a, rows, cols in (("vertices", vertices, self.num_vertices, 3), ("normals", normals, self.num_vertices, 3),
                                     ("spheres", spheres, self.num_spheres, 4)):
@@ -326,7 +381,7 @@ class DeviceScene:
                 setattr(upd, name, table(a, rows, cols, name))
         self._fill_material_update(upd, table, keep, materials, textures, lights, background, images)
         self.generation += 1
-        with _Launch(stream, made, used) as sp:     # (blocking: the tables stay alive until it returns)
+        with c.launch(stream) as sp:     # (blocking: the tables stay alive until it returns)
             _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
 
     def update_from(self, host_scene, stream=None):
@@ -370,20 +425,11 @@ class DeviceScene:
 
     # ---- ray queries (vimg_hip_trace_rays, _occluded, _camera_rays) ----------------------------------
     @staticmethod
-    def _query_io(a, cols, what):
-        """The [N, cols] float32 input of a query, 16-byte aligned: (tensor, N, came from numpy, made, used) - the
-        last two are the lists of the call's _Launch, which _query_output adds the outputs to."""
-        t, host = _device_tensor(a, what, ("float32",), (None, cols), aligned=True)
-        return (t, t.shape[0], host) + (([t], []) if host else ([], [t]))
-
-    @staticmethod
-    def _query_output(out, shape, dtype, what, made, used):
-        import torch
-        if out is None:
-            made.append(torch.empty(shape, dtype=getattr(torch, dtype), device="cuda"))
-            return made[-1]
-        used.append(_device_tensor(out, what, (dtype,), shape, aligned=len(shape) > 1, out=True)[0])
-        return out
+    def _query(a, cols, what):
+        """(the call's _Tensors, the [N, cols] float32 input of a query, 16-byte aligned, N)."""
+        c = _Tensors(to_host=isinstance(a, np.ndarray))
+        t = c.take(a, what, ("float32",), (None, cols), aligned=True)
+        return c, t, t.shape[0]
 
     def trace_rays(self, rays, info=False, out=None, stream=None):
         """Closest hits of ``rays`` ([N, 8] float32 laid out as VimgRay: org xyz, t_min, dir xyz, t_max) against the
@@ -392,35 +438,34 @@ class DeviceScene:
         uv [N, 2], mat [N] int32.  A CUDA tensor is used as it is and the results are views of device buffers,
         ordered on ``stream`` (torch's current one by default); a numpy array is copied up and numpy arrays come
         back.  ``out``: the [N, 4] float32 hit buffer, or (hits, [N, 12] info buffer) with ``info``."""
-        r, n, host, made, used = self._query_io(rays, 8, "rays")
+        c, r, n = self._query(rays, 8, "rays")
         hits_out, info_out = (out if info and out is not None else (out, None))
-        hits = self._query_output(hits_out, (n, 4), "float32", "trace_rays", made, used)
-        rec = self._query_output(info_out, (n, 12), "float32", "trace_rays info", made, used) if info else None
-        with _Launch(stream, made, used, to_host=host) as sp:
+        hits = c.output(hits_out, "trace_rays", "float32", (n, 4), aligned=True)
+        rec = c.output(info_out, "trace_rays info", "float32", (n, 12), aligned=True) if info else None
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_trace_rays(self._h, _ptr(r), n, _ptr(hits), _ptr(rec), sp))
-        return RayHits.of(hits, rec, host)
+        return RayHits.of(hits, rec, c.to_host)
 
     def occluded(self, rays, out=None, stream=None):
         """The render's shadow test on ``rays`` ([N, 8] float32, VimgRay; vimg_hip_occluded): bool [N], True when
         anything lies in [t_min, t_max].  CUDA tensor in, CUDA tensor out (a view of ``out``, [N] uint8, when
         given); numpy in, numpy out."""
         import torch
-        r, n, host, made, used = self._query_io(rays, 8, "rays")
-        flags = self._query_output(out, (n,), "uint8", "occluded", made, used)
-        with _Launch(stream, made, used, to_host=host) as sp:
+        c, r, n = self._query(rays, 8, "rays")
+        flags = c.output(out, "occluded", "uint8", (n,))
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_occluded(self._h, _ptr(r), n, _ptr(flags), sp))
-        res = flags.view(torch.bool)
-        return res.cpu().numpy() if host else res
+        return c.result(flags.view(torch.bool))
 
     def camera_rays(self, samples, out=None, stream=None):
         """The camera's rays (vimg_hip_camera_rays) for ``samples`` [N, 4] float32 {x, y, lens_u, lens_v} (pixel
         coordinates, lens samples): [N, 8] float32 VimgRay records with t_min 1e-4 and t_max +inf - the input of
         trace_rays for picking.  CUDA tensor in, CUDA tensor out; numpy in, numpy out."""
-        smp, n, host, made, used = self._query_io(samples, 4, "samples")
-        rays = self._query_output(out, (n, 8), "float32", "camera_rays", made, used)
-        with _Launch(stream, made, used, to_host=host) as sp:
+        c, smp, n = self._query(samples, 4, "samples")
+        rays = c.output(out, "camera_rays", "float32", (n, 8), aligned=True)
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_camera_rays(self._h, _ptr(smp), n, _ptr(rays), sp))
-        return rays.cpu().numpy() if host else rays
+        return c.result(rays)
 
     def progressive(self, params):
         """An accumulator for this frame (or shard) rendered a few samples at a time (vimg_hip_progressive_*):
@@ -451,10 +496,9 @@ class DeviceScene:
     def render_heatmap(self, params, factor=-1.0, out=None, stream=None):
         """BVH traversal-cost picture (reference heatmap_img) into a torch CUDA tensor [H, W, 3]
         (or the compact shard slab when params.tile_world > 1)."""
-        fresh = out is None
-        if fresh:
-            out = self._new_output(params, zero_slab=False)
-        with _Launch(stream, **_owned(out, fresh)) as sp:
+        c = _Tensors()
+        out = c.own(self._new_output(params, zero_slab=False)) if out is None else c.use(out)
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_render_heatmap(self._h, C.byref(params), factor,
                                                      C.c_void_p(out.data_ptr()), sp))
         return out
@@ -468,10 +512,10 @@ class DeviceScene:
     def assemble_shards(self, gathered, world, shard_stride_pixels, out=None, stream=None):
         import torch
         w, h = self.resolution
-        fresh = out is None
-        if fresh:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
-        with _Launch(stream, **_owned(out, fresh, gathered)) as sp:
+        c = _Tensors()
+        out = c.own(torch.empty((h, w, 3), dtype=torch.float32, device="cuda")) if out is None else c.use(out)
+        c.use(gathered)
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_assemble_shards(self._h, world, shard_stride_pixels,
                                                       C.c_void_p(gathered.data_ptr()),
                                                       C.c_void_p(out.data_ptr()), sp))
@@ -502,6 +546,23 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+
+class GuideCache:
+    """Feature frames of a resident scene, rendered once and kept until the scene is edited: ``get`` renders the frames
+    ``names`` of ``params`` at ``samples`` samples (render_features' dict) when (DeviceScene.generation, samples, names)
+    is not what ``held`` - (key, frames), or None: nothing, set it to drop them - was rendered from.  One per owner."""
+
+    def __init__(self, dev):
+        self._dev, self.held = dev, None
+
+    def get(self, params, samples, names, stream=None):
+        key = (self._dev.generation, int(samples), tuple(names))
+        if self.held is None or self.held[0] != key:
+            p = abi.RenderParams.from_buffer_copy(params)
+            p.samples = int(samples)
+            self.held = (key, self._dev.render_features(p, names, stream=stream))
+        return self.held[1]
 
 
 class RayHits:
@@ -542,7 +603,11 @@ class Progressive:
         h = C.c_void_p()
         _check(self._lib.vimg_hip_progressive_create(dev._h, C.byref(self.params), C.byref(h)))
         self._h = h
-        self._guides = None          # ((scene generation, feature samples), the four feature frames) of the last preview
+        self._guide_cache = GuideCache(dev)
+
+    @property
+    def _guides(self):           # (key, the four feature frames) of the last preview, or None
+        return self._guide_cache.held
 
     def _handle(self):
         if not self._h:
@@ -573,15 +638,15 @@ class Progressive:
         non-zero get the samples (vimg_hip_progressive_render_masked); every pixel's mean is returned, each
         bit for bit ``DeviceScene.render`` at that pixel's own count."""
         h = self._handle()
-        fresh = out is None
-        if fresh:
-            out = self._dev._new_output(self.params)
-        made, used = ([out], []) if fresh else ([], [] if out is False else [out])
+        c = _Tensors()
+        if out is None:
+            out = c.own(self._dev._new_output(self.params))
+        elif out is not False:
+            c.use(out)
         if mask is not None:
-            m, host = _device_tensor(mask, "mask", ("uint8", "bool"), self.pixel_shape)
-            (made if host else used).append(m)
+            m = c.take(mask, "mask", ("uint8", "bool"), self.pixel_shape)
         st = abi.RenderStats()
-        with _Launch(stream, made, used) as sp:
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_progressive_render_masked(self._dev._h, h, int(samples),
                                                                 None if mask is None else C.c_void_p(m.data_ptr()),
                                                                 None if out is False else C.c_void_p(out.data_ptr()), sp,
@@ -600,12 +665,7 @@ class Progressive:
         if self.params.tile_world != 1:
             raise ValueError("preview: the filter reads whole frames, not shards (tile_world must be 1)")
         noisy = self.render(samples, stream=stream)
-        key = (self._dev.generation, int(feature_samples))
-        if self._guides is None or self._guides[0] != key:
-            p = abi.RenderParams.from_buffer_copy(self.params)
-            p.samples = int(feature_samples)
-            self._guides = (key, self._dev.render_features(p, flt.GUIDES, stream=stream))
-        g = self._guides[1]
+        g = self._guide_cache.get(self.params, feature_samples, flt.GUIDES, stream=stream)
         return flt.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=out, stream=stream, **filter_kw)
 
     def state(self, stream=None):
@@ -650,13 +710,13 @@ class Progressive:
         (vimg_hip_progressive_select)."""
         import torch
         h = self._handle()
-        fresh = out is None
-        if fresh:
-            out = torch.zeros(self.pixel_shape, dtype=torch.uint8, device="cuda")
+        c = _Tensors()
+        if out is None:
+            out = c.own(torch.zeros(self.pixel_shape, dtype=torch.uint8, device="cuda"))
         else:
-            out, fresh = _device_tensor(out, "mask", ("uint8", "bool"), self.pixel_shape)
+            out = c.take(out, "mask", ("uint8", "bool"), self.pixel_shape)
         n = abi.u32(0)
-        with _Launch(stream, **_owned(out, fresh)) as sp:
+        with c.launch(stream) as sp:
             _check(self._lib.vimg_hip_progressive_select(h, float(target), int(max_samples), C.c_void_p(out.data_ptr()), sp,
                                                          C.byref(n)))
         return out, int(n.value)

@@ -3,7 +3,8 @@
 
 The third scene-free library: the last preview is reprojected into a moved camera by the `position`
 frame and blended with the current frame where normal and position say it is the same surface.  The binding shares the
-render binding's tensor check and stream rule (hip._device_tensor, hip._Launch).  There is no CPU fallback.
+render binding's tensor check and stream rule (hip.FrameCall: hip._device_tensor, hip._Launch).  There is no CPU
+fallback.
 """
 import ctypes as C
 import math
@@ -11,20 +12,14 @@ import math
 import numpy as np
 
 from . import _abi as abi
-from .hip import HipError, _Launch, _device_tensor
+from .hip import FrameCall, GuideCache, _checker
 
 FRAMES = ("color", "normal", "position", "depth")
 PARAMS = ("max_history", "current_weight", "sigma_normal", "sigma_plane")
 
 
-def _lib():
-    return abi.temporal_lib()
-
-
-def _check(rc):
-    if rc < 0:
-        raise HipError(f"[{rc}] " + _lib().vimg_temporal_last_error().decode())
-    return rc
+_lib = abi.temporal_lib
+_check = _checker(_lib, "vimg_temporal_last_error")
 
 
 def temporal_params(max_history=None, current_weight=None, sigma_normal=None, sigma_plane=None):
@@ -94,42 +89,30 @@ def accumulate(color, normal, position, depth, history=None, world_to_pixel=None
     may be ``color`` itself; ``next_history``: the [3, H, W, 4] float32 CUDA tensor to write (not the one ``history``
     holds), allocated when None.  ``params``: max_history, current_weight, sigma_normal, sigma_plane, default the
     library's (include/vimg_temporal.h).  The call only enqueues, on ``stream`` or torch's current stream."""
-    import torch
-    shape = getattr(color, "shape", None)
-    if shape is None or len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"temporal color: shape must be (H, W, 3), not {None if shape is None else tuple(shape)}")
+    c = FrameCall("temporal", color)
     unknown = sorted(set(params) - set(PARAMS))
     if unknown:
         raise TypeError(f"temporal: unknown parameters {unknown}; expected some of {PARAMS}")
-    h, w = int(shape[0]), int(shape[1])
+    h, w = c.h, c.w
     p = temporal_params(**params)
-    made, used, t = [], [], {}
-    for name, a in zip(FRAMES, (color, normal, position, depth)):
-        t[name], host = _device_tensor(a, f"temporal {name}", ("float32",), (h, w, 3))
-        (made if host else used).append(t[name])
-    to_host = not isinstance(color, torch.Tensor)
+    t = c.frames(FRAMES, (color, normal, position, depth))
     prev = matrix = None
     if history is not None:
         if not isinstance(history, History):
             raise ValueError("temporal: history must be a temporal.History")
         if history.world_to_pixel is None:
             raise ValueError("temporal: the history does not know its world_to_pixel matrix")
-        prev, host = _device_tensor(history.tensor, "temporal history", ("float32",), (3, h, w, 4), aligned=True)
-        (made if host else used).append(prev)
+        prev = c.take(history.tensor, "temporal history", ("float32",), (3, h, w, 4), aligned=True)
         matrix = (abi.f32 * 12)(*history.world_to_pixel.tolist())
-    if next_history is None:
-        next_history = torch.empty((3, h, w, 4), dtype=torch.float32, device="cuda")
-        made.append(next_history)
-    else:
-        used.append(_device_tensor(next_history, "temporal next_history", ("float32",), (3, h, w, 4), aligned=True, out=True)[0])
+    next_history = c.output(next_history, "temporal next_history", "float32", (3, h, w, 4), aligned=True)
     if out is not None:
-        used.append(_device_tensor(out, "temporal", ("float32",), (h, w, 3), out=True)[0])
+        c.output(out, "temporal", "float32", (h, w, 3))
     frames = abi.TemporalFrames(width=w, height=h, **{k: v.data_ptr() for k, v in t.items()})
-    with _Launch(stream, made, used, to_host=to_host) as sp:
+    with c.launch(stream) as sp:
         _check(_lib().vimg_temporal_accumulate(C.byref(frames), None if prev is None else C.c_void_p(prev.data_ptr()), matrix,
                                                C.byref(p), C.c_void_p(next_history.data_ptr()),
                                                None if out is None else C.c_void_p(out.data_ptr()), sp))
-    return History(next_history.cpu().numpy() if to_host else next_history, world_to_pixel)
+    return History(c.result(next_history), world_to_pixel)
 
 
 class TemporalPreview:
@@ -172,6 +155,7 @@ class TemporalPreview:
         self._features = flt.GUIDES if denoise else ("normal", "position", "depth")
         self._sigma_color = float(self.filter_kw.pop("sigma_color", None) or flt.atrous_params().sigma_color) if denoise else None
         self._max_history = float(temporal_params(max_history=temporal_kw.get("max_history")).max_history)
+        self._guides = GuideCache(dev)
         self.reset()
 
     def reset(self):
@@ -180,7 +164,7 @@ class TemporalPreview:
         self.history = None        # the History of the last frame(): unfiltered radiance, lengths, guides
         self._write = 0            # which buffer the frames since the last change write
         self._generation = None
-        self._guides = None
+        self._guides.held = None
         self._k = 0
         self._frames = 0           # frames accumulated since the reset: the nominal history length of the next output
 
@@ -191,15 +175,12 @@ class TemporalPreview:
         dev, acc = self._dev, self.acc
         if self._generation != dev.generation:
             acc.reset(stream=stream)
-            p = abi.RenderParams.from_buffer_copy(acc.params)
-            p.samples = self.feature_samples
-            self._guides = dev.render_features(p, self._features, stream=stream)
             if self.history is not None:           # the last frame's history freezes; the other buffer is written from now on
                 self._frozen, self._write = self.history, 1 - self._write
             self._generation, self._k = dev.generation, 0
+        g = self._guides.get(acc.params, self.feature_samples, self._features, stream=stream)
         mean = acc.render(self.samples, stream=stream)
         self._k += 1
-        g = self._guides
         target = mean if out is None else out
         self.history = accumulate(mean, g["normal"], g["position"], g["depth"], history=self._frozen,
                                   world_to_pixel=world_to_pixel(dev.camera), out=target, next_history=self._buffers[self._write],

@@ -4,7 +4,7 @@
 //   A    {r, g, b, L}         accumulated radiance, history length (0: no surface)
 //   G0   {n.x, n.y, n.z, z}
 //   G1   {P.x, P.y, P.z, 0}
-// Launch shape as in the filter library: one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of
+// Launch shape of frames/frame_lib.h: one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of
 // one row.  The current frame's reads (packed triples) and all writes are contiguous per wave; the up to four history
 // taps are gathers wherever the old camera saw the pixel's surface point, a whole float4 of plane A and xyz of the guide planes.  The tail is a
 // bounds test.  The matrix and the parameters travel as kernel arguments.
@@ -12,17 +12,14 @@
 // The arithmetic is the header's contract, operation for operation: built with -ffp-contract=off and without
 // fast-math, so + - * / round once each, and the select forms below are the contract's comparisons (a NaN compares
 // false), never fmaxf / fminf.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-
 #include "vimg_temporal.h"
+
+#define FRAME_LIB "temporal"
+#include "../frames/frame_lib.h"
 
 namespace vimg_temporal {
 
-constexpr int WAVE_X = 64, ROWS = 4;    // blockDim: a wave per row segment, four rows per workgroup
+using namespace vimg_frames;
 
 struct Constants {
   float m[12];     // prev_world_to_pixel, row-major 3 x 4
@@ -102,21 +99,6 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void temporal_accumulate_kernel(
   }
 }
 
-thread_local char g_error[256] = "";
-
-static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-static bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 }  // namespace vimg_temporal
 
 using namespace vimg_temporal;
@@ -139,25 +121,12 @@ uint64_t vimg_temporal_history_bytes(uint32_t width, uint32_t height) {
 
 int vimg_temporal_accumulate(const VimgTemporalFrames* f, const void* d_prev_history, const float prev_world_to_pixel[12],
                              const VimgTemporalParams* a, void* d_next_history, void* d_out_rgb, void* stream) {
-  if (!f) return fail(VIMG_E_INVALID, "temporal: null frames");
-  if (!a) return fail(VIMG_E_INVALID, "temporal: null params");
-  if (f->struct_size < sizeof(VimgTemporalFrames))
-    return fail(VIMG_E_INVALID, "temporal: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgTemporalFrames));
-  if (a->struct_size < sizeof(VimgTemporalParams))
-    return fail(VIMG_E_INVALID, "temporal: params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(VimgTemporalParams));
-  if (f->width == 0 || f->height == 0 || f->width > VIMG_TEMPORAL_MAX_EXTENT || f->height > VIMG_TEMPORAL_MAX_EXTENT)
-    return fail(VIMG_E_INVALID, "temporal: width and height must be 1..%u, not %u x %u", VIMG_TEMPORAL_MAX_EXTENT, f->width, f->height);
-  if (!f->color || !f->normal || !f->position || !f->depth)
-    return fail(VIMG_E_INVALID, "temporal: null %s frame", !f->color ? "color" : !f->normal ? "normal" : !f->position ? "position" : "depth");
+  if (const int rc = check_head(f, a, VIMG_TEMPORAL_MAX_EXTENT)) return rc;
   if (!d_next_history) return fail(VIMG_E_INVALID, "temporal: null next history");
-  if (!(a->max_history >= 1.f) || !std::isfinite(a->max_history))
-    return fail(VIMG_E_INVALID, "temporal: max_history must be >= 1 and finite, not %g", double(a->max_history));
-  if (!(a->current_weight >= 1.f) || !std::isfinite(a->current_weight))
-    return fail(VIMG_E_INVALID, "temporal: current_weight must be >= 1 and finite, not %g", double(a->current_weight));
-  if (!(a->sigma_normal > 0.f) || !std::isfinite(a->sigma_normal))
-    return fail(VIMG_E_INVALID, "temporal: sigma_normal must be > 0 and finite, not %g", double(a->sigma_normal));
-  if (!(a->sigma_plane > 0.f) || !std::isfinite(a->sigma_plane))
-    return fail(VIMG_E_INVALID, "temporal: sigma_plane must be > 0 and finite, not %g", double(a->sigma_plane));
+  if (const int rc = check_float("max_history", a->max_history, 1.f, false, false)) return rc;
+  if (const int rc = check_float("current_weight", a->current_weight, 1.f, false, false)) return rc;
+  if (const int rc = check_float("sigma_normal", a->sigma_normal, 0.f, true, false)) return rc;
+  if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
   if (reinterpret_cast<uintptr_t>(d_next_history) % 16)
     return fail(VIMG_E_INVALID, "temporal: the next history must be 16-byte aligned");
   Constants k{};
@@ -197,15 +166,12 @@ int vimg_temporal_accumulate(const VimgTemporalFrames* f, const void* d_prev_his
   k.sigma_normal = a->sigma_normal;
   k.sigma_plane = a->sigma_plane;
 
-  const dim3 block(WAVE_X, ROWS), grid((w + WAVE_X - 1) / WAVE_X, (h + ROWS - 1) / ROWS);
-  // an error left by an earlier HIP call of this thread is not this call's and is cleared first
-  (void)hipGetLastError();
-  temporal_accumulate_kernel<<<grid, block, 0, static_cast<hipStream_t>(stream)>>>(
+  clear_stale_error();
+  temporal_accumulate_kernel<<<pixel_grid(w, h), pixel_block(), 0, static_cast<hipStream_t>(stream)>>>(
       w, h, static_cast<const float*>(f->color), static_cast<const float*>(f->normal), static_cast<const float*>(f->position),
       static_cast<const float*>(f->depth), static_cast<const float4*>(d_prev_history), k, static_cast<float4*>(d_next_history),
       static_cast<float*>(d_out_rgb));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? int(VIMG_OK) : fail(VIMG_E_DEVICE, "temporal: launch failed: %s", hipGetErrorString(e));
+  return launched();
 }
 
 const char* vimg_temporal_last_error(void) { return g_error; }
