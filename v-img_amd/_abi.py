@@ -362,6 +362,30 @@ TEMPORAL_SYMBOLS = {
 }
 
 
+class VarFilterFrames(_Sized, C.Structure):
+    """VimgVarFilterFrames (include/vimg_varfilter.h): VimgFilterFrames and the per-pixel variance frame (float32)."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("color", C.c_void_p),
+                ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p),
+                ("variance", C.c_void_p)]
+
+
+class VarFilterParams(_Sized, C.Structure):
+    """VimgVarFilterParams (include/vimg_varfilter.h); vimg_varfilter_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("iterations", u32), ("sigma_luminance", f32), ("sigma_normal", f32),
+                ("sigma_plane", f32), ("albedo_floor", f32), ("variance_floor", f32)]
+
+
+# the list of symbols include/vimg_varfilter.h declares: libvimg_varfilter.so, the variance-guided a-trous filter
+VARFILTER_SYMBOLS = {
+    "vimg_varfilter_defaults": (None, [C.POINTER(VarFilterParams)]),
+    "vimg_varfilter_workspace": (C.c_uint64, [u32, u32]),
+    "vimg_varfilter_atrous": (C.c_int, [C.POINTER(VarFilterFrames), C.POINTER(VarFilterParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_uint64, C.c_void_p]),
+    "vimg_varfilter_variance": (C.c_int, [u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_varfilter_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -378,6 +402,7 @@ _LIBRARIES = {
     "hip": ("libvimg_hip.so", (HIP_SYMBOLS, HIP_TEST_SYMBOLS), "hip", "; there is no CPU fallback for the render path", True),
     "filter": ("libvimg_filter.so", (FILTER_SYMBOLS,), "filter", "; there is no CPU fallback for the filter", True),
     "temporal": ("libvimg_temporal.so", (TEMPORAL_SYMBOLS,), "temporal", "; there is no CPU fallback for temporal accumulation", True),
+    "varfilter": ("libvimg_varfilter.so", (VARFILTER_SYMBOLS,), "varfilter", "; there is no CPU fallback for the filter", True),
 }
 _loaded = {}
 
@@ -419,3 +444,8 @@ def filter_lib():
 def temporal_lib():
     """The temporal accumulation library (include/vimg_temporal.h)."""
     return _load("temporal")
+
+
+def varfilter_lib():
+    """The variance-guided filter library (include/vimg_varfilter.h)."""
+    return _load("varfilter")

@@ -279,16 +279,22 @@ class DeviceScene:
             res[name] = self.render(p, out=given, stats=False, stream=stream)
         return res
 
-    def render_denoised(self, params, out=None, stream=None, **filter_kw):
+    def render_denoised(self, params, out=None, stream=None, variance_guided=False, **filter_kw):
         """``render`` followed by the a-trous filter (vimg_amd.filter.atrous, include/vimg_filter.h) guided by the
         frame's own feature frames: exactly render(params) + render_features(params, ("albedo", "normal",
-        "position", "depth")) + filter.atrous(..., **filter_kw).  Returns the filtered [H, W, 3] image (``out`` when
-        given); whole frames only."""
+        "position", "depth")) + filter.atrous(..., **filter_kw).  ``variance_guided``: the variance-guided filter
+        (vimg_amd.varfilter.atrous, include/vimg_varfilter.h) instead, with ``filter_kw`` its parameters; a one-shot
+        render has no variance, so every pixel's is estimated from its surroundings.  Returns the filtered [H, W, 3]
+        image (``out`` when given); whole frames only."""
         from . import filter as flt
         if params.tile_world != 1:
             raise ValueError("render_denoised: the filter reads whole frames, not shards (tile_world must be 1)")
         noisy = self.render(params, stats=False, stream=stream)
         guides = self.render_features(params, flt.GUIDES, stream=stream)
+        if variance_guided:
+            from . import varfilter
+            return varfilter.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
+                                    stream=stream, **filter_kw)[0]
         return flt.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
                           stream=stream, **filter_kw)
 
@@ -654,18 +660,24 @@ class Progressive:
         img = None if out is False else out
         return (img, st) if stats else img
 
-    def preview(self, samples, out=None, stream=None, feature_samples=4, **filter_kw):
+    def preview(self, samples, out=None, stream=None, feature_samples=4, variance_guided=False, **filter_kw):
         """``render(samples)`` followed by the a-trous filter (vimg_amd.filter.atrous) on the running mean: the
         denoised picture of the frame so far.  The accumulator is advanced exactly as by ``render`` and keeps the
         unfiltered sums, so later increments and renders give the bits they would have given.  The guides -
         render_features(("albedo", "normal", "position", "depth")) at ``feature_samples`` samples - do not depend on
         the increments: they are rendered once and kept until the scene is edited (DeviceScene.generation).
-        Whole frames only.  ``filter_kw``: the parameters of filter.atrous."""
+        Whole frames only.  ``filter_kw``: the parameters of filter.atrous.  ``variance_guided``: render(samples) +
+        ``variance()`` + the variance-guided filter (vimg_amd.varfilter.atrous, ``filter_kw`` its parameters) on the
+        same guides - each pixel is filtered by its own noise, whatever its count."""
         from . import filter as flt
         if self.params.tile_world != 1:
             raise ValueError("preview: the filter reads whole frames, not shards (tile_world must be 1)")
         noisy = self.render(samples, stream=stream)
         g = self._guide_cache.get(self.params, feature_samples, flt.GUIDES, stream=stream)
+        if variance_guided:
+            from . import varfilter
+            return varfilter.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], variance=self.variance(stream),
+                                    out=out, stream=stream, **filter_kw)[0]
         return flt.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=out, stream=stream, **filter_kw)
 
     def state(self, stream=None):
@@ -703,6 +715,22 @@ class Progressive:
         with _Launch(stream, made=[e]) as sp:
             _check(self._lib.vimg_hip_progressive_error(h, C.c_void_p(e.data_ptr()), sp))
         return e
+
+    def variance(self, stream=None):
+        """Estimated variance of each pixel's mean luminance (vimg_varfilter_variance of the records): [H, W] float32
+        CUDA tensor, NaN for pixels that took part in fewer than two increments - the quantity under the square root
+        of ``error()``, and what vimg_amd.varfilter.atrous takes as ``variance``.  Whole frames only."""
+        import torch
+        from . import varfilter
+        h = self._handle()
+        if self.params.tile_world != 1:
+            raise ValueError("variance: the variance frame is a whole frame's, not a shard's (tile_world must be 1)")
+        # the library's own uint32 buffers (as int32: the same bits), not _read_state's widened ones
+        n, k = (torch.zeros(self.pixel_shape, dtype=torch.int32, device="cuda") for _ in range(2))
+        m2 = torch.zeros(self.pixel_shape, dtype=torch.float32, device="cuda")
+        with _Launch(stream, made=[n, k, m2]) as sp:
+            _check(self._lib.vimg_hip_progressive_state(h, None, _ptr(n), _ptr(k), _ptr(m2), sp))
+        return varfilter.variance(n, k, m2, out=m2, stream=stream)
 
     def select(self, target, max_samples, out=None, stream=None):
         """(mask, active): the uint8 mask of the pixels that still need samples - error above ``target`` and count
