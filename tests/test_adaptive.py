@@ -12,7 +12,7 @@ import pytest
 
 import oracle_lib as O
 import scenes
-from test_adaptive_abi import same_floats, stat_error, stat_update
+from test_adaptive_abi import SEQUENCES, check_against_model, restatement_over, same_floats, stat_error, stat_update
 from test_gpu_parity import SCHEDULES
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +21,11 @@ STATS_FIELDS = ("paths", "closest_rays", "shadow_rays", "internal_visits", "leaf
                 "sphere_tests", "nan_samples")
 INTEGRATORS = ("s_normal", "g_normal", "material", "mis")
 RES = (70, 44)          # ragged in both directions: tiles with slots off the image
+# Above 2^20 items the list builder's scan (adapt_scan_kernel, 1024 workgroups of 1024 items per pass) takes a second
+# pass and carries a total into it.  BIG: ragged in both directions, 138 x 128 tiles, 1 130 496 items, 1104 list
+# workgroups; with 128 tile rows the items from 2^20 on are exactly the pixels with x >= 1024.  BIG_SHARD: every
+# second tile of 225 x 150, 1 080 000 items, 1055 list workgroups.
+BIG, BIG_SHARD = (1099, 1021), (1800, 1200)
 
 
 def _dev(s, **opts):
@@ -91,11 +96,14 @@ def _masks(shape, seed):
     return [(a, 2), (np.zeros(shape, np.uint8), 3), (b, 1), (np.ones(shape, np.uint8), 2), (c, 1)]
 
 
-def _run_sequence(d, s, integrator, world, rank, stats, refs, what, oracle_pixels=0):
+def _run_sequence(d, s, integrator, world, rank, stats, refs, what, oracle_pixels=0, res=RES, calls=None,
+                  check_after=(2, 4), then=None):
     """One sequence of masked calls on a fresh accumulator, every pixel checked against the library's own one-shot
     render at its count.  The oracle's trace_pixel is asked for a handful of pixels of whole frames only (shards,
     and the schedules other than lane and cu, are held to that one-shot render, which tests/test_gpu_parity.py
-    holds to the oracle)."""
+    holds to the oracle).  `calls(shape, valid)` gives another sequence of (mask or None, n) than _masks', checked
+    against the one-shot renders after the calls of `check_after`; `then(acc, valid)` runs on the accumulator the
+    sequence leaves."""
     import torch
     p = _params(s, integrator, tile_world=world, tile_rank=rank)
     acc = d.progressive(p)
@@ -103,18 +111,18 @@ def _run_sequence(d, s, integrator, world, rank, stats, refs, what, oracle_pixel
     if world == 1:
         valid = np.ones(shape, dtype=bool)
     else:
-        valid = _shard_valid(RES, world, rank)[0]
+        valid = _shard_valid(res, world, rank)[0]
     expect = np.zeros(shape, dtype=np.int64)
     n_old, k_old, m2_old = np.zeros(shape, np.uint32), np.zeros(shape, np.uint32), np.zeros(shape, np.float32)
     s_old = np.zeros(shape + (3,), np.float32)
     paths = 0
-    for i, (mask, n) in enumerate(_masks(shape, 1234 + world)):
+    for i, (mask, n) in enumerate(_masks(shape, 1234 + world) if calls is None else calls(shape, valid)):
         # numpy masks are copied up, CUDA tensors are used where they are
-        m = mask if i % 2 == 0 else torch.from_numpy(mask).cuda()
+        m = mask if i % 2 == 0 or mask is None else torch.from_numpy(mask).cuda()
         launches = acc.launches
         r = acc.render(n, mask=m, stats=stats)
         img = r[0] if stats else r
-        sel = (mask != 0) & valid
+        sel = ((mask != 0) & valid) if mask is not None else valid
         classes = np.unique(expect[sel]).size
         assert acc.launches - launches == classes, (what, i)     # one launch per distinct count among the selected
         expect[sel] += n
@@ -136,15 +144,15 @@ def _run_sequence(d, s, integrator, world, rank, stats, refs, what, oracle_pixel
         assert same_floats(err, want_err), (what, i)
         assert np.array_equal(s_new[~sel], s_old[~sel]), (what, i)       # unselected pixels keep their sums
         n_old, k_old, m2_old, s_old = n_new, k_new, m2_new, s_new
-        if i == 2:
+        if i == 2 and calls is None:
             assert np.unique(counts[valid]).size >= 4 and (counts[valid] == 0).any(), (what, "four counts with 0")
-        if i in (2, 4):
+        if i in check_after:
             _check_contract(img, counts, refs, valid, (what, i))
     assert np.unique(expect[valid]).size >= 4
     if stats:
         assert paths == int(expect[valid].sum()), what             # 3. the paths of the calls add up to sum_p N_p
     if oracle_pixels and world == 1:
-        w, h = RES
+        w, h = res
         rng = np.random.default_rng(99)
         img = _np(img)
         for x, y in [(0, 0), (w - 1, h - 1), (w // 2, h // 2)] + [(int(rng.integers(w)), int(rng.integers(h)))
@@ -153,6 +161,8 @@ def _run_sequence(d, s, integrator, world, rank, stats, refs, what, oracle_pixel
             ref = O.trace_pixel(s, _params(s, integrator, samples=n), x, y)
             print(f"oracle pixel ({x}, {y}) at N = {n}: gpu {img[h - 1 - y, x]} oracle {ref}")
             assert np.array_equal(_bits(img[h - 1 - y, x]), _bits(ref)), (what, x, y, n)
+    if then:
+        then(acc, valid)
     acc.close()
 
 
@@ -241,14 +251,9 @@ def test_a_pixel_of_constant_background_has_error_zero():
     assert same_floats(err, stat_error(_np(st["count"]), _np(st["batches"]), _np(st["m2"]), _np(st["sum"])))
 
 
-def test_render_adaptive():
-    """5.  The driver terminates; every pixel ends at err <= target or count == max_samples; counts are multiples
-    of step; the image is every pixel's render at its own count; two runs agree; one launch per step."""
-    s = scenes.json_scene("disney_spheres.json", res=RES)
-    d = _dev(s)
-    p = _params(s, "mis")
-    refs = _Refs(s, "mis", 1, 0)
-    target, step, cap = 0.08, 4, 40
+def _adaptive_runs(d, p, refs, target, step, cap, what):
+    """render_adaptive twice on fresh accumulators of `d`: what test_render_adaptive states, checked on each run;
+    the first run's (image, counts)."""
     runs = []
     for _ in range(2):
         acc = d.progressive(p)
@@ -262,12 +267,24 @@ def test_render_adaptive():
         assert active == sorted(active, reverse=True)           # a pixel that dropped out stays out
         assert ((err <= target) | (counts == cap)).all()
         assert (counts % step == 0).all() and counts.min() >= 2 * step and counts.max() <= cap
-        _check_contract(img, counts, refs, np.ones(counts.shape, bool), "render_adaptive")
+        _check_contract(img, counts, refs, np.ones(counts.shape, bool), what)
         assert acc.select(target, cap)[1] == 0
         runs.append((_np(img).copy(), counts.copy()))
         acc.close()
     assert np.array_equal(_bits(runs[0][0]), _bits(runs[1][0])) and np.array_equal(runs[0][1], runs[1][1])
     assert np.unique(runs[0][1]).size > 1, "the target separates no pixels: the test shows nothing"
+    return runs[0]
+
+
+def test_render_adaptive():
+    """5.  The driver terminates; every pixel ends at err <= target or count == max_samples; counts are multiples
+    of step; the image is every pixel's render at its own count; two runs agree; one launch per step."""
+    s = scenes.json_scene("disney_spheres.json", res=RES)
+    d = _dev(s)
+    p = _params(s, "mis")
+    refs = _Refs(s, "mis", 1, 0)
+    target, step, cap = 0.08, 4, 40
+    runs = [_adaptive_runs(d, p, refs, target, step, cap, "render_adaptive")]
     # a shard runs the same loop on its own pixels
     acc = d.progressive(_params(s, "mis", tile_world=2, tile_rank=1))
     img = acc.render_adaptive(target, step, cap)
@@ -279,6 +296,150 @@ def test_render_adaptive():
         acc.render_adaptive(target, 4, 42)
     with pytest.raises(ValueError):
         acc.render_adaptive(target, 4, 40, min_samples=4)
+
+
+_big = {}
+
+
+def _big_frame():
+    """The scene at BIG, its one-shot references and one device per scheduler, made once for the tests that share them
+    (and never changed by them)."""
+    if not _big:
+        s = scenes.json_scene("disney_spheres.json", res=BIG)
+        _big.update(s=s, refs=_Refs(s, "mis", 1, 0), cu=_dev(s, scheduler="cu"))
+        _big["lane"] = _big["refs"].dev
+    return _big
+
+
+def _big_calls(shape, valid):
+    """The calls that put the scan's second pass and its carry under _run_sequence's assertions.  The counts: after
+    the third call 2 and 6 left of x = 1024, 1 and 5 right of it; the fifth call's n = 1 lifts list workgroup 1024
+    (right) to 2 and 6, so those two classes of the last call have thousands of members before item 2^20 and 1024
+    after it, while 1 and 5 lie wholly in the second pass; the two single items and the last pixel make two more
+    classes of one member (3 or 7 left, 4 or 8 right).  Six distinct counts at the end.  (Left of x = 1024 only the
+    first and third call and one item of the fifth change anything, so no choice of n gives every class members on
+    both sides.)"""
+    w, h = BIG
+    ok, x, y = _shard_valid(BIG, 1, 0)
+    assert ok.size == 1104 * 1024 and np.array_equal(x[ok] >= 1024, np.flatnonzero(ok) >= 1 << 20)
+    at = lambda items: (h - 1 - y[items], x[items])          # an item's place in the image
+    right = np.ascontiguousarray(np.broadcast_to(np.arange(w) >= 1024, shape))
+    rng = np.random.default_rng(77)
+    first = (rng.random(shape) < 0.6).astype(np.uint8)
+    last = np.flatnonzero(ok)[-1]
+    assert (x[last], y[last]) == (w - 1, h - 1)
+    one = np.zeros(shape, np.uint8)
+    one[at(last)] = 1
+    # list workgroup 1024 whole; beside it one item each of 1023 and 1025: valid ones, the left one at count 2 or 6
+    count3 = np.where(right, 1, 2) + 4 * first.astype(np.int64)
+    group = np.zeros(shape, np.uint8)
+    items = np.arange(1024 * 1024, 1025 * 1024)
+    assert ok[items].all()
+    group[at(items)] = 1
+    for wg in (1023, 1025):
+        items = np.arange(wg * 1024, (wg + 1) * 1024)
+        group[at(items[ok[items]][:1])] = 1
+    assert group.sum() == 1026 and set(np.unique(count3[group != 0])) <= {1, 2, 5, 6}
+    return [(first, 4), (right.astype(np.uint8), 1), ((~right).astype(np.uint8), 2), (one, 3), (group, 1),
+            (np.zeros(shape, np.uint8), 3), (None, 2)]
+
+
+def _check_select(acc, valid):
+    """vimg_hip_progressive_select pixel by pixel: ((err > target) & (N < max_samples)) | (K < 2) from error(),
+    counts() and state(), 0 on a shard's off-image slots, and the returned number of ones."""
+    err, counts = _np(acc.error()), _np(acc.counts())
+    k = _np(acc.state()["batches"])
+    finite = err[valid & np.isfinite(err)]
+    assert finite.size
+    for target in (0.0, float(np.median(finite)), float("inf")):
+        for max_samples in (int(counts[valid].min()), int(counts[valid].max()) + 1):
+            mask, active = acc.select(target, max_samples)
+            want = (((err > np.float32(target)) & (counts < max_samples)) | (k < 2)) & valid
+            assert np.array_equal(_np(mask), want.astype(np.uint8)), (target, max_samples)
+            assert active == int(want.sum()), (target, max_samples)
+
+
+@pytest.mark.parametrize("stats", [False, True])
+@pytest.mark.parametrize("sched", ["cu", "lane"])
+def test_a_frame_above_2_20_items(sched, stats):
+    """The list of a class longer than one scan pass (BIG: 1104 list workgroups, 80 of them in the second pass):
+    _big_calls' seven calls - a random mask, only the second pass, only the first, the last valid item alone, list
+    workgroup 1024 with one item of each neighbour, nothing, everyone - under everything _run_sequence asserts after
+    each call, the one-shot renders after the third and the last, the oracle for four pixels ((1098, 1020) among
+    them), and select() pixel by pixel on the accumulator they leave."""
+    b = _big_frame()
+    _run_sequence(b[sched], b["s"], "mis", 1, 0, stats, b["refs"], (sched, stats), oracle_pixels=1, res=BIG,
+                  calls=_big_calls, check_after=(2, 6), then=_check_select)
+
+
+def test_render_adaptive_above_2_20_items():
+    """test_render_adaptive's statements at BIG: every masked step builds a list through both scan passes."""
+    b = _big_frame()
+    _, counts = _adaptive_runs(b["cu"], _params(b["s"], "mis"), b["refs"], 0.08, 4, 24, "render_adaptive at BIG")
+    assert counts[:, 1024:].max() > 8 and counts[:, :1024].max() > 8       # masked steps had members in both passes
+
+
+def test_a_shard_above_2_20_items():
+    """A shard whose own items pass 2^20 (BIG_SHARD, rank 1 of 2: 1055 list workgroups): _masks' five calls on cu.
+    225 x 150 tiles cover the frame exactly, so this shard has no off-image slots; what they hold (count 0, error
+    0, select mask 0) is asserted on the ragged shard of test_select_on_a_ragged_shard."""
+    s = scenes.json_scene("disney_spheres.json", res=BIG_SHARD)
+    d = _dev(s, scheduler="cu")
+    assert _shard_valid(BIG_SHARD, 2, 1)[0].sum() == 1080000
+    _run_sequence(d, s, "mis", 2, 1, True, _Refs(s, "mis", 2, 1), "shard above 2^20", res=BIG_SHARD, then=_check_select)
+
+
+def test_select_on_a_ragged_shard():
+    """select() pixel by pixel where a shard has slots off the image: those are 0 in the mask, the error and the
+    counts, and are not counted."""
+    s = scenes.json_scene("disney_spheres.json", res=RES)
+    valid = _shard_valid(RES, 2, 1)[0]
+    assert not valid.all()
+
+    def then(acc, v):
+        assert not _np(acc.error())[~v].any() and not _np(acc.counts())[~v].any()
+        _check_select(acc, v)
+
+    _run_sequence(_dev(s), s, "mis", 2, 1, False, _Refs(s, "mis", 2, 1), "select on a shard", then=then)
+
+
+def test_twelve_classes_in_one_call():
+    """Four striped masks with n = 1, 2, 4, 8 write the bits of x % 12 into the counts; the unmasked call that
+    follows is twelve launches, one per class, and every pixel is the render at its own count."""
+    s = scenes.json_scene("disney_spheres.json", res=RES)
+    acc = _dev(s).progressive(_params(s, "mis"))
+    want = np.broadcast_to(np.arange(RES[0]) % 12, acc.pixel_shape).astype(np.int64)
+    for bit in range(4):
+        acc.render(1 << bit, mask=((want >> bit) & 1).astype(np.uint8), out=False)
+    assert np.array_equal(_np(acc.counts()), want) and np.unique(want).size == 12
+    before = acc.launches                      # (1 + 2 + 4 + 4: the classes among the pixels each stripe selected)
+    img = acc.render(1)
+    assert acc.launches - before == 12
+    assert np.array_equal(_np(acc.counts()), want + 1) and acc.samples == 12
+    _check_contract(img, want + 1, _Refs(s, "mis", 1, 0), np.ones(want.shape, bool), "twelve classes")
+
+
+@pytest.mark.parametrize("name", list(SEQUENCES))
+def test_the_statistic_of_a_long_run_against_float64(name):
+    """A real accumulator through the 8 to 256 increments of SEQUENCES (up to 512 samples): the sums after every
+    increment give the float64 model of tests/test_adaptive_abi.py, which holds the final M2 and error() by its derived
+    bound; they are also the numpy restatement's bit for bit, and the image is the one-shot render at N."""
+    ns = SEQUENCES[name]
+    s = scenes.json_scene("cornell_box_spheres.json", res=(64, 64))
+    d = _dev(s)
+    acc = d.progressive(_params(s, "mis"))
+    sums = [np.zeros(acc.pixel_shape + (3,), np.float32)]
+    for i, n in enumerate(ns):
+        img = acc.render(n, out=None if i == len(ns) - 1 else False)
+        sums.append(_np(acc.state()["sum"]))
+    st = acc.state()
+    assert (_np(st["count"]) == sum(ns)).all() and (_np(st["batches"]) == len(ns)).all() and acc.launches == len(ns)
+    m2, err = _np(st["m2"]), _np(acc.error())
+    check_against_model(("device", name), np.stack(sums), ns, m2, err)
+    _, _, m2_np, err_np = restatement_over(sums, ns)
+    assert same_floats(m2, m2_np) and same_floats(err, err_np)
+    want = d.render(_params(s, "mis", samples=sum(ns)), stats=False)
+    assert np.array_equal(_bits(img), _bits(want))
 
 
 def test_lifecycle_and_errors():

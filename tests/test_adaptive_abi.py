@@ -54,6 +54,138 @@ def same_floats(a, b):
     return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
 
 
+# ---- the statistic from its definition, float64: what the float32 expressions above are supposed to estimate ------
+U = 2.0 ** -24                                 # unit roundoff of float32
+# (the kernel's weights ARE these float32 numbers: the model takes them as exact inputs, like the sums)
+LUM64 = np.array([F(0.212671), F(0.715160), F(0.072169)], dtype=np.float64)
+# the increment lengths of the long runs (tests/test_adaptive.py runs the same four on a device)
+SEQUENCES = {"128x4": (4,) * 128, "256x1": (1,) * 256, "32x16": (16,) * 32, "unequal": (1, 7, 64, 3, 128, 5, 2, 90)}
+
+
+def model_stat(sums, ns):
+    """The statistic of a pixel whose float32 running sums were sums[0] = 0, sums[1], ..., sums[K] ([K + 1, ..., 3])
+    after increments of ns[0], ..., ns[K - 1] samples, in float64 and from the definition - not from adapt_m2:
+    b_i = Y(S_i - S_{i-1}) / n_i, N = sum n_i, m = Y(S_K) / N, M2 = sum n_i (b_i - m)^2 in closed form (the
+    incremental form equals it exactly in real arithmetic), err = sqrt(M2 / (K - 1) / N) / (|m| + 1e-3).
+    Returns (N, m, M2, err, bound), `bound` the derived limit of |M2_float32 - M2| (m2_bound)."""
+    s = np.asarray(sums, dtype=np.float64)
+    ns = np.asarray(ns, dtype=np.float64)
+    k, n_all = len(ns), ns.sum()
+    assert s.shape[0] == k + 1 and k >= 2 and not s[0].any()
+    shape = (k,) + (1,) * (s.ndim - 2)
+    b = ((s[1:] - s[:-1]) @ LUM64) / ns.reshape(shape)
+    m = (s[-1] @ LUM64) / n_all
+    m2 = (ns.reshape(shape) * (b - m) ** 2).sum(axis=0)
+    err = np.sqrt(m2 / (k - 1) / n_all) / (np.abs(m) + 1e-3)
+    return n_all, m, m2, err, m2_bound(s, ns)
+
+
+def m2_bound(s, ns):
+    """How far the float32 M2 of include/vimg_hip.h may lie from model_stat's, derived (u = 2^-24), not fitted.
+    b = ((x1 - x0) w0 + (y1 - y0) w1 + (z1 - z0) w2) / float(n) is a subtraction, a product, two additions and a
+    division on exact inputs - five roundings on a sum of terms of one sign (sums of radiance only grow) - and m_old,
+    m_new are four (float(N) is exact below 2^24): each is off by at most 6 u of itself, so a difference b - m_x is
+    off by at most 12 u L, L = max(|b|, |m_old|, |m_new|), before its own rounding.  The term n (b - m_old)(b - m_new)
+    is then off by n 12 u L (|b - m_old| + |b - m_new| + 12 u L) from the two perturbed factors, and by 4 u |term|
+    from its own four roundings (two subtractions, two products).  Adding it to M2 rounds once more: u |M2|.  The
+    bound is the sum of the three over the increments.  It is absolute: on a pixel whose samples nearly agree M2 is
+    some 1e-8 m^2 and the first part dominates it."""
+    s, ns = np.asarray(s, dtype=np.float64), np.asarray(ns, dtype=np.float64)
+    bound, m2, n_old = 0.0, 0.0, 0.0
+    for i, n in enumerate(ns):
+        b = ((s[i + 1] - s[i]) @ LUM64) / n
+        m_old = (s[i] @ LUM64) / n_old if n_old else 0.0 * b
+        m_new = (s[i + 1] @ LUM64) / (n_old + n)
+        big = np.maximum(np.abs(b), np.maximum(np.abs(m_old), np.abs(m_new)))
+        term = n * (b - m_old) * (b - m_new)
+        m2 = m2 + term
+        bound = bound + n * 12 * U * big * (np.abs(b - m_old) + np.abs(b - m_new) + 12 * U * big) + 4 * U * np.abs(term) \
+            + U * np.abs(m2)
+        n_old += n
+    return bound
+
+
+def check_against_model(what, sums, ns, m2_f32, err_f32):
+    """|M2_float32 - M2| <= bound and the matching limit of err, no extra factor; prints the worst ratios.  Returns
+    (worst |dM2| / bound, worst |dM2| / M2)."""
+    n_all, m, m2, err, bound = model_stat(sums, ns)
+    k = len(ns)
+    d = np.abs(np.asarray(m2_f32, dtype=np.float64) - m2)
+    ratio = float(np.max(np.where(bound > 0, d / np.where(bound > 0, bound, 1), np.where(d > 0, np.inf, 0.0))))
+    pos = m2 > 0
+    rel = float(np.max(d[pos] / m2[pos])) if pos.any() else 0.0
+    e = np.asarray(err_f32, dtype=np.float64)
+    e_lim = np.where(pos, err * (8 * U + 0.5 * bound / np.where(pos, m2, 1)), np.sqrt(bound / (k - 1) / n_all) / (np.abs(m) + 1e-3))
+    e_off = np.where(pos, np.abs(e - err), e)
+    e_ratio = float(np.max(np.where(e_lim > 0, e_off / np.where(e_lim > 0, e_lim, 1), np.where(e_off > 0, np.inf, 0.0))))
+    print(f"{what}: worst |M2_f32 - M2_f64| / bound {ratio:.3f}, worst relative error of M2 {rel:.3e}, "
+          f"worst |err_f32 - err_f64| / its limit {e_ratio:.3f}")
+    assert (d <= bound).all(), (what, "M2", ratio)
+    assert (e_off <= e_lim).all(), (what, "err", e_ratio)
+    return ratio, rel
+
+
+def restatement_over(sums, ns):
+    """stat_update over the whole sequence (every pixel selected every time), then stat_error: (N, K, M2, err)."""
+    shape = np.asarray(sums[0]).shape[:-1]
+    n, k, m2 = np.zeros(shape, np.uint32), np.zeros(shape, np.uint32), np.zeros(shape, F)
+    for i, inc in enumerate(ns):
+        n, k, m2 = stat_update(n, k, m2, sums[i], sums[i + 1], inc, np.ones(shape, bool))
+    return n, k, m2, stat_error(n, k, m2, sums[-1])
+
+
+def synthetic_sums(kind, ns, pixels, seed):
+    """Float32 running sums [K + 1, pixels, 3] of per-sample radiances added one by one in float32, as the render
+    kernels add them: gamma-distributed noise; near-constant (relative spread 1e-4); 1 % fireflies of x 1e4."""
+    rng = np.random.default_rng(seed)
+    base = rng.uniform(0.05, 2.0, (pixels, 3)).astype(F)
+    run = np.zeros((pixels, 3), F)
+    sums = [run.copy()]
+    for n in ns:
+        if kind == "near-constant":
+            y = base * (F(1) + F(1e-4) * (F(2) * rng.random((n, pixels, 3), dtype=F) - F(1)))
+        else:
+            y = base * (F(0.5) * rng.standard_gamma(2.0, (n, pixels, 3), dtype=F))
+            if kind == "firefly":
+                y = y * np.where(rng.random((n, pixels, 1), dtype=F) < F(0.01), F(1e4), F(1))
+        for sample in y:
+            run = run + sample
+        sums.append(run.copy())
+    return np.stack(sums)
+
+
+def test_the_model_is_the_textbook_standard_error():
+    """With every increment one sample long, err (|m| + 1e-3) is the standard error of the mean of the samples'
+    luminances: np.std(y, ddof=1) / sqrt(N)."""
+    ns = (1,) * 200
+    sums = synthetic_sums("noisy", ns, 50, 7)
+    n_all, m, m2, err, _ = model_stat(sums, ns)
+    y = (sums[1:].astype(np.float64) - sums[:-1].astype(np.float64)) @ LUM64
+    assert n_all == 200
+    assert np.allclose(m, y.mean(axis=0), rtol=1e-12, atol=0)
+    assert np.allclose(err * (np.abs(m) + 1e-3), np.std(y, axis=0, ddof=1) / np.sqrt(200), rtol=1e-12, atol=0)
+
+
+def test_the_float32_statistic_stays_within_its_derived_bound_of_the_float64_model():
+    """The incremental float32 M2 and err, after the 8 to 256 increments of SEQUENCES, against model_stat on 20 000
+    synthetic pixels of each kind; the bound is m2_bound's, derived there.  Figures of this test (the worst over
+    all twelve cases): DESIGN.md 4.14."""
+    worst, rel_noisy, rel_const = 0.0, 0.0, 0.0
+    for kind in ("noisy", "near-constant", "firefly"):
+        for j, (name, ns) in enumerate(SEQUENCES.items()):
+            sums = synthetic_sums(kind, ns, 20000, 100 + j)
+            n, k, m2, err = restatement_over(sums, ns)
+            assert (n == sum(ns)).all() and (k == len(ns)).all()
+            ratio, rel = check_against_model((kind, name), sums, ns, m2, err)
+            worst = max(worst, ratio)
+            if kind == "noisy":
+                rel_noisy = max(rel_noisy, rel)
+            if kind == "near-constant":
+                rel_const = max(rel_const, rel)
+    print(f"all cases: worst |dM2| / bound {worst:.3f}; worst relative error of M2: noisy {rel_noisy:.2e}, "
+          f"near-constant {rel_const:.2e}")
+
+
 def test_the_restatement_on_values_worked_by_hand():
     # two increments of 2 samples on one grey pixel: sums 2 -> 6 (batch means 1 and 2; Y of grey = sum of weights)
     w = F(0.212671) + F(0.715160) + F(0.072169)
