@@ -615,7 +615,15 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
     // state.  On a frame short of pixels the last pixels' chains of (vertex stage, walk) hops are
     // the frame time, and the walk then runs beside most of the vertex stage instead of behind it.
     // A slot is complete when its rays AND its vertex stage have finished (CF_DONE_V, the last OR decides).
+    //
+    // A build that queues its rays LATE (EARLY == 0) gains nothing from that order and pays for it - the skip is a
+    // 64-bit multiply-add, and a second generator state lives across the BSDF sample: its Lambertian batches
+    // (LIGHT_FIRST) take the light sample first, from `rng`, and the BSDF sample from the state it leaves.  The
+    // same draws for the same consumers.  (Not its Principled batches: the textured build pays 16 B of scratch for
+    // the emitter record alive across the BSDF sample, and the untextured one gains nothing: DESIGN.md 4.4.)
     constexpr int MT = MTC;
+    constexpr bool LAMB = MT == int(VIMG_MAT_LAMBERTIAN);
+    constexpr bool LIGHT_FIRST = EARLY == 0 && LAMB;
     const bool early_on = EARLY == 2 ? (A.cu_flex & 32u) != 0u : (EARLY == 1);   // (a build of its own: as a runtime branch it costs the whole frame 1.2 %)
     uint32_t mat_type = 0u;
     float hit_dist = 0.f, surface_spread_angle = 0.f;
@@ -632,8 +640,13 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         surface_spread_angle = spread_angle_from_curvature(hit.curvature, cone.cone_width, ray_d, hit.ns);
       }
       reg_before = non_specular_bounce;
-      rng_l = rng;
-      if (mat_type != VIMG_MAT_DIELECTRIC) pcg_skip6(rng);   // (!is_delta: the light sample's six draws)
+      if constexpr (LIGHT_FIRST) {   // (not a delta material: the light is always sampled)
+        lights_sample<TEX>(g, hit.p, rng, light_col, li);
+        nee = (li.pdf != 0.f);
+      } else {
+        rng_l = rng;
+        if (mat_type != VIMG_MAT_DIELECTRIC) pcg_skip6(rng);   // (!is_delta: the light sample's six draws)
+      }
       sc = sample_mat<TEX, MT>(g, hit, ray_d, rng, reg_before);
       if constexpr (TEX) nee_cone = propagate_reflect_cone(cone, surface_spread_angle * 2.f, hit_dist);
       if (sc.valid) {
@@ -661,9 +674,11 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
     }
     if (early_on) push_rays(false, pushed_r, slot);
     pv_lap(3);
-    if (at_vertex && mat_type != VIMG_MAT_DIELECTRIC) {
-      lights_sample<TEX>(g, hit.p, rng_l, light_col, li);
-      nee = (li.pdf != 0.f);
+    if constexpr (!LIGHT_FIRST) {
+      if (at_vertex && mat_type != VIMG_MAT_DIELECTRIC) {
+        lights_sample<TEX>(g, hit.p, rng_l, light_col, li);
+        nee = (li.pdf != 0.f);
+      }
     }
     if (rec_written && nee) {
       // the shadow ray and its reach (the reference's absolute epsilon, quirk Q15) beside a record whose
@@ -682,21 +697,41 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
       // regularisation flag is the one from BEFORE this bounce
       f3 f_l{0.f, 0.f, 0.f}, f_s{0.f, 0.f, 0.f};   // towards the light / along the sampled direction
       float pdf_l = 0.f, pdf_s = 0.f;
-#pragma unroll 1
-      for (int pass = 0; pass < (split ? 1 : 2); ++pass) {
-        const bool second = split ? mirror : (pass == 1);   // which of the two this lane evaluates in this pass
-        const bool run = second ? sc.valid : nee;
-        f3 f{0.f, 0.f, 0.f};
-        float pdf = 0.f;
-        if (run) {
-          const v4u w4 = rd(second ? CR_DIR : CR_SHD, slot);   // (sc.wo / li.wi, from the slot's record)
-          const f3 wo{uf(w4.x), uf(w4.y), uf(w4.z)};
-          const RayCone c = second ? cone : nee_cone;
-          const bool reg = second ? non_specular_bounce : reg_before;
-          eval_pdf_pair<TEX, MT>(g, hit, ray_d, wo, c, reg, f, pdf);
+      if constexpr (LAMB) {
+        // Lambertian::eval_pdf_pair (the Lambertian branch of render_kernels.h: eval_pdf_pair, restated) for both
+        // directions, in line, from li.wi and sc.wo in registers.  The loop below exists to share the Principled
+        // evaluation's code between its two uses and to park ten registers in the slot's record meanwhile; a
+        // Lambertian evaluation is a cosine over pi times a colour and needs neither: no read-back of the
+        // directions, the DMaterial bits tested once.  The colour is a function of the hit alone (a textured build
+        // looks it up under the reflected cone, which is `nee_cone` for the light and - a Lambertian scatter does
+        // not refract - `cone` itself for the sampled direction): once for both.  The two double quotients stand
+        // side by side so that their chains overlap.
+        if (nee || sc.valid) {
+          gptr<DMaterial> dm = g.dmaterials + hit.mat;
+          const f3 col = (dm->bits & DMAT_COLOUR) ? load3(dm->base)
+                                                  : col_at_ray_hit<TEX>(g, g.materials[hit.mat].tex, ray_d, nee_cone, hit);
+          const float cos_l = sel_max(0.0f, dot(li.wi, hit.ns)), cos_s = sel_max(0.0f, dot(sc.wo, hit.ns));
+          const float dp_l = static_cast<float>(cos_l / kPi), dp_s = static_cast<float>(cos_s / kPi);
+          if (nee) f_l = col * dp_l, pdf_l = dp_l;
+          if (sc.valid) f_s = col * dp_s, pdf_s = dp_s;
         }
-        if (second) f_s = f, pdf_s = pdf;
-        else f_l = f, pdf_l = pdf;
+      } else {
+#pragma unroll 1
+        for (int pass = 0; pass < (split ? 1 : 2); ++pass) {
+          const bool second = split ? mirror : (pass == 1);   // which of the two this lane evaluates in this pass
+          const bool run = second ? sc.valid : nee;
+          f3 f{0.f, 0.f, 0.f};
+          float pdf = 0.f;
+          if (run) {
+            const v4u w4 = rd(second ? CR_DIR : CR_SHD, slot);   // (sc.wo / li.wi, from the slot's record)
+            const f3 wo{uf(w4.x), uf(w4.y), uf(w4.z)};
+            const RayCone c = second ? cone : nee_cone;
+            const bool reg = second ? non_specular_bounce : reg_before;
+            eval_pdf_pair<TEX, MT>(g, hit, ray_d, wo, c, reg, f, pdf);
+          }
+          if (second) f_s = f, pdf_s = pdf;
+          else f_l = f, pdf_l = pdf;
+        }
       }
       pv_lap(4);
       if (split) {   // the owner lane takes the sampled direction's evaluation from its mirror lane

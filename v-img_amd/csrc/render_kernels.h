@@ -1278,6 +1278,7 @@ VD void eval_pdf_pair(const DScene& g, const Hit& hit, f3 wi, f3 wo, RayCone con
   const uint32_t type = MT >= 0 ? uint32_t(MT) : m->type;
   if (type == VIMG_MAT_LAMBERTIAN) {
     // Lambertian::eval_pdf_pair, reference src/material/lambertian.cpp:47-54
+    // (render_cu_kernel.h's Lambertian batches restate these lines for both directions of a vertex at once)
     float dot_product = static_cast<float>(sel_max(0.0f, dot(wo, hit.ns)) / kPi);
     gptr<DMaterial> dm = g.dmaterials + hit.mat;
     const f3 col = (dm->bits & DMAT_COLOUR) ? load3(dm->base) : col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit);
