@@ -1,5 +1,5 @@
-"""ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h and
-include/vimg_temporal.h.
+"""ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
+include/vimg_temporal.h, include/vimg_varfilter.h and include/vimg_moments.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -386,6 +386,28 @@ VARFILTER_SYMBOLS = {
 }
 
 
+class MomentsFrames(_Sized, C.Structure):
+    """VimgMomentsFrames (include/vimg_moments.h): VimgTemporalFrames and the per-pixel variance frame (float32)."""
+    _fields_ = TemporalFrames._fields_ + [("variance", C.c_void_p)]
+
+
+class MomentsParams(_Sized, C.Structure):
+    """VimgMomentsParams (include/vimg_moments.h): VimgTemporalParams and min_history; vimg_moments_defaults fills it."""
+    _fields_ = TemporalParams._fields_ + [("min_history", f32)]
+
+
+MOMENTS_HISTORY_PER_PIXEL = 64
+
+# the list of symbols include/vimg_moments.h declares: libvimg_moments.so, temporal accumulation with luminance moments
+MOMENTS_SYMBOLS = {
+    "vimg_moments_defaults": (None, [C.POINTER(MomentsParams)]),
+    "vimg_moments_history_bytes": (C.c_uint64, [u32, u32]),
+    "vimg_moments_accumulate": (C.c_int, [C.POINTER(MomentsFrames), C.c_void_p, Pf32, C.POINTER(MomentsParams), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_moments_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -403,6 +425,7 @@ _LIBRARIES = {
     "filter": ("libvimg_filter.so", (FILTER_SYMBOLS,), "filter", "; there is no CPU fallback for the filter", True),
     "temporal": ("libvimg_temporal.so", (TEMPORAL_SYMBOLS,), "temporal", "; there is no CPU fallback for temporal accumulation", True),
     "varfilter": ("libvimg_varfilter.so", (VARFILTER_SYMBOLS,), "varfilter", "; there is no CPU fallback for the filter", True),
+    "moments": ("libvimg_moments.so", (MOMENTS_SYMBOLS,), "moments", "; there is no CPU fallback for temporal accumulation", True),
 }
 _loaded = {}
 
@@ -449,3 +472,8 @@ def temporal_lib():
 def varfilter_lib():
     """The variance-guided filter library (include/vimg_varfilter.h)."""
     return _load("varfilter")
+
+
+def moments_lib():
+    """The temporal accumulation library with luminance moments (include/vimg_moments.h)."""
+    return _load("moments")

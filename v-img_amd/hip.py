@@ -298,17 +298,19 @@ class DeviceScene:
         return flt.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
                           stream=stream, **filter_kw)
 
-    def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, **temporal_kw):
+    def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, **temporal_kw):
         """A preview that survives a moving camera (vimg_amd.temporal.TemporalPreview, include/vimg_temporal.h): its
         ``frame()`` renders ``samples`` more samples of the scene as it now stands and returns the [H, W, 3] picture -
         after set_camera or an edit blended with the last picture reprojected into the new camera, while nothing
         changes the plain progressive stream blended with that history - filtered by filter.atrous when ``denoise``, its sigma_color divided by the square root of the frames accumulated.
         ``temporal_kw``: max_history, sigma_normal, sigma_plane, ``filter_kw`` (a dict for filter.atrous),
-        ``scale_sigma_color`` (False: the filter's sigma_color as it is).  Whole
-        frames only."""
+        ``scale_sigma_color`` (False: the filter's sigma_color as it is).  ``variance_guided``: the histories carry the
+        moments of luminance (vimg_amd.moments, include/vimg_moments.h) and varfilter.atrous filters each pixel by the
+        variance of its own accumulated mean; ``filter_kw`` are then its parameters, ``temporal_kw`` takes min_history
+        too and ``scale_sigma_color`` is refused.  Whole frames only."""
         from . import temporal
         return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
-                                        **temporal_kw)
+                                        variance_guided=variance_guided, **temporal_kw)
 
     def _new_output(self, params, zero_slab=True):
         """A frame [H, W, 3] for these parameters, or the shard's compact slab [shard_pixels, 3] when tile_world > 1

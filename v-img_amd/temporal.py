@@ -132,28 +132,49 @@ class TemporalPreview:
     Progressive.preview filters it).  It is one factor for the picture: pixels that have just started over are filtered
     as lightly as the rest.  ``scale_sigma_color=False`` passes sigma_color as it is.
 
+    ``variance_guided`` (with ``denoise``) lifts that limit: the histories carry the moments of luminance
+    (vimg_amd.moments, include/vimg_moments.h; ``temporal_kw`` then takes min_history too), a frame is acc.render,
+    acc.variance() once this camera position has had two increments (else no variance frame), moments.accumulate and
+    varfilter.atrous on the accumulated colour with the variance the moments give - NaN where the history is shorter
+    than min_history, which the filter estimates from the pixel's surroundings.  ``filter_kw`` are then
+    varfilter.atrous's parameters, ``scale_sigma_color`` is refused, and ``history`` is a moments.History.  The
+    accumulated colour, the history lengths and the accumulator are bit for bit what they are without it.
+
     Limits: history from before a geometry or material edit is reprojected all the same and fades at 1 / max_history
     per frame (``reset()`` drops it); a thin lens is treated as its pinhole; see include/vimg_temporal.h."""
 
-    def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=True,
-                 **temporal_kw):
+    def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
+                 variance_guided=False, **temporal_kw):
         import torch
         from . import filter as flt
         if params.tile_world != 1:
             raise ValueError("temporal_preview: reprojection reads whole frames, not shards (tile_world must be 1)")
         if int(samples) < 1 or int(feature_samples) < 1:
             raise ValueError("temporal_preview: samples and feature_samples must be at least 1")
-        unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"})
+        self.variance_guided = bool(variance_guided)
+        if self.variance_guided and not denoise:
+            raise ValueError("temporal_preview: variance_guided chooses the filter, so it needs denoise=True")
+        if self.variance_guided and scale_sigma_color is not None:
+            raise ValueError("temporal_preview: scale_sigma_color belongs to the fixed filter; the variance-guided filter has no "
+                             "sigma_color")
+        unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"} - ({"min_history"} if variance_guided else set()))
         if unknown:
             raise TypeError(f"temporal_preview: unknown parameters {unknown}")
         self._dev, self.samples, self.denoise, self.feature_samples = dev, int(samples), bool(denoise), int(feature_samples)
-        self.temporal_kw, self.filter_kw, self.scale_sigma_color = dict(temporal_kw), dict(filter_kw or {}), bool(scale_sigma_color)
+        self.temporal_kw, self.filter_kw = dict(temporal_kw), dict(filter_kw or {})
+        self.scale_sigma_color = scale_sigma_color is None or bool(scale_sigma_color)
         self.acc = dev.progressive(params)
         w, h = dev.resolution
-        self._buffers = [torch.empty((3, h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-        self._workspace = torch.empty((flt.atrous_workspace_bytes(w, h),), dtype=torch.uint8, device="cuda") if denoise else None
+        self._buffers = [torch.empty((4 if self.variance_guided else 3, h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
         self._features = flt.GUIDES if denoise else ("normal", "position", "depth")
-        self._sigma_color = float(self.filter_kw.pop("sigma_color", None) or flt.atrous_params().sigma_color) if denoise else None
+        if self.variance_guided:
+            from . import varfilter
+            self._workspace = torch.empty((varfilter.workspace_bytes(w, h),), dtype=torch.uint8, device="cuda")
+            self._variance = torch.empty((h, w), dtype=torch.float32, device="cuda")
+            self._sigma_color = None
+        else:
+            self._workspace = torch.empty((flt.atrous_workspace_bytes(w, h),), dtype=torch.uint8, device="cuda") if denoise else None
+            self._sigma_color = float(self.filter_kw.pop("sigma_color", None) or flt.atrous_params().sigma_color) if denoise else None
         self._max_history = float(temporal_params(max_history=temporal_kw.get("max_history")).max_history)
         self._guides = GuideCache(dev)
         self.reset()
@@ -182,6 +203,8 @@ class TemporalPreview:
         mean = acc.render(self.samples, stream=stream)
         self._k += 1
         target = mean if out is None else out
+        if self.variance_guided:
+            return self._frame_variance_guided(mean, g, target, stream)
         self.history = accumulate(mean, g["normal"], g["position"], g["depth"], history=self._frozen,
                                   world_to_pixel=world_to_pixel(dev.camera), out=target, next_history=self._buffers[self._write],
                                   stream=stream, current_weight=self._k, **self.temporal_kw)
@@ -191,6 +214,21 @@ class TemporalPreview:
             sigma_color = self._sigma_color / math.sqrt(n)
             flt.atrous(target, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=target, workspace=self._workspace,
                        stream=stream, sigma_color=sigma_color, **self.filter_kw)
+        return target
+
+    def _frame_variance_guided(self, mean, g, target, stream):
+        """The rest of frame() with ``variance_guided``: moments.accumulate in place of accumulate, handing the variance
+        of the accumulated colour to varfilter.atrous.  The accumulator knows a variance once this camera position has
+        had two increments; until then the moments alone say what a pixel's noise is."""
+        from . import moments, varfilter
+        known = self.acc.variance(stream) if self._k >= 2 else None
+        self.history = moments.accumulate(mean, g["normal"], g["position"], g["depth"], variance=known, history=self._frozen,
+                                          world_to_pixel=world_to_pixel(self._dev.camera), out=target, out_variance=self._variance,
+                                          next_history=self._buffers[self._write], stream=stream, current_weight=self._k,
+                                          **self.temporal_kw)
+        self._frames += 1
+        varfilter.atrous(target, g["normal"], g["position"], g["depth"], albedo=g["albedo"], variance=self._variance, out=target,
+                         workspace=self._workspace, stream=stream, **self.filter_kw)
         return target
 
     def close(self):
