@@ -357,12 +357,20 @@ __global__ void ploc_nearest(const uint32_t* __restrict__ cluster, const float* 
   float mine[6];
   for (int a = 0; a < 6; ++a) mine[a] = box[size_t(cluster[i]) * 6 + a];
   const uint32_t lo = i > radius ? i - radius : 0u, hi = (i + radius < c - 1u) ? i + radius : c - 1u;
+  // The partner is the smallest PAIR in a total order that both ends compute alike: (union's half area, lower
+  // position odd, distance, lower position).  The smallest pair of the array is then mutual, so a round always
+  // merges; and where unions tie exactly (equal boxes at equal spacing, coincident boxes) the even / odd term makes
+  // every second pair mutual.  Without it ("ties go to the lower index") such input has ONE mutual pair per round:
+  // a round per primitive, and past the round limit no tree.  tests/bvh_build_ref.py:nearest carries the same order.
   float best = __builtin_huge_valf();
+  unsigned long long best_key = ~0ull;
   uint32_t best_j = i;
   for (uint32_t j = lo; j <= hi; ++j) {
     if (j == i) continue;
     const float sa = union_half_area(mine, box + size_t(cluster[j]) * 6);
-    if (sa < best) best = sa, best_j = j;   // ties: the lower index (both sides see the same order)
+    const uint32_t low = j < i ? j : i, dist = j < i ? i - j : j - i;   // (both below 2^25)
+    const unsigned long long key = (static_cast<unsigned long long>(low & 1u) << 62) | (static_cast<unsigned long long>(dist) << 31) | low;
+    if (sa < best || (sa == best && key < best_key)) best = sa, best_key = key, best_j = j;
   }
   nn[i] = best_j;
 }
@@ -691,8 +699,9 @@ int ploc_core(uint32_t n, const float* bounds, vimg::DeviceTree* out) {
     uint32_t created = 0;
     HIP_TRY(hipMemcpy(&created, d_counter.p, 4, hipMemcpyDeviceToHost));   // (also the round's synchronisation)
     const uint32_t c_new = n - created;
-    if (c_new >= c || ++rounds > 4096)   // a round always merges the closest pair at least
+    if (c_new >= c)   // (the smallest pair of ploc_nearest's order is mutual: only NaN boxes get here)
       return fail(VIMG_E_DEVICE, "build_ploc: a clustering round merged nothing");
+    if (++rounds > 4096) return fail(VIMG_E_DEVICE, "build_ploc: the clustering rounds ran out (more than 4096)");
     c = c_new;
     cur ^= 1;
   }
