@@ -1,5 +1,5 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
-include/vimg_temporal.h, include/vimg_varfilter.h and include/vimg_moments.h.
+include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h and include/vimg_infill.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -408,6 +408,30 @@ MOMENTS_SYMBOLS = {
 }
 
 
+class InfillFrames(_Sized, C.Structure):
+    """VimgInfillFrames (include/vimg_infill.h): VimgFilterFrames and the per-pixel sample count (uint32)."""
+    _fields_ = FilterFrames._fields_ + [("count", C.c_void_p)]
+
+
+class InfillParams(_Sized, C.Structure):
+    """VimgInfillParams (include/vimg_infill.h); vimg_infill_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("radius", u32), ("sigma_normal", f32), ("sigma_plane", f32), ("albedo_floor", f32)]
+
+
+INFILL_WORKSPACE_PER_PIXEL = 48
+INFILL_MAX_RADIUS = 4
+INFILL_SAMPLED, INFILL_GUIDED, INFILL_UNGUIDED, INFILL_HOLE = 0, 1, 2, 3
+
+# the list of symbols include/vimg_infill.h declares: libvimg_infill.so, reconstruction of sparsely sampled frames
+INFILL_SYMBOLS = {
+    "vimg_infill_defaults": (None, [C.POINTER(InfillParams)]),
+    "vimg_infill_workspace": (C.c_uint64, [u32, u32]),
+    "vimg_infill_reconstruct": (C.c_int, [C.POINTER(InfillFrames), C.POINTER(InfillParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.c_void_p]),
+    "vimg_infill_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -426,6 +450,7 @@ _LIBRARIES = {
     "temporal": ("libvimg_temporal.so", (TEMPORAL_SYMBOLS,), "temporal", "; there is no CPU fallback for temporal accumulation", True),
     "varfilter": ("libvimg_varfilter.so", (VARFILTER_SYMBOLS,), "varfilter", "; there is no CPU fallback for the filter", True),
     "moments": ("libvimg_moments.so", (MOMENTS_SYMBOLS,), "moments", "; there is no CPU fallback for temporal accumulation", True),
+    "infill": ("libvimg_infill.so", (INFILL_SYMBOLS,), "infill", "; there is no CPU fallback for the reconstruction", True),
 }
 _loaded = {}
 
@@ -477,3 +502,8 @@ def varfilter_lib():
 def moments_lib():
     """The temporal accumulation library with luminance moments (include/vimg_moments.h)."""
     return _load("moments")
+
+
+def infill_lib():
+    """The reconstruction library for sparsely sampled frames (include/vimg_infill.h)."""
+    return _load("infill")

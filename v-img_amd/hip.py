@@ -312,6 +312,16 @@ class DeviceScene:
         return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
                                         variance_guided=variance_guided, **temporal_kw)
 
+    def render_sparse(self, params, stride=2, **kw):
+        """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,
+        **kw)`` - ``params.samples`` samples for one pixel in stride^2, the others filled from the feature frames
+        (vimg_amd.infill, include/vimg_infill.h) - and the accumulator closed.  Returns the [H, W, 3] image."""
+        acc = self.progressive(params)
+        try:
+            return acc.render_sparse(params.samples, stride=stride, **kw)
+        finally:
+            acc.close()
+
     def _new_output(self, params, zero_slab=True):
         """A frame [H, W, 3] for these parameters, or the shard's compact slab [shard_pixels, 3] when tile_world > 1
         (zeroed, when asked: a ragged shard has slots off the image that no launch writes)."""
@@ -612,6 +622,7 @@ class Progressive:
         _check(self._lib.vimg_hip_progressive_create(dev._h, C.byref(self.params), C.byref(h)))
         self._h = h
         self._guide_cache = GuideCache(dev)
+        self._sparse_calls = 0       # render_sparse calls since creation or the last reset: the next lattice phase
 
     @property
     def _guides(self):           # (key, the four feature frames) of the last preview, or None
@@ -681,6 +692,29 @@ class Progressive:
             return varfilter.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], variance=self.variance(stream),
                                     out=out, stream=stream, **filter_kw)[0]
         return flt.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=out, stream=stream, **filter_kw)
+
+    def render_sparse(self, samples, stride=2, radius=None, out=None, stream=None, feature_samples=4, **infill_kw):
+        """``samples`` more samples for ONE pixel in stride^2 - the lattice infill.lattice_mask(H, W, stride, phase)
+        with phase = (calls since creation or reset) % stride^2 - and the picture with the other pixels filled from
+        the feature frames (vimg_amd.infill.reconstruct on the guides ``preview`` keeps, and ``counts()``).  The
+        pixels of one lattice stand at one count, so each call is one render launch; after stride^2 calls every pixel
+        has had ``samples`` more and the picture is ``render``'s bit for bit.  The accumulator keeps the plain sums:
+        later increments and renders give the bits they would have given.  ``radius``: the reach of the fill, default
+        ``stride``; ``infill_kw``: the other parameters of infill.reconstruct.  Keep to one ``stride`` between resets.
+        Returns the [H, W, 3] image (``out`` when given); whole frames only."""
+        import torch
+        from . import infill
+        if self.params.tile_world != 1:
+            raise ValueError("render_sparse: the fill reads whole frames, not shards (tile_world must be 1)")
+        stride = int(stride)
+        h, w = self.pixel_shape
+        with torch.cuda.stream(stream):          # (the mask is filled where the increment reads it)
+            mask = infill.lattice_mask(h, w, stride, self._sparse_calls % (stride * stride))
+        noisy = self.render(samples, stream=stream, mask=mask)
+        self._sparse_calls += 1
+        g = self._guide_cache.get(self.params, feature_samples, infill.GUIDES, stream=stream)
+        return infill.reconstruct(noisy, g["normal"], g["position"], g["depth"], self.counts(stream), albedo=g["albedo"],
+                                  radius=stride if radius is None else radius, out=out, stream=stream, **infill_kw)[0]
 
     def state(self, stream=None):
         """The per-pixel records (vimg_hip_progressive_state) as CUDA tensors in ``pixel_shape``: a dict with
@@ -791,6 +825,7 @@ class Progressive:
         h = self._handle()
         with _Launch(stream):
             _check(self._lib.vimg_hip_progressive_reset(h))
+        self._sparse_calls = 0
 
     def close(self):
         if self._h:
