@@ -1,5 +1,5 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
-include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h and include/vimg_infill.h.
+include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h and include/vimg_wtemporal.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -432,6 +432,29 @@ INFILL_SYMBOLS = {
 }
 
 
+class WTemporalFrames(_Sized, C.Structure):
+    """VimgWTemporalFrames (include/vimg_wtemporal.h): VimgTemporalFrames and the per-pixel weight frame (float32)."""
+    _fields_ = TemporalFrames._fields_ + [("weight", C.c_void_p)]
+
+
+class WTemporalParams(_Sized, C.Structure):
+    """VimgWTemporalParams (include/vimg_wtemporal.h): VimgTemporalParams without current_weight;
+    vimg_wtemporal_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("max_history", f32), ("sigma_normal", f32), ("sigma_plane", f32)]
+
+
+WTEMPORAL_DEAD, WTEMPORAL_STARTED, WTEMPORAL_BLENDED, WTEMPORAL_CARRIED, WTEMPORAL_SHOWN = 0, 1, 2, 3, 4
+
+# the list of symbols include/vimg_wtemporal.h declares: libvimg_wtemporal.so, temporal accumulation with per-pixel
+# weights on libvimg_temporal's history (TEMPORAL_HISTORY_PER_PIXEL)
+WTEMPORAL_SYMBOLS = {
+    "vimg_wtemporal_defaults": (None, [C.POINTER(WTemporalParams)]),
+    "vimg_wtemporal_accumulate": (C.c_int, [C.POINTER(WTemporalFrames), C.c_void_p, Pf32, C.POINTER(WTemporalParams), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_wtemporal_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -451,6 +474,7 @@ _LIBRARIES = {
     "varfilter": ("libvimg_varfilter.so", (VARFILTER_SYMBOLS,), "varfilter", "; there is no CPU fallback for the filter", True),
     "moments": ("libvimg_moments.so", (MOMENTS_SYMBOLS,), "moments", "; there is no CPU fallback for temporal accumulation", True),
     "infill": ("libvimg_infill.so", (INFILL_SYMBOLS,), "infill", "; there is no CPU fallback for the reconstruction", True),
+    "wtemporal": ("libvimg_wtemporal.so", (WTEMPORAL_SYMBOLS,), "wtemporal", "; there is no CPU fallback for temporal accumulation", True),
 }
 _loaded = {}
 
@@ -507,3 +531,8 @@ def moments_lib():
 def infill_lib():
     """The reconstruction library for sparsely sampled frames (include/vimg_infill.h)."""
     return _load("infill")
+
+
+def wtemporal_lib():
+    """The temporal accumulation library with per-pixel weights (include/vimg_wtemporal.h)."""
+    return _load("wtemporal")

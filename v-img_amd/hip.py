@@ -298,7 +298,8 @@ class DeviceScene:
         return flt.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
                           stream=stream, **filter_kw)
 
-    def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, **temporal_kw):
+    def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
+                         fill_weight=None, **temporal_kw):
         """A preview that survives a moving camera (vimg_amd.temporal.TemporalPreview, include/vimg_temporal.h): its
         ``frame()`` renders ``samples`` more samples of the scene as it now stands and returns the [H, W, 3] picture -
         after set_camera or an edit blended with the last picture reprojected into the new camera, while nothing
@@ -307,10 +308,13 @@ class DeviceScene:
         ``scale_sigma_color`` (False: the filter's sigma_color as it is).  ``variance_guided``: the histories carry the
         moments of luminance (vimg_amd.moments, include/vimg_moments.h) and varfilter.atrous filters each pixel by the
         variance of its own accumulated mean; ``filter_kw`` are then its parameters, ``temporal_kw`` takes min_history
-        too and ``scale_sigma_color`` is refused.  Whole frames only."""
+        too and ``scale_sigma_color`` is refused.  ``sparse`` (a stride 2..4): a frame samples one pixel in sparse^2,
+        on a lattice that cycles, fills the others from the guides (vimg_amd.infill) and accumulates with per-pixel
+        weights (vimg_amd.wtemporal, include/vimg_wtemporal.h) - a filled pixel, worth ``fill_weight`` samples, takes
+        its reprojected history where it has one; not with ``variance_guided``.  Whole frames only."""
         from . import temporal
         return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
-                                        variance_guided=variance_guided, **temporal_kw)
+                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,

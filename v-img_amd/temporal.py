@@ -140,11 +140,22 @@ class TemporalPreview:
     varfilter.atrous's parameters, ``scale_sigma_color`` is refused, and ``history`` is a moments.History.  The
     accumulated colour, the history lengths and the accumulator are bit for bit what they are without it.
 
+    ``sparse`` (a stride 2..4): a frame samples ONE pixel in sparse^2 and the history supplies the
+    rest.  A frame() is then: the lattice infill.lattice_mask(H, W, sparse, phase) with phase = (frames since reset())
+    mod sparse^2 - a camera change does not restart it, so a moving camera still visits every cell - one
+    acc.render(samples, mask=lattice), infill.reconstruct with acc.counts(), the cached guides, the albedo and
+    radius = sparse, wtemporal.sparse_weights (a pixel with samples weighs its increments, a filled one
+    ``fill_weight``, default wtemporal.FILL_WEIGHT, a fallback or a hole 0) and wtemporal.accumulate
+    (include/vimg_wtemporal.h) in place of accumulate: a sampled pixel blends as ever, a filled pixel takes its
+    reprojected history where it has one, and the fill is used only where the history has nothing.  After sparse^2
+    frames of a standing camera the accumulator is bit for bit a Progressive after one render(samples).  ``history``
+    stays a History; ``variance_guided`` is refused with it (the moments history is not weighted per pixel).
+
     Limits: history from before a geometry or material edit is reprojected all the same and fades at 1 / max_history
     per frame (``reset()`` drops it); a thin lens is treated as its pinhole; see include/vimg_temporal.h."""
 
     def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
-                 variance_guided=False, **temporal_kw):
+                 variance_guided=False, sparse=None, fill_weight=None, **temporal_kw):
         import torch
         from . import filter as flt
         if params.tile_world != 1:
@@ -157,6 +168,19 @@ class TemporalPreview:
         if self.variance_guided and scale_sigma_color is not None:
             raise ValueError("temporal_preview: scale_sigma_color belongs to the fixed filter; the variance-guided filter has no "
                              "sigma_color")
+        self.sparse, self.fill_weight = None, None
+        if sparse is not None:
+            from . import infill, wtemporal
+            if self.variance_guided:
+                raise ValueError("temporal_preview: sparse does not go with variance_guided: the moments history has no "
+                                 "per-pixel weights")
+            infill.lattice_cell(sparse, 0)           # (refuses a stride outside 2..4)
+            self.sparse = int(sparse)
+            self.fill_weight = wtemporal.FILL_WEIGHT if fill_weight is None else float(fill_weight)
+            if not self.fill_weight >= 0.0:
+                raise ValueError(f"temporal_preview: fill_weight must be >= 0, not {fill_weight}")
+        elif fill_weight is not None:
+            raise ValueError("temporal_preview: fill_weight is the weight of a filled pixel: it needs sparse")
         unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"} - ({"min_history"} if variance_guided else set()))
         if unknown:
             raise TypeError(f"temporal_preview: unknown parameters {unknown}")
@@ -166,7 +190,10 @@ class TemporalPreview:
         self.acc = dev.progressive(params)
         w, h = dev.resolution
         self._buffers = [torch.empty((4 if self.variance_guided else 3, h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-        self._features = flt.GUIDES if denoise else ("normal", "position", "depth")
+        self._features = flt.GUIDES if denoise or self.sparse else ("normal", "position", "depth")
+        if self.sparse:
+            from . import infill
+            self._infill_workspace = torch.empty((infill.workspace_bytes(w, h),), dtype=torch.uint8, device="cuda")
         if self.variance_guided:
             from . import varfilter
             self._workspace = torch.empty((varfilter.workspace_bytes(w, h),), dtype=torch.uint8, device="cuda")
@@ -188,6 +215,7 @@ class TemporalPreview:
         self._guides.held = None
         self._k = 0
         self._frames = 0           # frames accumulated since the reset: the nominal history length of the next output
+        self.phase = None          # with ``sparse``: the lattice phase of the last frame()
 
     def frame(self, out=None, stream=None):
         """The preview of the scene as it now stands: ``samples`` more samples, accumulated; [H, W, 3] float32 CUDA
@@ -200,14 +228,23 @@ class TemporalPreview:
                 self._frozen, self._write = self.history, 1 - self._write
             self._generation, self._k = dev.generation, 0
         g = self._guides.get(acc.params, self.feature_samples, self._features, stream=stream)
-        mean = acc.render(self.samples, stream=stream)
+        if self.sparse:
+            mean = self._render_sparse(g, stream)
+        else:
+            mean = acc.render(self.samples, stream=stream)
         self._k += 1
         target = mean if out is None else out
         if self.variance_guided:
             return self._frame_variance_guided(mean, g, target, stream)
-        self.history = accumulate(mean, g["normal"], g["position"], g["depth"], history=self._frozen,
-                                  world_to_pixel=world_to_pixel(dev.camera), out=target, next_history=self._buffers[self._write],
-                                  stream=stream, current_weight=self._k, **self.temporal_kw)
+        if self.sparse:
+            from . import wtemporal
+            self.history = wtemporal.accumulate(mean, g["normal"], g["position"], g["depth"], self._weight, history=self._frozen,
+                                                world_to_pixel=world_to_pixel(dev.camera), out=target, out_code=False,
+                                                next_history=self._buffers[self._write], stream=stream, **self.temporal_kw)[0]
+        else:
+            self.history = accumulate(mean, g["normal"], g["position"], g["depth"], history=self._frozen,
+                                      world_to_pixel=world_to_pixel(dev.camera), out=target, next_history=self._buffers[self._write],
+                                      stream=stream, current_weight=self._k, **self.temporal_kw)
         self._frames += 1
         if self.denoise:
             n = min(float(self._frames), self._max_history) if self.scale_sigma_color else 1.0
@@ -215,6 +252,24 @@ class TemporalPreview:
             flt.atrous(target, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=target, workspace=self._workspace,
                        stream=stream, sigma_color=sigma_color, **self.filter_kw)
         return target
+
+    def _render_sparse(self, g, stream):
+        """The sparse increment of frame(): one masked render launch on the lattice of this frame's phase, the fill,
+        and the weight frame for wtemporal.accumulate (``self._weight``).  Returns the filled picture."""
+        import torch
+        from . import infill, wtemporal
+        acc = self.acc
+        h, w = acc.pixel_shape
+        self.phase = self._frames % (self.sparse * self.sparse)
+        with torch.cuda.stream(stream):          # (the mask is filled where the increment reads it)
+            lattice = infill.lattice_mask(h, w, self.sparse, self.phase)
+        noisy = acc.render(self.samples, stream=stream, mask=lattice)
+        state = acc.state(stream)
+        filled, code = infill.reconstruct(noisy, g["normal"], g["position"], g["depth"], state["count"], albedo=g["albedo"],
+                                          radius=self.sparse, out=noisy, workspace=self._infill_workspace, stream=stream)
+        with torch.cuda.stream(stream):
+            self._weight = wtemporal.sparse_weights(state["count"], code, state["batches"], fill_weight=self.fill_weight)
+        return filled
 
     def _frame_variance_guided(self, mean, g, target, stream):
         """The rest of frame() with ``variance_guided``: moments.accumulate in place of accumulate, handing the variance
