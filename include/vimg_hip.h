@@ -58,7 +58,7 @@ typedef struct VimgHipOptions {
   uint32_t struct_size;       /* sizeof(VimgHipOptions): lets the library accept older callers */
   int32_t scheduler;          /* AUTO (launch_policy.hip:make_launch): CU for every launch; LANE for frames wider than 65 535 pixels */
   int32_t waves_per_simd;     /* LANE: register budget, 2 or 3.  AUTO: 3 for scenes > 32 MiB else 2.  (CU is built for 4) */
-  int32_t lds_budget_kb;      /* LANE: LDS per workgroup for the top of the tree and the stacks, AUTO 40.  CU: LDS for the top of the tree alone, AUTO 4.5 */
+  int32_t lds_budget_kb;      /* LANE: LDS per workgroup for the top of the tree and the stacks, AUTO 40.  CU: LDS for the top of the tree alone, AUTO 4.5; a value no launch fits beside is VIMG_E_INVALID at the render */
   int32_t pool_slots;         /* CU: path slots per compute unit.  AUTO: what the CU's LDS holds, <= 1280 on trees in LDS, pixels / 2.7 on launches of 1 to 2.7 pools' worth of pixels, never more than pixels per CU + 8 */
   int32_t pool_segments;      /* CU: segments a pixel's samples are cut into.  AUTO: ~176 / pool generations of the launch, <= 64 and <= samples / 4; 1 on launches of ten generations or more */
   int32_t pool_refill;        /* CU: finished rays of a walking wave that trigger hand-over and refill.  AUTO 16; on trees in global memory 2 */
@@ -72,7 +72,7 @@ typedef struct VimgHipOptions {
   int32_t stage_wchunk;       /* accepted and ignored */
   int32_t stage_walk_quota;   /* accepted and ignored */
   int32_t pool4_rays;         /* accepted and ignored */
-  int32_t lds_stack;          /* CU: entries of a lane's traversal stack kept in LDS, the rest in global memory.  AUTO 32 */
+  int32_t lds_stack;          /* CU: entries of a lane's traversal stack kept in LDS, the rest in global memory.  AUTO 32 (fewer where the LDS asks for it); a value no launch fits is VIMG_E_INVALID at the render */
   int32_t pool_gbreak;        /* accepted and ignored */
   int32_t cu_waves;           /* CU: reserved; one 16-wave workgroup is a whole compute unit (12 waves at 168 registers measured slower) */
   int32_t cu_walkers;         /* CU: waves of the 16 that walk (the rest only shade).  AUTO: 9 on trees in LDS, 10 on trees in global memory, all 16 when every pixel of the launch owns a slot (tree in LDS) */

@@ -115,6 +115,29 @@ struct DScene {
   uint32_t background_emissive;
 };
 
+// The launch-constant shading tables a small scene's launch serves from LDS (render_cu_kernel.h), in staging order.
+// A row in LDS is the table's record, copied word for word; a VimgSphere (20 B) is padded to 32 B so that no row
+// straddles a 16-byte boundary it need not.
+enum : uint32_t {
+  TAB_PRIMS = 0, TAB_TRI_SHADE, TAB_SPHERES, TAB_MATERIAL_FLAGS, TAB_MESHES,   // hit records
+  TAB_MATERIALS, TAB_DMATERIALS,                                               // materials
+  TAB_COUNT
+};
+struct __attribute__((aligned(16))) LSphere {   // VimgSphere's members under their names, one 32-byte row
+  float center[3];
+  float radius;
+  uint32_t material;
+  uint32_t pad[3];
+};
+static_assert(sizeof(LSphere) == 32, "LSphere must be 32 bytes");
+// bytes of a table's row in LDS
+__host__ __device__ constexpr uint32_t tab_row_bytes(uint32_t t) {
+  return t == TAB_PRIMS ? uint32_t(sizeof(VimgPrim)) : t == TAB_TRI_SHADE ? uint32_t(sizeof(DTriShade)) :
+         t == TAB_SPHERES ? uint32_t(sizeof(LSphere)) : t == TAB_MATERIAL_FLAGS ? 4u :
+         t == TAB_MESHES ? uint32_t(sizeof(VimgMesh)) : t == TAB_MATERIALS ? uint32_t(sizeof(VimgMaterial)) :
+         uint32_t(sizeof(DMaterial));
+}
+
 enum : uint32_t {
   MATF_NEEDS_UV = 1u,      // colour texture is not constant (checker / image) or RG / normal map
   MATF_NEEDS_FRAME = 2u,   // Principled: reads HitInfo::n_frame
@@ -167,6 +190,12 @@ struct RenderArgs {
   // else (pixel, records, output offset) goes by the item found.  Other launches: nullptr, 0
   const VIMG_GLOBAL uint32_t* item_list;
   uint32_t item_count;
+  // CU scheduler: the launch-constant shading tables each workgroup copies to LDS behind its leaf records when the
+  // launch starts (render_cu_kernel.h: stage_tables).  lds_tables: the groups staged (plain_build.h: PF_TAB_*), each
+  // whole or not at all, 0 = none; tab_off / tab_rows: of every table of a staged group, its byte offset from the
+  // start of the workgroup's dynamic LDS (a multiple of 16) and its rows
+  uint32_t lds_tables;
+  uint32_t tab_off[TAB_COUNT], tab_rows[TAB_COUNT];
 };
 
 struct DeviceStats {

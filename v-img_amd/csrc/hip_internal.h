@@ -32,6 +32,7 @@ struct VimgDeviceScene {
   int waves_per_simd = 2;      // LANE register budget by policy (scene size)
   bool too_wide = false;       // resolution beyond the 16-bit pixel coordinates of the slot records
   bool force_general = false;  // VIMG_HIP_PLAIN=0 at upload: never a PLAIN build of render_cu_kernel (tests, A/B runs)
+  bool no_lds_tables = false;  // VIMG_HIP_LDS_TABLES=0 at upload: no launch stages the shading tables in LDS (tests, A/B runs)
   uint32_t num_cus = 0;
   uint32_t num_leaf_prims = 0;   // records in d.leaf_prims (= primitives of the scene)
   // scratch owned by the scene; the last four grow to what a launch asks for and never shrink
@@ -46,6 +47,7 @@ struct VimgDeviceScene {
   // geometry updates (vimg_hip_scene_update_geometry): what the upload knew of the tables and the tree
   uint64_t generation = 0;       // bumped by every change of the resident scene; accumulators remember theirs
   uint32_t num_vertices = 0, num_tris = 0, num_spheres = 0;
+  uint32_t num_meshes = 0;       // (with the counts above and the host copies below: the rows of the tables a launch may stage in LDS)
   std::vector<std::pair<uint32_t, uint32_t>> normal_rows;   // (first vertex, count) of the meshes with normals, merged
   uint32_t n_internal = 0;       // DNode records of the tree; the n_chain chain records follow them
   uint32_t n_chain = 0;
@@ -102,8 +104,10 @@ inline bool is_feature_integrator(uint32_t i) { return i >= VIMG_INTEGRATOR_ALBE
 inline uint32_t opt_or(int32_t v, uint32_t dflt) { return v == VIMG_OPT_AUTO ? dflt : static_cast<uint32_t>(v); }
 
 struct LaunchCfg {
+  const char* error;   // nullptr, or why no launch can be made of the scene's options (make_launch_cu): VIMG_E_INVALID
   RenderArgs args;
   uint32_t grid, lds_bytes;
+  uint32_t table_bytes;   // CU scheduler: the part of lds_bytes that holds the shading tables (the end of the layout)
   int sched;     // VIMG_SCHED_CU or VIMG_SCHED_LANE
   int wps;       // register-budget build (waves per SIMD of __launch_bounds__)
   bool deep;     // CU scheduler: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)
@@ -210,6 +214,8 @@ const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c);
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
 // whether the launch, as its arguments stand, runs a PLAIN build (plain_build.h)
 bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
+// takes the shading tables out of a launch that will not run a PLAIN build (call once its arguments are complete)
+void drop_unread_tables(const VimgDeviceScene* s, LaunchCfg& c, bool stats);
 
 }  // namespace vimg
 #pragma GCC visibility pop

@@ -74,10 +74,14 @@ void magic_div(uint32_t d, uint32_t* magic, uint32_t* shift) {
   *shift = l - 1u;
 }
 
+constexpr uint32_t CU_LDS_LIMIT = 160u * 1024u;   // LDS of a workgroup of 16 waves: the compute unit's
+
 // The launch of the CU-wide scheduler (render_cu_kernel.h): one workgroup of 16 waves per compute unit
 // (or two of 8), a pool of as many slots as the CU's LDS holds behind the top of the tree, the
 // walking waves' stacks and the rings - never more than the launch has pixels per workgroup.
-LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+// `node_budget`: bytes of LDS for the top of the tree; `stack_cap`: most stack entries of a lane kept in LDS
+// (make_launch_cu below decides both)
+LaunchCfg cu_launch_with(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy, uint32_t node_budget, uint32_t stack_cap) {
   LaunchCfg c{};
   const VimgHipOptions& o = s->opt;
   const uint64_t items = (sx >= 0) ? 1 : uint64_t(local_tiles(s, p)) * 64u;
@@ -86,7 +90,7 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   c.cu_waves = 16;   // (a build with two 8-wave workgroups per CU halves the pool a batch draws from; not built)
   const uint32_t nw = uint32_t(c.cu_waves);
   RenderArgs& a = c.args = base_args(s, p, sx, sy);
-  a.stack_lds = std::min(a.stack_entries, std::max(1u, opt_or(o.lds_stack, 32u)));
+  a.stack_lds = std::min(a.stack_entries, std::max(1u, stack_cap));
   // walking waves: five of eight by policy (config 2: the walk is 60 % of the wave cycles); when every
   // wave walks, every wave must be allowed to shade too
   a.cu_walkers = 0;   // (set below, once the tree's place is known)
@@ -99,8 +103,6 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   a.pool_classes = std::min(3u, std::max(1u, opt_or(o.pool_classes, 3u)));
   // LDS of the workgroup: the whole CU's (16 waves) or half of it, minus a margin
   const uint32_t share = (160u * 1024u) / (16u / nw) - 1024u;
-  uint32_t node_budget = 4608u;
-  if (o.lds_budget_kb != VIMG_OPT_AUTO) node_budget = uint32_t(std::max(1, o.lds_budget_kb)) * 1024u;
   a.lds_nodes = std::min(node_budget / 56u, s->d.num_nodes);
   const uint32_t node_bytes = (a.lds_nodes * 56u + 255u) & ~255u;
   // the build with the overflow path and the global node fetch serves both trees beyond the LDS
@@ -166,10 +168,43 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
   magic_div(slots, &a.cu_magic_v, &a.cu_shift_v);
   magic_div(2u * slots, &a.cu_magic_w, &a.cu_shift_w);
   c.lds_bytes = node_bytes + stack_bytes + cu_pool_bytes(slots, nw) + leaf_bytes;
+  // The launch-constant shading tables of a small scene behind the leaf records (render_cu_kernel.h: stage_tables),
+  // in the room the pool leaves: group by group (hit records, then materials), each whole or not at all, and
+  // never at the price of a slot - the pool is sized first.  Only for the builds that read them from there: a launch
+  // that, as far as the policy knows it here, a PLAIN build serves, by the groups those builds fold (enqueue_render
+  // takes the tables out again where statistics or an item list send the launch to another build: drop_unread_tables).
+  // VIMG_HIP_LDS_TABLES=0 at upload: none.
+  a.lds_tables = 0u;
+  c.table_bytes = 0u;
+  if (!s->no_lds_tables && plain_build_serves(plain_launch_of(true, s->textured, c.deep, c.cu_waves, false, s->force_general, a))) {
+    const uint32_t n_mat = uint32_t(s->materials.size());
+    uint32_t rows[TAB_COUNT];
+    rows[TAB_PRIMS] = s->num_leaf_prims, rows[TAB_TRI_SHADE] = s->num_tris, rows[TAB_SPHERES] = s->num_spheres;
+    rows[TAB_MATERIAL_FLAGS] = n_mat, rows[TAB_MESHES] = s->num_meshes;
+    rows[TAB_MATERIALS] = n_mat, rows[TAB_DMATERIALS] = n_mat;
+    static const struct { uint32_t bit, first, end; } groups[2] = {{PF_TAB_HIT, TAB_PRIMS, TAB_MATERIALS}, {PF_TAB_MAT, TAB_MATERIALS, TAB_COUNT}};
+    const uint64_t used = uint64_t(c.lds_bytes) + 64u;
+    uint64_t room = share > used ? share - used : 0u;
+    for (const auto& gr : groups) {
+      if (!(PLAIN_FOLD & gr.bit)) continue;
+      uint64_t bytes = 0;
+      for (uint32_t t = gr.first; t < gr.end; ++t) bytes += (uint64_t(rows[t]) * tab_row_bytes(t) + 15u) & ~uint64_t(15);
+      if (bytes > room) continue;
+      for (uint32_t t = gr.first; t < gr.end; ++t) {
+        a.tab_off[t] = c.lds_bytes, a.tab_rows[t] = rows[t];
+        c.lds_bytes += (rows[t] * tab_row_bytes(t) + 15u) & ~15u;
+      }
+      c.table_bytes += uint32_t(bytes);
+      room -= bytes;
+      a.lds_tables |= gr.bit;
+    }
+  }
   int per_cu = 0;
   // (asked of the build that will run, as far as the policy knows the launch: an item list or statistics come later
   // and take the general or the statistics build, of the same workgroup shape)
-  hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, launched_kernel_of(s, c, false), int(nw * 64u), c.lds_bytes);
+  // (not of a layout beyond the compute unit's LDS: make_launch_cu shrinks or refuses that one)
+  hipError_t oe = c.lds_bytes > CU_LDS_LIMIT ? hipErrorInvalidValue
+                                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, launched_kernel_of(s, c, false), int(nw * 64u), c.lds_bytes);
   if (oe != hipSuccess || per_cu < 1) per_cu = 1;
   per_cu = std::min<int>(per_cu, int(16u / nw));
   const uint64_t need_blocks = (items + slots - 1) / slots;
@@ -180,6 +215,35 @@ LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, in
     const uint32_t len = segments_for(s, p, items, uint64_t(c.grid) * slots, 176.0, 64.0, &a);
     a.cu_watchdog = static_cast<uint32_t>(std::min<uint64_t>((1000000000ull + 5000000ull * len) >> 20, 0x7fffffffull));   // 10 s + 50 ms per sample of a segment
   }
+  return c;
+}
+
+// The one place that fits a CU launch into the compute unit's LDS.  What the policy chooses itself gives way to what
+// the caller asked for: past the workgroup's share the node cache shrinks first (to the 1 KB the smallest option
+// gives), then the stack entries kept in LDS (to one), each only where its option was left to the policy.  A launch
+// that still cannot fit has its options to blame: c.error names the one, and nothing is launched (VIMG_E_INVALID).
+LaunchCfg make_launch_cu(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy) {
+  const VimgHipOptions& o = s->opt;
+  const bool own_nodes = o.lds_budget_kb == VIMG_OPT_AUTO, own_stack = o.lds_stack == VIMG_OPT_AUTO;
+  uint32_t node_budget = own_nodes ? 4608u : uint32_t(std::min(std::max(1, o.lds_budget_kb), 1 << 20)) * 1024u;
+  uint32_t stack_cap = opt_or(o.lds_stack, 32u);
+  const uint32_t limit = CU_LDS_LIMIT;
+  LaunchCfg c = cu_launch_with(s, p, sx, sy, node_budget, stack_cap);
+  if (c.lds_bytes > limit && own_nodes) c = cu_launch_with(s, p, sx, sy, node_budget = 1024u, stack_cap);
+  // (a smaller stack may turn the launch into one of the DEEP build, with one more walking wave: a few rounds)
+  for (int round = 0; round < 8 && c.lds_bytes > limit && own_stack && c.args.stack_lds > 1u; ++round) {
+    const uint32_t per_row = std::max(1u, c.args.cu_walkers) * 256u;
+    const uint32_t rows_over = (c.lds_bytes - limit + per_row - 1u) / per_row;
+    stack_cap = c.args.stack_lds > rows_over + 1u ? c.args.stack_lds - rows_over - 1u : 1u;
+    c = cu_launch_with(s, p, sx, sy, node_budget, stack_cap);
+  }
+  // (with both options left to the policy the smallest layout - 1 KB of nodes, one stack row per walking wave, eight
+  // slots, at most 4 KB of leaves - always fits: that case names no option)
+  if (c.lds_bytes > limit)
+    c.error = !own_nodes && !own_stack ? "options: lds_budget_kb and lds_stack together are beyond the compute unit's 160 KB of LDS"
+              : !own_nodes           ? "options: lds_budget_kb is beyond the compute unit's 160 KB of LDS"
+              : !own_stack           ? "options: lds_stack is beyond the compute unit's 160 KB of LDS"
+                                     : "the launch does not fit the compute unit's 160 KB of LDS";
   return c;
 }
 
@@ -202,7 +266,17 @@ const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
 // The one place that decides between a PLAIN build and the general one: the launch as its arguments stand
 // (enqueue_render asks after it has set the item list and the statistics flag) against plain_build.h's list.
 bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
-  return plain_build_serves(plain_launch_of(c.sched == VIMG_SCHED_CU, s->textured, c.deep, c.cu_waves, stats, s->force_general, c.args));
+  return plain_build_serves(plain_launch_of(c.sched == VIMG_SCHED_CU, s->textured, c.deep, c.cu_waves, stats, s->force_general, c.args)) &&
+         plain_tables_serve(c.args.lds_tables);
+}
+
+// A launch whose arguments, now complete, send it to the general or the statistics build reads no table from LDS:
+// their room goes back (they are the last thing in the layout) and RenderArgs::lds_tables says what is staged
+void drop_unread_tables(const VimgDeviceScene* s, LaunchCfg& c, bool stats) {
+  if (c.sched != VIMG_SCHED_CU || c.args.lds_tables == 0u || plain_launch_serves(s, c, stats)) return;
+  c.lds_bytes -= c.table_bytes;
+  c.table_bytes = 0u;
+  c.args.lds_tables = 0u;
 }
 
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
@@ -264,6 +338,7 @@ LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int s
   // (the upload admits the schedulers AUTO, LANE and CU only)
   if (s->too_wide || s->opt.scheduler == VIMG_SCHED_LANE) return make_launch_lane(s, p, sx, sy);   // slots pack pixel coordinates in 16 bits
   LaunchCfg c = make_launch_cu(s, p, sx, sy);
+  if (c.error) return c;
   cu_scratch(s, c);
   return c;
 }
@@ -283,6 +358,7 @@ const char* vimg_hip_launch_kernel(const VimgDeviceScene* s, const VimgRenderPar
   if (p->tile_world == 0 || p->tile_rank >= p->tile_world) return "";
   if (is_feature_integrator(p->integrator)) return s->textured ? "feature_kernel<true>" : "feature_kernel<false>";
   const LaunchCfg c = make_launch(s, p, -1, -1);
+  if (c.error) return "";
   // The build whole frames are timed on keeps the name it has always had: that is a PLAIN build now (plain_build.h).
   // Where the general build of the same scene class runs instead - another integrator, other options, the override
   // VIMG_HIP_PLAIN=0 - the name says so.  (Builds for textures or trees in global memory have no PLAIN counterpart.)

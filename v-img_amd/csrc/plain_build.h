@@ -24,12 +24,18 @@ enum : uint32_t {
   PF_ITEMS = 16u,       // no item list (masked progressive increments bring one)
   PF_FLEX = 32u,        // cu_flex at the policy's default: walking waves may shade (bit 1), no wave priorities (bits 2 and 4),
                         // split batches on (bit 16 clear); bit 32 (early rays) is the EARLY template parameter already
+  // The launch-constant shading tables, read from the workgroup's copies in LDS (render_kernels.h: LdsTables, tb_*),
+  // one bit per group; a group is staged whole or not at all (launch_policy.hip), as the leaf records are
+  PF_TAB_HIT = 64u,     // hit records: prims, tri_shade, spheres, material_flags, meshes
+  PF_TAB_MAT = 128u,    // materials: materials, dmaterials.  NOT folded by default (it costs the PLAIN
+                        // kernels their 128th register; a sweep bit, like every other, through -DVIMG_PLAIN_FOLD)
+  PF_TABLES = PF_TAB_HIT | PF_TAB_MAT,   // (the emitter tables stay in global memory: DESIGN.md 4.4)
 };
 // What the PLAIN builds fold (DESIGN.md 4.4 has the times of the candidates)
 #ifdef VIMG_PLAIN_FOLD   // (sweeps: -DVIMG_PLAIN_FOLD=<mask> on the units that include this header)
 constexpr uint32_t PLAIN_FOLD = VIMG_PLAIN_FOLD;
 #else
-constexpr uint32_t PLAIN_FOLD = PF_INTEGRATOR | PF_CLASSES | PF_LEAF_LDS | PF_SINGLE | PF_ITEMS | PF_FLEX;
+constexpr uint32_t PLAIN_FOLD = PF_INTEGRATOR | PF_CLASSES | PF_LEAF_LDS | PF_SINGLE | PF_ITEMS | PF_FLEX | PF_TAB_HIT;
 #endif
 
 // what the predicate needs to know of a launch (plain_launch_of below fills it)
@@ -56,6 +62,13 @@ constexpr bool plain_build_serves(const PlainLaunch& l, uint32_t fold = PLAIN_FO
   if ((fold & PF_ITEMS) && l.has_item_list) return false;
   if ((fold & PF_FLEX) && (l.cu_flex & ~32u) != PLAIN_FLEX_DEFAULT) return false;
   return true;
+}
+
+// The table groups are one more folded constant, with a predicate of their own beside the one above: `staged` is
+// the launch's RenderArgs::lds_tables (the groups the policy found room for).  A build that reads a group from LDS
+// serves only launches that staged it; a launch whose tables do not fit runs the general build.
+constexpr bool plain_tables_serve(uint32_t staged, uint32_t fold = PLAIN_FOLD) {
+  return (staged & fold & PF_TABLES) == (fold & PF_TABLES);
 }
 
 // The description of a launch from what the policy knows of it: the kernel family and the build class, whether

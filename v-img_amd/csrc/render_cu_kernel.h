@@ -164,6 +164,35 @@ template <uint32_t PLAIN> VD bool opt_has_items(const RenderArgs& A) {
 template <uint32_t PLAIN> VD uint32_t opt_flex(const RenderArgs& A) {   // (without the early bit: EARLY is a parameter of its own)
   if constexpr (PLAIN & PF_FLEX) return PLAIN_FLEX_DEFAULT; else return A.cu_flex;
 }
+// (the table groups PF_TAB_* are folded through the type of the scene the vertex stages read: LdsTables<PLAIN & PF_TABLES>)
+
+// The workgroup's copies of the launch-constant shading tables (device_scene.h: TAB_*), made once when the launch
+// starts, from the resident tables as they stand then: an update of the scene between launches needs nothing more.
+// Rows are copied word for word (a sphere's five words into a row of eight).
+template <class T>
+VD void stage_rows(VIMG_LDS unsigned char* lds_raw, const RenderArgs& A, uint32_t t, gptr<T> src) {
+  constexpr uint32_t src_w = uint32_t(sizeof(T)) / 4u;
+  const uint32_t dst_w = tab_row_bytes(t) / 4u, words = A.tab_rows[t] * src_w;
+  VIMG_LDS uint32_t* dst = reinterpret_cast<VIMG_LDS uint32_t*>(lds_raw + A.tab_off[t]);
+  gptr<uint32_t> w = reinterpret_cast<gptr<uint32_t>>(src);
+  for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) {
+    const uint32_t r = i / src_w;
+    dst[r * dst_w + (i - r * src_w)] = w[i];
+  }
+}
+VD void stage_tables(const DScene& g, const RenderArgs& A, VIMG_LDS unsigned char* lds_raw) {
+  if (A.lds_tables & PF_TAB_HIT) {
+    stage_rows(lds_raw, A, TAB_PRIMS, g.prims);
+    stage_rows(lds_raw, A, TAB_TRI_SHADE, g.tri_shade);
+    stage_rows(lds_raw, A, TAB_SPHERES, g.spheres);
+    stage_rows(lds_raw, A, TAB_MATERIAL_FLAGS, g.material_flags);
+    stage_rows(lds_raw, A, TAB_MESHES, g.meshes);
+  }
+  if (A.lds_tables & PF_TAB_MAT) {
+    stage_rows(lds_raw, A, TAB_MATERIALS, g.materials);
+    stage_rows(lds_raw, A, TAB_DMATERIALS, g.dmaterials);
+  }
+}
 
 
 // Kernel arguments: ONE struct by value, read through a pointer to the kernel-argument segment that
@@ -223,6 +252,8 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] VIMG_LDS CuWaveRec* wrec = reinterpret_cast<VIMG_LDS CuWaveRec*>(G + 1) + wave;                      \
   [[maybe_unused]] VIMG_LDS v4f* lds_leaf = reinterpret_cast<VIMG_LDS v4f*>(reinterpret_cast<VIMG_LDS CuWaveRec*>(G + 1) + NW); \
   [[maybe_unused]] VIMG_LDS uint32_t* recw = reinterpret_cast<VIMG_LDS uint32_t*>(recs);                                \
+  /* the scene as the vertex stages read its shading tables: from LDS for the groups this build folds (PF_TAB_*) */     \
+  [[maybe_unused]] const auto& gt = table_view<(PLAIN & PF_TABLES)>(g, A, (const VIMG_LDS unsigned char*)lds_raw);      \
   [[maybe_unused]] auto rd = [&](uint32_t r, uint32_t slot) -> v4u { return recs[r * P + slot]; };                      \
   [[maybe_unused]] auto wr = [&](uint32_t r, uint32_t slot, v4u v) { recs[r * P + slot] = v; };                         \
   [[maybe_unused]] auto flag_word = [&](uint32_t slot) -> VIMG_LDS uint32_t* { return recw + (CR_DIR * P + slot) * 4u + 3u; }; \
@@ -448,7 +479,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         hr.prim = r_hx.x;
         hr.kind = (flags & CF_KIND_SPHERE) ? 1u : 0u;
         TravRay tr{ray_o, ray_d, 0.0001f, uf(r_hx.y)};
-        make_hit_info<TEX>(g, hr, tr, hit);
+        make_hit_info<TEX>(gt, hr, tr, hit);
       }
       if (material_mode) {
         // material_integrator (mat_integrator.cpp:16-23,79-81)
@@ -474,7 +505,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
           result = background_emit<TEX>(g, ray_d, cone);
           finish = true;
         } else {
-          gptr<VimgMaterial> m = g.materials + hit.mat;
+          const auto m = tb_materials(gt) + hit.mat;
           if (m->type == VIMG_MAT_DIFFUSE_LIGHT) {
             result = mat_emitted(m, ray_d, hit.ns);
             finish = true;
@@ -486,11 +517,11 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
       } else {
         // the ray sampled from the BSDF at the previous vertex (mis_integrator.cpp:120-186)
         if (hit_any) {
-          gptr<VimgMaterial> m = g.materials + hit.mat;
+          const auto m = tb_materials(gt) + hit.mat;
           if (m->type == VIMG_MAT_DIFFUSE_LIGHT) {
             const f3 le = mat_emitted(m, ray_d, hit.ns);
             if (prev_pdf != 0) {
-              float light_pdf = surf_pdf(g, hit.prim, ray_o, hit.p, ray_d) / g.num_lights;
+              float light_pdf = surf_pdf(gt, hit.prim, ray_o, hit.p, ray_d) / g.num_lights;
               float Gt = geometric_term(ray_o, hit.p, hit.ng);
               float mis_weight = balance_heuristic(prev_pdf * Gt, light_pdf);
               result = result + throughput * mis_weight * le;
@@ -552,9 +583,9 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
   if constexpr (!finisher_batch) {
     if (material_mode && at_vertex) {
       // mat_integrator.cpp:24-78: BSDF sampling only, throughput *= emitted + eval/pdf
-      gptr<VimgMaterial> m = g.materials + hit.mat;
+      const auto m = tb_materials(gt) + hit.mat;
       const f3 emitted_col = mat_emitted(m, ray_d, hit.ns);
-      Scatter sc = sample_mat<TEX>(g, hit, ray_d, rng, non_specular_bounce);
+      Scatter sc = sample_mat<TEX>(gt, hit, ray_d, rng, non_specular_bounce);
       if (!sc.valid) {
         result = throughput * emitted_col;
         finish = true;
@@ -578,7 +609,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         } else if (type == VIMG_MAT_PRINCIPLED) {
           f3 f;
           float pdf;
-          principled_eval_pdf<TEX>(g, m, ray_d, sc.wo, hit, cone, non_specular_bounce, f, pdf);
+          principled_eval_pdf<TEX>(gt, m, ray_d, sc.wo, hit, cone, non_specular_bounce, f, pdf);
           fdiv = f / pdf;
         }
         throughput = throughput * (emitted_col + fdiv);
@@ -634,20 +665,20 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
     Scatter sc = no_scatter();
     Rng rng_l{0};   // the stream where the light sample draws
     if (at_vertex) {
-      mat_type = MT >= 0 ? uint32_t(MT) : g.materials[hit.mat].type;
+      mat_type = MT >= 0 ? uint32_t(MT) : tb_materials(gt)[hit.mat].type;
       if constexpr (TEX) {
         hit_dist = length(ray_o - hit.p);
         surface_spread_angle = spread_angle_from_curvature(hit.curvature, cone.cone_width, ray_d, hit.ns);
       }
       reg_before = non_specular_bounce;
       if constexpr (LIGHT_FIRST) {   // (not a delta material: the light is always sampled)
-        lights_sample<TEX>(g, hit.p, rng, light_col, li);
+        lights_sample<TEX>(gt, hit.p, rng, light_col, li);
         nee = (li.pdf != 0.f);
       } else {
         rng_l = rng;
         if (mat_type != VIMG_MAT_DIELECTRIC) pcg_skip6(rng);   // (!is_delta: the light sample's six draws)
       }
-      sc = sample_mat<TEX, MT>(g, hit, ray_d, rng, reg_before);
+      sc = sample_mat<TEX, MT>(gt, hit, ray_d, rng, reg_before);
       if constexpr (TEX) nee_cone = propagate_reflect_cone(cone, surface_spread_angle * 2.f, hit_dist);
       if (sc.valid) {
         if (!sc.is_specular) non_specular_bounce = true;
@@ -676,7 +707,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
     pv_lap(3);
     if constexpr (!LIGHT_FIRST) {
       if (at_vertex && mat_type != VIMG_MAT_DIELECTRIC) {
-        lights_sample<TEX>(g, hit.p, rng_l, light_col, li);
+        lights_sample<TEX>(gt, hit.p, rng_l, light_col, li);
         nee = (li.pdf != 0.f);
       }
     }
@@ -707,9 +738,9 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
         // not refract - `cone` itself for the sampled direction): once for both.  The two double quotients stand
         // side by side so that their chains overlap.
         if (nee || sc.valid) {
-          gptr<DMaterial> dm = g.dmaterials + hit.mat;
+          const auto dm = tb_dmaterials(gt) + hit.mat;
           const f3 col = (dm->bits & DMAT_COLOUR) ? load3(dm->base)
-                                                  : col_at_ray_hit<TEX>(g, g.materials[hit.mat].tex, ray_d, nee_cone, hit);
+                                                  : col_at_ray_hit<TEX>(g, tb_materials(gt)[hit.mat].tex, ray_d, nee_cone, hit);
           const float cos_l = sel_max(0.0f, dot(li.wi, hit.ns)), cos_s = sel_max(0.0f, dot(sc.wo, hit.ns));
           const float dp_l = static_cast<float>(cos_l / kPi), dp_s = static_cast<float>(cos_s / kPi);
           if (nee) f_l = col * dp_l, pdf_l = dp_l;
@@ -727,7 +758,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
             const f3 wo{uf(w4.x), uf(w4.y), uf(w4.z)};
             const RayCone c = second ? cone : nee_cone;
             const bool reg = second ? non_specular_bounce : reg_before;
-            eval_pdf_pair<TEX, MT>(g, hit, ray_d, wo, c, reg, f, pdf);
+            eval_pdf_pair<TEX, MT>(gt, hit, ray_d, wo, c, reg, f, pdf);
           }
           if (second) f_s = f, pdf_s = pdf;
           else f_l = f, pdf_l = pdf;
@@ -1252,6 +1283,7 @@ render_cu_kernel(const CuKArgs ka) {
     for (uint32_t i = lane; i < sizeof(CuWaveRec) / 4u; i += 64u) reinterpret_cast<VIMG_LDS uint32_t*>(wrec)[i] = 0u;
     for (uint32_t i = threadIdx.x; i < A.lds_leaf * 3u; i += blockDim.x)
       lds_leaf[i] = reinterpret_cast<gptr<v4f>>(g.leaf_prims)[i];
+    if constexpr ((PLAIN & PF_TABLES) != 0u) stage_tables(g, A, (VIMG_LDS unsigned char*)lds_raw);   // (the builds that read them there)
     // every slot starts "fresh" in the finisher queue: it needs a pixel
     for (uint32_t s = threadIdx.x; s < P; s += blockDim.x) {
       recw[(CR_DIR * P + s) * 4u + 3u] = CF_FRESH;

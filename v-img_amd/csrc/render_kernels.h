@@ -18,6 +18,7 @@
 #include "device_math.h"
 #include "device_scene.h"
 #include "material_terms.h"
+#include "plain_build.h"
 
 namespace vimg {
 
@@ -626,29 +627,78 @@ VD bool traverse(const DScene& g, const Lds& L, TravRay& ray, HitRec& rec, Count
   return found;
 }
 
+// ================================================================================ where the shading tables are read
+// The launch-constant shading tables (device_scene.h: TAB_*) have two sources: the scene's arrays in global memory,
+// and - in a launch of render_cu_kernel that staged them - the workgroup's copies in LDS.  The hit record, the
+// material and the emitter functions below take the scene as `const S& g` and read every such table through its
+// accessor tb_<table>(g): S = DScene gives the global array, S = LdsTables<GROUPS> the LDS copy for the tables of the
+// groups in GROUPS (plain_build.h: PF_TAB_*) and the global array for the others.  One text, the same loads in the
+// same order, the same arithmetic: only the address space differs.  Everything else of the scene (vertex normals,
+// uvs, textures, the emitter records, the CDF pool, the background) is read through scn(g), the DScene itself.
+template <typename T>
+using lptr = const VIMG_LDS T*;
+template <uint32_t GROUPS>
+struct LdsTables {
+  const DScene& d;
+  const RenderArgs& A;                  // tab_off: where each staged table starts
+  const VIMG_LDS unsigned char* base;   // start of the workgroup's dynamic LDS
+  VD operator const DScene&() const { return d; }
+};
+// the scene as a build that folds GROUPS reads its tables: the DScene itself when it folds none
+template <uint32_t GROUPS>
+VD decltype(auto) table_view(const DScene& g, const RenderArgs& A, const VIMG_LDS unsigned char* lds_raw) {
+  if constexpr (GROUPS == 0u) return (g); else return LdsTables<GROUPS>{g, A, lds_raw};
+}
+VD const DScene& scn(const DScene& g) { return g; }
+template <uint32_t GROUPS>
+VD const DScene& scn(const LdsTables<GROUPS>& g) { return g.d; }
+#define VIMG_TABLE(name, GT, LT, group, slot)                                                 \
+  VD gptr<GT> tb_##name(const DScene& g) { return g.name; }                                   \
+  template <uint32_t GROUPS>                                                                  \
+  VD auto tb_##name(const LdsTables<GROUPS>& g) {                                             \
+    if constexpr ((GROUPS & (group)) != 0u)                                                   \
+      return reinterpret_cast<lptr<LT>>(g.base + g.A.tab_off[slot]);                          \
+    else                                                                                      \
+      return g.d.name;                                                                        \
+  }
+VIMG_TABLE(prims, VimgPrim, VimgPrim, PF_TAB_HIT, TAB_PRIMS)
+VIMG_TABLE(tri_shade, DTriShade, DTriShade, PF_TAB_HIT, TAB_TRI_SHADE)
+VIMG_TABLE(spheres, VimgSphere, LSphere, PF_TAB_HIT, TAB_SPHERES)
+VIMG_TABLE(material_flags, uint32_t, uint32_t, PF_TAB_HIT, TAB_MATERIAL_FLAGS)
+VIMG_TABLE(meshes, VimgMesh, VimgMesh, PF_TAB_HIT, TAB_MESHES)
+VIMG_TABLE(materials, VimgMaterial, VimgMaterial, PF_TAB_MAT, TAB_MATERIALS)
+VIMG_TABLE(dmaterials, DMaterial, DMaterial, PF_TAB_MAT, TAB_DMATERIALS)
+#undef VIMG_TABLE
+VD f3 load3(lptr<float> p) { return f3{p[0], p[1], p[2]}; }
+VD VimgPrim load_prim(lptr<VimgPrim> p) {
+  v2u v = *reinterpret_cast<const VIMG_LDS v2u*>(p);
+  return VimgPrim{v.x, v.y};
+}
+
 // ================================================================================ hit records
-VD f2 load_uv(const DScene& g, gptr<VimgMesh> m, uint32_t set, uint32_t vtx) {
+template <class MeshPtr>
+VD f2 load_uv(const DScene& g, MeshPtr m, uint32_t set, uint32_t vtx) {
   gptr<float> p = g.uvs + 2 * (size_t(m->uv_offset[set]) + (vtx - m->first_vertex));
   return f2{p[0], p[1]};
 }
 // Triangle::hit_info: reference src/geometry/triangle.cpp:13-153
-template <bool TEX>
-VD void tri_hit_info(const DScene& g, uint32_t tri, const HitRec& rec, uint32_t prim_id, Hit& h) {
-  gptr<DTriShade> ts = g.tri_shade + tri;
+template <bool TEX, class S>
+VD void tri_hit_info(const S& g, uint32_t tri, const HitRec& rec, uint32_t prim_id, Hit& h) {
+  const auto ts = tb_tri_shade(g) + tri;
   const f3 p0{ts->p[0], ts->p[1], ts->p[2]}, p1{ts->p[3], ts->p[4], ts->p[5]},
       p2{ts->p[6], ts->p[7], ts->p[8]};
-  gptr<VimgMesh> mesh = g.meshes + ts->mesh;
+  const auto mesh = tb_meshes(g) + ts->mesh;
   const uint32_t i0 = ts->i0, i1 = ts->i1, i2 = ts->i2;
   const uint32_t mat = mesh->material;
-  const uint32_t mflags = g.material_flags[mat];
+  const uint32_t mflags = tb_material_flags(g)[mat];
   f3 edge1 = p1 - p0, edge2 = p2 - p0;
   float u = rec.e0 * rec.inv_det, v = rec.e1 * rec.inv_det, w = rec.e2 * rec.inv_det;
   const f3 tri_normal{ts->n[0], ts->n[1], ts->n[2]};   // normalize(cross(edge1, edge2)), baked
   f3 n0 = tri_normal, n1 = tri_normal, n2 = tri_normal, shading_normal = tri_normal;
   if (mesh->has_normals) {
-    n0 = load3(g.normals + 3 * size_t(i0));
-    n1 = load3(g.normals + 3 * size_t(i1));
-    n2 = load3(g.normals + 3 * size_t(i2));
+    n0 = load3(scn(g).normals + 3 * size_t(i0));
+    n1 = load3(scn(g).normals + 3 * size_t(i1));
+    n2 = load3(scn(g).normals + 3 * size_t(i2));
     shading_normal = normalize(u * n0 + v * n1 + w * n2);
   }
   h.p = u * p0 + v * p1 + w * p2;
@@ -695,7 +745,7 @@ VD void tri_hit_info(const DScene& g, uint32_t tri, const HitRec& rec, uint32_t 
     get_axis(shading_normal, dpdu, dpdv);
   }
   if constexpr (TEX) {
-    const int nmap = g.materials[mat].normal_map;
+    const int nmap = tb_materials(g)[mat].normal_map;
     if (nmap >= 0) {
       f2 n_uv{u, v};
       const uint32_t nset = mesh->normal_tex_uv;
@@ -704,7 +754,7 @@ VD void tri_hit_info(const DScene& g, uint32_t tri, const HitRec& rec, uint32_t 
            q2 = load_uv(g, mesh, nset, i2);
         n_uv = u * q0 + v * q1 + w * q2;
       }
-      f3 n_tangent_space = normalize(col_at_uv_mipmap(g, g.textures + nmap, 0, n_uv));
+      f3 n_tangent_space = normalize(col_at_uv_mipmap(g, scn(g).textures + nmap, 0, n_uv));
       Onb onb_n_map = init_onb(shading_normal);
       f3 local_space_normal = xform_with_onb(onb_n_map, n_tangent_space);
       float ulen = length(dpdu), vlen = length(dpdv);
@@ -729,14 +779,14 @@ VD void tri_hit_info(const DScene& g, uint32_t tri, const HitRec& rec, uint32_t 
   }
 }
 // Sphere::hit_info: reference src/geometry/sphere.cpp:12-45
-template <bool TEX>
-VD void sphere_hit_info(const DScene& g, uint32_t sphere, const TravRay& r, uint32_t prim_id,
+template <bool TEX, class S>
+VD void sphere_hit_info(const S& g, uint32_t sphere, const TravRay& r, uint32_t prim_id,
                         Hit& h) {
-  gptr<VimgSphere> sp = g.spheres + sphere;
+  const auto sp = tb_spheres(g) + sphere;
   const f3 center = load3(sp->center);
   const float radius = sp->radius;
   const uint32_t mat = sp->material;
-  const uint32_t mflags = g.material_flags[mat];
+  const uint32_t mflags = tb_material_flags(g)[mat];
   h.p = r.o + r.d * r.max_t;
   const f3 normal = normalize(h.p - center);
   h.ns = normal;
@@ -765,9 +815,9 @@ VD void sphere_hit_info(const DScene& g, uint32_t sphere, const TravRay& r, uint
     h.tex_area = 0.000001f;
   }
 }
-template <bool TEX>
-VD void make_hit_info(const DScene& g, const HitRec& rec, const TravRay& ray, Hit& h) {
-  const VimgPrim p = load_prim(g.prims + rec.prim);
+template <bool TEX, class S>
+VD void make_hit_info(const S& g, const HitRec& rec, const TravRay& ray, Hit& h) {
+  const VimgPrim p = load_prim(tb_prims(g) + rec.prim);
   if (p.type == VIMG_PRIM_TRIANGLE)
     tri_hit_info<TEX>(g, p.index, rec, rec.prim, h);
   else
@@ -777,7 +827,8 @@ VD void make_hit_info(const DScene& g, const HitRec& rec, const TravRay& ray, Hi
 // ================================================================================ materials
 // emitted: base 0 (include/material/material.h:63-66), DiffuseLight one-sided
 // (include/material/diffuse_light.h:30-38)
-VD f3 mat_emitted(gptr<VimgMaterial> m, f3 ray_dir, f3 shading_normal) {
+template <class MatPtr>   // (a row of tb_materials)
+VD f3 mat_emitted(MatPtr m, f3 ray_dir, f3 shading_normal) {
   if (m->type != VIMG_MAT_DIFFUSE_LIGHT) return f3{0.f, 0.f, 0.f};
   return (dot(shading_normal, ray_dir) < 0) ? load3(m->emit) : f3{0.f, 0.f, 0.f};
 }
@@ -793,7 +844,8 @@ VD f3 refract_dir(f3 wi, f3 n, float i_over_o, float cos_i, float sin2_t) {
   float normal_mul = (i_over_o * cos_i) - sqrt_f(1.f - sin2_t);
   return (i_over_o * wi) + (normal_mul * n);
 }
-VD Scatter dielectric_sample(gptr<VimgMaterial> m, const Hit& hit, f3 wi, Rng& rng) {
+template <class MatPtr>
+VD Scatter dielectric_sample(MatPtr m, const Hit& hit, f3 wi, Rng& rng) {
   const float ior = m->ior;
   f3 wo;
   float eta;
@@ -911,12 +963,14 @@ VD float fd_term(f3 n, f3 w, float fd90) {   // FD, disney_diffuse.h:9-11
 // where they used to compute it, for a material whose validity bit is set, and run material_terms.h's statements
 // otherwise; the untextured builds never read a metallic-roughness map (principled_prologue), so their scalar
 // group always holds.
-VD DMatCoat load_coat(gptr<DMatCoat> p) {
+template <class CoatPtr>
+VD DMatCoat load_coat(CoatPtr p) {
   DMatCoat c;
   c.alpha_g = p->alpha_g, c.ag2 = p->ag2, c.ag2m1 = p->ag2m1, c.pad = 0.f, c.ag2m1_d = p->ag2m1_d, c.pi_log = p->pi_log;
   return c;
 }
-VD DMatWeights load_weights(gptr<DMatWeights> p) {
+template <class WeightsPtr>
+VD DMatWeights load_weights(WeightsPtr p) {
   DMatWeights w;
   w.choose_diff = p->choose_diff, w.choose_clearcoat = p->choose_clearcoat, w.choose_metal = p->choose_metal;
   w.choose_glass = p->choose_glass, w.sum2 = p->sum2, w.sum3 = p->sum3, w.sum4 = p->sum4;
@@ -927,9 +981,10 @@ VD DMatWeights load_weights(gptr<DMatWeights> p) {
 // A material's record, addressed anew at every site that loads a group: the empty statement keeps the compiler from
 // merging the sites' loads into one at the top of the function, where the loaded terms would stay live across the
 // whole evaluation in a kernel that sits at its register budget.
-VD gptr<DMaterial> dmat_at(const DScene& g, uint32_t mat) {
+template <class S>
+VD auto dmat_at(const S& g, uint32_t mat) {
   asm volatile("" : "+v"(mat));
-  return g.dmaterials + mat;
+  return tb_dmaterials(g) + mat;
 }
 template <bool TEX>
 VD bool dmat_scalars(uint32_t bits) {
@@ -942,8 +997,8 @@ struct PrincipledCommon {
   float metallic, roughness;
 };
 // shared prologue of Principled::eval_pdf / sample_mat: principled.h:103-119, principled.cpp:5-21
-template <bool TEX>
-VD PrincipledCommon principled_prologue(const DScene& g, gptr<VimgMaterial> m, f3 wi, const Hit& hit) {
+template <bool TEX, class S, class MatPtr>
+VD PrincipledCommon principled_prologue(const S& g, MatPtr m, f3 wi, const Hit& hit) {
   PrincipledCommon p;
   p.dir_in = -wi;
   p.frame = Onb{hit.tu, hit.tv, hit.ns};
@@ -966,8 +1021,8 @@ VD PrincipledCommon principled_prologue(const DScene& g, gptr<VimgMaterial> m, f
 // helpers eval_pdf_disney_{rough_glass,diffuse,clearcoat,metal} and eval_disney_sheen
 // (disney_glass.h:188-234, disney_diffuse.h:73-104, disney_clearcoat.h:107-139,
 // disney_metal.h:122-152, disney_sheen.h:10-27)
-template <bool TEX>
-VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
+template <bool TEX, class S, class MatPtr>
+VD void principled_eval_pdf(const S& g, MatPtr m, f3 wi,
                                                  f3 wo, const Hit& hit, RayCone cone,
                                                  bool regularize, f3& f_out, float& pdf_out) {
   const PrincipledCommon pc = principled_prologue<TEX>(g, m, wi, hit);
@@ -980,7 +1035,7 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
   f3 base_color;
   bool scalars, colour;
   {
-    gptr<DMaterial> dm = dmat_at(g, mat);
+    const auto dm = dmat_at(g, mat);
     const uint32_t bits = dm->bits;
     scalars = dmat_scalars<TEX>(bits), colour = (bits & DMAT_COLOUR) != 0;
     base_color = colour ? load3(dm->base) : col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit);
@@ -993,7 +1048,7 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
   // alphax * alphax, alphay * alphay and kPi * alphax * alphay, where a lobe's D is formed
   auto alpha_products = [&](float& ax2, float& ay2, double& pi_axay) {
     if (scalars) {
-      gptr<DMatAlpha> a = dmat_at(g, mat)->alpha + reg;
+      const auto a = dmat_at(g, mat)->alpha + reg;
       ax2 = a->ax2, ay2 = a->ay2, pi_axay = a->pi_axay;
     } else {
       ax2 = alphax * alphax, ay2 = alphay * alphay, pi_axay = kPi * alphax * alphay;
@@ -1124,9 +1179,9 @@ VD void principled_eval_pdf(const DScene& g, gptr<VimgMaterial> m, f3 wi,
 }
 
 // MT: material type known at compile time (a batch of one material class), -1 = read it
-template <bool TEX, int MT = -1>
-VD Scatter sample_mat(const DScene& g, const Hit& hit, f3 wi, Rng& rng, bool regularize) {
-  gptr<VimgMaterial> m = g.materials + hit.mat;
+template <bool TEX, int MT = -1, class S>
+VD Scatter sample_mat(const S& g, const Hit& hit, f3 wi, Rng& rng, bool regularize) {
+  const auto m = tb_materials(g) + hit.mat;
   const uint32_t type = MT >= 0 ? uint32_t(MT) : m->type;
   const f3 dir_in = -wi;
   uint32_t lobe = LOBE_NONE;
@@ -1147,7 +1202,7 @@ VD Scatter sample_mat(const DScene& g, const Hit& hit, f3 wi, Rng& rng, bool reg
     const float metallic = pc.metallic;
     float roughness = pc.roughness;
     const float ng_in = dot(hit.ng, dir_in);
-    gptr<DMaterial> dm = g.dmaterials + hit.mat;
+    const auto dm = tb_dmaterials(g) + hit.mat;
     const bool scalars = dmat_scalars<TEX>(dm->bits);
     const int reg = regularize ? 1 : 0;
     if (ng_in < 0) {
@@ -1271,16 +1326,16 @@ VD Scatter sample_mat(const DScene& g, const Hit& hit, f3 wi, Rng& rng, bool reg
 }
 // Material::eval_pdf_pair dispatch; the base class returns (0, 1) (material.h:56-60), which is
 // what Dielectric and DiffuseLight inherit
-template <bool TEX, int MT = -1>
-VD void eval_pdf_pair(const DScene& g, const Hit& hit, f3 wi, f3 wo, RayCone cone, bool regularize,
+template <bool TEX, int MT = -1, class S>
+VD void eval_pdf_pair(const S& g, const Hit& hit, f3 wi, f3 wo, RayCone cone, bool regularize,
                       f3& f, float& pdf) {
-  gptr<VimgMaterial> m = g.materials + hit.mat;
+  const auto m = tb_materials(g) + hit.mat;
   const uint32_t type = MT >= 0 ? uint32_t(MT) : m->type;
   if (type == VIMG_MAT_LAMBERTIAN) {
     // Lambertian::eval_pdf_pair, reference src/material/lambertian.cpp:47-54
     // (render_cu_kernel.h's Lambertian batches restate these lines for both directions of a vertex at once)
     float dot_product = static_cast<float>(sel_max(0.0f, dot(wo, hit.ns)) / kPi);
-    gptr<DMaterial> dm = g.dmaterials + hit.mat;
+    const auto dm = tb_dmaterials(g) + hit.mat;
     const f3 col = (dm->bits & DMAT_COLOUR) ? load3(dm->base) : col_at_ray_hit<TEX>(g, m->tex, wi, cone, hit);
     f = col * dot_product;
     pdf = dot_product;
@@ -1320,26 +1375,28 @@ VD void tri_light_sample_with(f3 p0, f3 p1, f3 p2, f3 n0, f3 n1, f3 n2, float pd
 VD void tri_light_sample_at(f3 p0, f3 p1, f3 p2, f3 tri_normal, float pdf, f3 look_from, Rng& rng, f3& hit_n, EmitterInfo& info) {
   tri_light_sample_with(p0, p1, p2, tri_normal, tri_normal, tri_normal, pdf, look_from, rng, hit_n, info);
 }
-VD void tri_light_sample(const DScene& g, uint32_t tri, f3 look_from, Rng& rng, f3& le,
+template <class S>
+VD void tri_light_sample(const S& g, uint32_t tri, f3 look_from, Rng& rng, f3& le,
                          EmitterInfo& info) {
-  gptr<DTriShade> ts = g.tri_shade + tri;
+  const auto ts = tb_tri_shade(g) + tri;
   const f3 p0{ts->p[0], ts->p[1], ts->p[2]}, p1{ts->p[3], ts->p[4], ts->p[5]},
       p2{ts->p[6], ts->p[7], ts->p[8]};
-  gptr<VimgMesh> mesh = g.meshes + ts->mesh;
+  const auto mesh = tb_meshes(g) + ts->mesh;
   f3 tri_normal{ts->n[0], ts->n[1], ts->n[2]};   // normalize(cross(edge1, edge2)), baked
   f3 n0 = tri_normal, n1 = tri_normal, n2 = tri_normal;
   if (mesh->has_normals) {
-    n0 = load3(g.normals + 3 * size_t(ts->i0));
-    n1 = load3(g.normals + 3 * size_t(ts->i1));
-    n2 = load3(g.normals + 3 * size_t(ts->i2));
+    n0 = load3(scn(g).normals + 3 * size_t(ts->i0));
+    n1 = load3(scn(g).normals + 3 * size_t(ts->i1));
+    n2 = load3(scn(g).normals + 3 * size_t(ts->i2));
   }
   f3 hit_n;
-  tri_light_sample_with(p0, p1, p2, n0, n1, n2, g.tri_area_pdf[tri] /* 1.f / (length(cross(edge2, edge1)) / 2.0f), baked */, look_from,
+  tri_light_sample_with(p0, p1, p2, n0, n1, n2, scn(g).tri_area_pdf[tri] /* 1.f / (length(cross(edge2, edge1)) / 2.0f), baked */, look_from,
                         rng, hit_n, info);
-  le = mat_emitted(g.materials + mesh->material, info.wi, hit_n);
+  le = mat_emitted(tb_materials(g) + mesh->material, info.wi, hit_n);
 }
 // Triangle::surf_pdf: reference src/geometry/triangle.cpp:235-248
-VD float tri_surf_pdf(const DScene& g, uint32_t tri) { return g.tri_area_pdf[tri]; }
+template <class S>
+VD float tri_surf_pdf(const S& g, uint32_t tri) { return scn(g).tri_area_pdf[tri]; }
 // Sphere::sample: reference src/geometry/sphere.cpp:58-118 (cone construction of quirk Q16 kept)
 VD void sphere_light_sample_at(f3 center, float radius, f3 look_from, Rng& rng, f3& shading_normal, EmitterInfo& info) {
   float rand1 = rand_float(rng);
@@ -1374,7 +1431,8 @@ VD void sphere_light_sample_at(f3 center, float radius, f3 look_from, Rng& rng, 
   }
 }
 // Sphere::surf_pdf: reference src/geometry/sphere.cpp:120-139
-VD float sphere_surf_pdf(gptr<VimgSphere> sp, f3 look_from, f3 point_on_light, f3 dir) {
+template <class SpherePtr>   // (a row of tb_spheres)
+VD float sphere_surf_pdf(SpherePtr sp, f3 look_from, f3 point_on_light, f3 dir) {
   const f3 center = load3(sp->center);
   const float radius = sp->radius;
   if (length2(look_from - center) <= radius * radius) {
@@ -1488,17 +1546,17 @@ VD void background_sample(const DScene& g, Rng& rng, f3& le, EmitterInfo& info) 
   info = EmitterInfo{wi, pdf, VIMG_INF, 1.f};
 }
 // GroupOfEmitters::sample: reference include/geometry/emitters.h:39-56
-template <bool TEX>
-VD void lights_sample(const DScene& g, f3 look_from, Rng& rng, f3& le, EmitterInfo& info) {
+template <bool TEX, class S>
+VD void lights_sample(const S& g, f3 look_from, Rng& rng, f3& le, EmitterInfo& info) {
   float rnd = rand_float(rng);
-  float sx = rnd * g.num_lights;
-  const int index_obj = clampi(static_cast<int>(sx), 0, static_cast<int>(g.num_lights) - 1);
-  const float prob_obj = 1.f / g.num_lights;
+  float sx = rnd * scn(g).num_lights;
+  const int index_obj = clampi(static_cast<int>(sx), 0, static_cast<int>(scn(g).num_lights) - 1);
+  const float prob_obj = 1.f / scn(g).num_lights;
   // the emitter's baked record (device_scene.h: DLight): one fetch, then arithmetic
-  gptr<DLight> L = g.dlights + index_obj;
+  gptr<DLight> L = scn(g).dlights + index_obj;
   const uint32_t kind = L->kind;
   if (kind == 0u) {
-    background_sample<TEX>(g, rng, le, info);
+    background_sample<TEX>(scn(g), rng, le, info);
   } else if (kind == 2u) {
     tri_light_sample(g, L->index, look_from, rng, le, info);   // (vertex normals: through the tables)
   } else {
@@ -1517,10 +1575,11 @@ VD void lights_sample(const DScene& g, f3 look_from, Rng& rng, f3& le, EmitterIn
   }
   info.pdf *= prob_obj;
 }
-VD float surf_pdf(const DScene& g, uint32_t prim_id, f3 look_from, f3 look_at, f3 dir) {
-  const VimgPrim p = load_prim(g.prims + prim_id);
+template <class S>
+VD float surf_pdf(const S& g, uint32_t prim_id, f3 look_from, f3 look_at, f3 dir) {
+  const VimgPrim p = load_prim(tb_prims(g) + prim_id);
   if (p.type == VIMG_PRIM_TRIANGLE) return tri_surf_pdf(g, p.index);
-  return sphere_surf_pdf(g.spheres + p.index, look_from, look_at, dir);
+  return sphere_surf_pdf(tb_spheres(g) + p.index, look_from, look_at, dir);
 }
 
 VD float balance_heuristic(float pdf1, float pdf2) { return pdf1 / (pdf1 + pdf2); }

@@ -445,6 +445,7 @@ void record_for_updates(VimgDeviceScene* s, const VimgScene* sc) {
   s->num_vertices = sc->num_vertices;
   s->num_tris = sc->num_tris;
   s->num_spheres = sc->num_spheres;
+  s->num_meshes = sc->num_meshes;
   for (uint32_t i = 0; i < sc->num_meshes; ++i) {
     const VimgMesh& m = sc->meshes[i];
     if (!m.has_normals || m.num_vertices == 0) continue;
@@ -471,6 +472,7 @@ int resolve_options(VimgDeviceScene* s, const VimgHipOptions* opts) {
   options_from_env(&s->opt);
   if (const char* e = getenv("VIMG_HIP_QUERY_BLOCKS")) s->query_launch = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("VIMG_HIP_PLAIN")) s->force_general = atoi(e) == 0;   // 0: the general build of render_cu_kernel for every launch
+  if (const char* e = getenv("VIMG_HIP_LDS_TABLES")) s->no_lds_tables = atoi(e) == 0;   // 0: the shading tables stay in global memory
   if (s->opt.scheduler != VIMG_OPT_AUTO && (s->opt.scheduler < VIMG_SCHED_LANE || s->opt.scheduler > VIMG_SCHED_CU))
     return fail(VIMG_E_INVALID, "options: unknown scheduler");
   // the one gate: every launch builder relies on a resident scene's scheduler being AUTO, LANE or CU

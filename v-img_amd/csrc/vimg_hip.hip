@@ -94,6 +94,7 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, const RenderLa
   const hipStream_t st = r.st;
   float* d_out = r.d_out;
   LaunchCfg c = make_launch(s, p, r.sx, r.sy);
+  if (c.error) return fail(VIMG_E_INVALID, c.error);   // (options no launch can be made of: nothing has been enqueued)
   if (prog) {
     c.args.sample_base = prog->base;
     c.args.spp_div = static_cast<float>(prog->base + p->samples);   // (the caller keeps the total <= UINT32_MAX)
@@ -104,6 +105,7 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, const RenderLa
   }
   if (int rc = ensure_pool(s, c)) return rc;
   c.args.full_stats = r.stats ? 1u : 0u;
+  drop_unread_tables(s, c, r.stats);
   if (c.args.num_local_tiles == 0 && r.sx < 0) return VIMG_OK;
   // (the work counter only: the error word behind it is sticky until a blocking call or vimg_hip_check reads it)
   HIP_TRY(hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), st));
