@@ -1,7 +1,8 @@
 """What the two frame libraries share (v-img_amd/frames/frame_lib.h, hip._Tensors, hip.FrameCall, hip.GuideCache;
 DESIGN.md 4.20): every argument error is, code and whole sentence, what it was before the host skeleton was shared
-(tests/golden/frame_lib_errors.json, recorded from the two separate units), each library keeps an error slot of its
-own, the two frames structs open with the same eight fields, a call collects its tensors in one place, and a preview
+(tests/golden/frame_lib_errors.json, recorded from the two separate units), of two faults made at once every library
+reports the one it reported while its checks were its own copy (the record's "order"), each library keeps an error
+slot of its own, the two frames structs open with the same eight fields, a call collects its tensors in one place, and a preview
 renders its guides again after an edit of the scene and only then."""
 import ctypes as C
 import json
@@ -45,6 +46,60 @@ def test_an_argument_error_is_the_recorded_code_and_sentence(lib, case):
     mod = {"filter": FA, "temporal": TA}[lib]
     rc, msg = mod._call(**_arguments(mod, case))
     assert {"code": rc, "message": msg} == GOLDEN[lib][case]
+
+
+# ---- a'. which of two faults is reported ----------------------------------------------------------------------------
+# GOLDEN["order"]: per library its "faults", single edits of the module's _good_call() listed in the order of the
+# checks they trip ("nan" stands for the float), and "pairs" [i, j, code, message]: what the call said with faults i
+# and j made at once, j up to three places behind i, recorded from the units before their reprojection checks
+# (frames/reproject.h) and workspace checks (frame_lib.h's check_workspace) were written once.
+def _order_modules():
+    import test_infill_abi as IA
+    import test_moments_abi as MA
+    import test_varfilter_abi as VA
+    import test_wtemporal_abi as WA
+    return {"filter": FA, "temporal": TA, "varfilter": VA, "moments": MA, "infill": IA, "wtemporal": WA}
+
+
+def _fault(edit):
+    return {k: float(v) if isinstance(v, str) else v for k, v in edit.items()}
+
+
+def _clash(a, b):
+    """Two faults that cannot be made at once: they edit one argument (matrix and its entries m0..m11 are one)."""
+    keys = lambda e: {"matrix" if k[0] == "m" and k[1:].isdigit() else k for k in e}
+    return bool(keys(a) & keys(b))
+
+
+ORDER = [(lib, i, j) for lib, rec in GOLDEN["order"].items() for i, j, _, _ in rec["pairs"]]
+
+
+def test_the_order_record_covers_the_chains_and_the_seams():
+    assert sorted(GOLDEN["order"]) == sorted(_order_modules())
+    for lib, rec in GOLDEN["order"].items():
+        said = " | ".join(m for _, _, _, m in rec["pairs"])
+        if lib in ("filter", "varfilter", "infill"):
+            want = ("null workspace", "the workspace has 1 bytes")      # (null + short, short + misaligned)
+        else:
+            want = ("must be 16-byte aligned", "needs its world-to-pixel matrix", "entry 3 is not finite", "overlaps the previous one",
+                    "the next history overlaps the depth frame", "the output overlaps the previous history",
+                    "the output overlaps the position frame")
+            want += {"temporal": (), "moments": ("min_history must be", "is above max_history", "the output overlaps the variance frame",
+                                                 "the output variance overlaps the previous history", "the output variance overlaps the output"),
+                     "wtemporal": ("null weight frame", "the weight frame must be 4-byte aligned", "the output overlaps the weight frame",
+                                   "the output codes overlap the previous history", "the output codes overlap the weight frame")}[lib]
+        assert all(w in said for w in want), (lib, [w for w in want if w not in said])
+        # every adjacent pair that can be made at once is in the record
+        have = {(i, j) for i, j, _, _ in rec["pairs"]}
+        faults = rec["faults"]
+        assert all((i, i + 1) in have for i in range(len(faults) - 1) if not _clash(faults[i], faults[i + 1]))
+
+
+@pytest.mark.parametrize("lib,i,j", ORDER, ids=[f"{lib}:{i}+{j}" for lib, i, j in ORDER])
+def test_two_faults_at_once_report_the_recorded_one(lib, i, j):
+    mod, rec = _order_modules()[lib], GOLDEN["order"][lib]
+    rc, msg = mod._call(**mod._edit(**_fault(rec["faults"][i]), **_fault(rec["faults"][j])))
+    assert [i, j, rc, msg] in rec["pairs"], (rec["faults"][i], rec["faults"][j], rc, msg)
 
 
 # ---- b. two error slots ---------------------------------------------------------------------------------------------

@@ -7,10 +7,11 @@ so a filter call is ordered against torch exactly as a render is.  There is no C
 import ctypes as C
 
 from . import _abi as abi
-from .hip import FrameCall, _checker
+from .hip import FrameCall, _checker, library_params
 
 FRAMES = ("color", "normal", "position", "depth", "albedo")
 GUIDES = ("albedo", "normal", "position", "depth")     # the feature frames the filter reads beside the colour
+FLOATS = ("sigma_color", "sigma_normal", "sigma_plane", "albedo_floor")
 
 
 _lib = abi.filter_lib
@@ -20,17 +21,8 @@ _check = _checker(_lib, "vimg_filter_last_error")
 def atrous_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo_floor=None):
     """An abi.AtrousParams: the library's defaults (vimg_filter_atrous_defaults; include/vimg_filter.h names them) with
     the given values in place of them."""
-    p = abi.AtrousParams()
-    _lib().vimg_filter_atrous_defaults(C.byref(p))
-    if iterations is not None:
-        if not 0 <= int(iterations) < 2 ** 32:
-            raise ValueError(f"atrous: iterations must be 1..12, not {iterations}")
-        p.iterations = int(iterations)
-    for name, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane),
-                    ("albedo_floor", albedo_floor)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return library_params("atrous", abi.AtrousParams, _lib().vimg_filter_atrous_defaults, FLOATS,
+                          zip(FLOATS, (sigma_color, sigma_normal, sigma_plane, albedo_floor)), ("iterations", iterations, "1..12"))
 
 
 def atrous_workspace_bytes(width, height):
@@ -47,18 +39,12 @@ def atrous(color, normal, position, depth, albedo=None, iterations=None, sigma_c
     may be ``color`` itself; ``workspace``: a contiguous, 16-byte aligned CUDA tensor of at least
     atrous_workspace_bytes(W, H) bytes (64 per pixel), allocated here when None.  The call only enqueues, on
     ``stream`` or torch's current stream."""
-    import torch
     c = FrameCall("atrous", color)
     h, w = c.h, c.w
     params = atrous_params(iterations, sigma_color, sigma_normal, sigma_plane, albedo_floor)
     t = c.frames(FRAMES, (color, normal, position, depth, albedo), optional=("albedo",))
     out = c.output(out, "atrous", "float32", (h, w, 3))
-    if workspace is None:
-        workspace = c.own(torch.empty((atrous_workspace_bytes(w, h),), dtype=torch.uint8, device="cuda"))
-    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("atrous: workspace must be a contiguous CUDA tensor")
-    else:
-        c.use(workspace)
+    workspace = c.workspace(workspace, atrous_workspace_bytes(w, h))
     frames = abi.FilterFrames(width=w, height=h, **{k: v.data_ptr() for k, v in t.items()})
     with c.launch(stream) as sp:
         _check(_lib().vimg_filter_atrous(C.byref(frames), C.byref(params), C.c_void_p(out.data_ptr()),

@@ -14,6 +14,7 @@
 
 #define FRAME_LIB "atrous"
 #include "../frames/frame_lib.h"
+#include "../frames/guides.h"
 
 namespace vimg_filter {
 
@@ -25,8 +26,6 @@ struct Planes {
   float4* g0;
   float4* g1;
 };
-
-__device__ inline float floored(float a, float floor) { return a > floor ? a : floor; }
 
 __global__ __launch_bounds__(WAVE_X * ROWS) void atrous_pack_kernel(
     uint32_t w, uint32_t h, const float* __restrict__ color, const float* __restrict__ normal,
@@ -83,14 +82,10 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void atrous_iteration_kernel(
         if (!(nq.w > 0.f)) continue;
         const float4 pq = g1[q];
         cq = cin[q];
-        const float dn = 1.f - ((np.x * nq.x + np.y * nq.y) + np.z * nq.z);
-        const float s_n = dn < 0.f ? 0.f : dn / sigma_normal;
-        const float ex = pq.x - pp.x, ey = pq.y - pp.y, ez = pq.z - pp.z;
-        const float d = (np.x * ex + np.y * ey) + np.z * ez;
-        const float s_p = (d * d) / plane_den;
+        const float s_g = guide_score(np, pp, nq, pq, sigma_normal, plane_den);
         const float cx = cp.x - cq.x, cy = cp.y - cq.y, cz = cp.z - cq.z;
         const float s_c = ((cx * cx + cy * cy) + cz * cz) / color_den;
-        const float S = (s_n + s_p) + s_c;
+        const float S = s_g + s_c;
         const float one_s = 1.f - S;
         wq = S < 1.f ? k * (one_s * one_s) : 0.f;
       }
@@ -152,15 +147,9 @@ int vimg_filter_atrous(const VimgFilterFrames* f, const VimgAtrousParams* a, voi
   if (const int rc = check_float("sigma_normal", a->sigma_normal, 0.f, true, false)) return rc;
   if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
   if (const int rc = check_float("albedo_floor", a->albedo_floor, 0.f, true, false)) return rc;
-  if (!d_workspace) return fail(VIMG_E_INVALID, "atrous: null workspace");
-  const uint64_t need = vimg_filter_atrous_workspace(f->width, f->height);
-  if (workspace_bytes < need)
-    return fail(VIMG_E_INVALID, "atrous: the workspace has %llu bytes, %u x %u needs %llu",
-                static_cast<unsigned long long>(workspace_bytes), f->width, f->height, static_cast<unsigned long long>(need));
-  if (reinterpret_cast<uintptr_t>(d_workspace) % 16)
-    return fail(VIMG_E_INVALID, "atrous: the workspace must be 16-byte aligned");
-
   const uint32_t w = f->width, h = f->height;
+  if (const int rc = check_workspace(d_workspace, workspace_bytes, vimg_filter_atrous_workspace(w, h), w, h)) return rc;
+
   const size_t n = size_t(w) * h;
   float4* base = static_cast<float4*>(d_workspace);
   const Planes pl{base, base + n, base + 2 * n, base + 3 * n};

@@ -1,6 +1,8 @@
-// The host skeleton of a frame library (libvimg_filter.so, libvimg_temporal.so): the error slot, the
-// argument checks every frame library starts with, the launch shape and the launch check.  Internal: not installed,
-// not in include/.  A unit #defines FRAME_LIB ("atrous") before it includes this: it opens every sentence made here.
+// The host skeleton of a frame library (libvimg_filter.so, libvimg_temporal.so, ...): the error slot,
+// the argument checks every frame library starts with, the workspace check, the launch shape and the launch check.
+// Internal: not installed, not in include/.  A unit #defines FRAME_LIB ("atrous") before it includes this: it opens
+// every sentence made here and in reproject.h, which the libraries that reproject a history include after it;
+// guides.h holds the tap score of the spatial ones.
 // Everything is in an anonymous namespace: each library gets its own copy, and above all its own error slot.  One
 // inline variable of default visibility would be one weak symbol in two libraries, which the dynamic linker may
 // merge - vimg_filter_last_error() would then return the temporal library's message.
@@ -66,6 +68,16 @@ int check_float(const char* name, float v, float low, bool strict, bool may_be_i
 bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
   const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
   return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+// the caller's workspace of `have` bytes, of which a w x h frame needs `need`
+int check_workspace(const void* workspace, uint64_t have, uint64_t need, uint32_t w, uint32_t h) {
+  if (!workspace) return fail(VIMG_E_INVALID, FRAME_LIB ": null workspace");
+  if (have < need)
+    return fail(VIMG_E_INVALID, FRAME_LIB ": the workspace has %llu bytes, %u x %u needs %llu", static_cast<unsigned long long>(have),
+                w, h, static_cast<unsigned long long>(need));
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(VIMG_E_INVALID, FRAME_LIB ": the workspace must be 16-byte aligned");
+  return VIMG_OK;
 }
 
 // ---- the launch shape: one lane per pixel, a wave is 64 consecutive pixels of one row, the tail is a bounds test ----

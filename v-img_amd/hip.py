@@ -193,6 +193,69 @@ class FrameCall(_Tensors):
         return {name: self.take(a, f"{self.what} {name}", ("float32",), shape)
                 for name, a in zip(names, arrays) if not (a is None and name in optional)}
 
+    def history(self, history, cls):
+        """(device tensor, the 12 floats of its matrix) of the ``history`` an accumulate call reprojects, which must be
+        a ``cls`` (a FrameHistory class) that knows its matrix; (None, None) without one."""
+        if history is None:
+            return None, None
+        if not isinstance(history, cls):
+            raise ValueError(f"{self.what}: history must be a {cls.__module__.rsplit('.', 1)[-1]}.{cls.__name__}")
+        if history.world_to_pixel is None:
+            raise ValueError(f"{self.what}: the history does not know its world_to_pixel matrix")
+        prev = self.take(history.tensor, f"{self.what} history", ("float32",), (cls.PLANES, self.h, self.w, 4), aligned=True)
+        return prev, (abi.f32 * 12)(*history.world_to_pixel.tolist())
+
+    def workspace(self, workspace, nbytes):
+        """The caller's ``workspace`` as it is, or ``nbytes`` bytes of this call's own when None."""
+        import torch
+        if workspace is None:
+            return self.own(torch.empty((nbytes,), dtype=torch.uint8, device="cuda"))
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError(f"{self.what}: workspace must be a contiguous CUDA tensor")
+        return self.use(workspace)
+
+
+class FrameHistory:
+    """What the histories of the accumulating frame libraries share (temporal.History, moments.History): ``tensor``
+    [PLANES, H, W, 4] float32, whose planes open with A = {rgb, length}, G0 = {normal, depth}, G1 = {position, 0}, and
+    ``world_to_pixel``, the matrix of the camera its frame was rendered under (None: unknown, the history cannot be
+    reprojected).  ``color`` [H, W, 3] and ``length`` [H, W] are views."""
+    PLANES = None
+
+    def __init__(self, tensor, world_to_pixel=None):
+        if len(tensor.shape) != 4 or tensor.shape[0] != self.PLANES or tensor.shape[3] != 4:
+            raise ValueError(f"History: shape must be ({self.PLANES}, H, W, 4), not {tuple(tensor.shape)}")
+        self.tensor = tensor
+        self.world_to_pixel = None if world_to_pixel is None else np.ascontiguousarray(world_to_pixel, dtype=np.float32).reshape(12)
+
+    @property
+    def color(self):
+        return self.tensor[0, :, :, :3]
+
+    @property
+    def length(self):
+        return self.tensor[0, :, :, 3]
+
+
+def library_params(what, struct, defaults, floats, given, count=None):
+    """An abi ``struct`` of parameters: the library's defaults (``defaults`` fills them in) with the values of ``given``
+    ((name, value) pairs; None keeps the default) in place of them.  ``floats`` are the names ``given`` may hold - a
+    call's keywords with another are refused - and ``count`` = (name, value, "1..12") is the library's one integer
+    field."""
+    p = struct()
+    defaults(C.byref(p))
+    if count is not None and count[1] is not None:
+        name, v, allowed = count
+        if not 0 <= int(v) < 2 ** 32:
+            raise ValueError(f"{what}: {name} must be {allowed}, not {v}")
+        setattr(p, name, int(v))
+    for name, v in given:
+        if name not in floats:
+            raise TypeError(f"{what}: unknown parameters {sorted(n for n, _ in given if n not in floats)}; expected some of {floats}")
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi as abi
 from .filter import FRAMES, GUIDES
-from .hip import FrameCall, _checker
+from .hip import FrameCall, _checker, library_params
 
 _lib = abi.infill_lib
 _check = _checker(_lib, "vimg_infill_last_error")
@@ -24,16 +24,8 @@ MIN_STRIDE, MAX_STRIDE = 2, 4
 def params(radius=None, sigma_normal=None, sigma_plane=None, albedo_floor=None):
     """An abi.InfillParams: the library's defaults (vimg_infill_defaults; include/vimg_infill.h names them) with the
     given values in place of them."""
-    p = abi.InfillParams()
-    _lib().vimg_infill_defaults(C.byref(p))
-    if radius is not None:
-        if not 0 <= int(radius) < 2 ** 32:
-            raise ValueError(f"infill: radius must be 1..{abi.INFILL_MAX_RADIUS}, not {radius}")
-        p.radius = int(radius)
-    for name, v in zip(FLOATS, (sigma_normal, sigma_plane, albedo_floor)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return library_params("infill", abi.InfillParams, _lib().vimg_infill_defaults, FLOATS,
+                          zip(FLOATS, (sigma_normal, sigma_plane, albedo_floor)), ("radius", radius, f"1..{abi.INFILL_MAX_RADIUS}"))
 
 
 def workspace_bytes(width, height):
@@ -88,12 +80,7 @@ def reconstruct(color, normal, position, depth, count, albedo=None, radius=None,
     t["count"] = c.take(count, "infill count", ("int32",), (h, w))
     out = c.output(out, "infill", "float32", (h, w, 3))
     out_code = c.output(out_code, "infill out_code", "uint8", (h, w))
-    if workspace is None:
-        workspace = c.own(torch.empty((workspace_bytes(w, h),), dtype=torch.uint8, device="cuda"))
-    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("infill: workspace must be a contiguous CUDA tensor")
-    else:
-        c.use(workspace)
+    workspace = c.workspace(workspace, workspace_bytes(w, h))
     frames = abi.InfillFrames(width=w, height=h, **{k: v.data_ptr() for k, v in t.items()})
     with c.launch(stream) as sp:
         _check(_lib().vimg_infill_reconstruct(C.byref(frames), C.byref(p), C.c_void_p(out.data_ptr()),

@@ -21,12 +21,11 @@
 
 #define FRAME_LIB "infill"
 #include "../frames/frame_lib.h"
+#include "../frames/guides.h"
 
 namespace vimg_infill {
 
 using namespace vimg_frames;
-
-__device__ inline float floored(float a, float floor) { return a > floor ? a : floor; }
 
 __global__ __launch_bounds__(WAVE_X * ROWS) void infill_pack_kernel(
     uint32_t w, uint32_t h, const float* __restrict__ color, const float* __restrict__ normal,
@@ -64,12 +63,7 @@ __device__ inline void add_tap(Sums& s, float k, bool live, const float4& np, co
   if (live_q != live) return;
   float wq = k;
   if (live) {
-    const float dn = 1.f - ((np.x * nq.x + np.y * nq.y) + np.z * nq.z);
-    const float s_n = dn < 0.f ? 0.f : dn / sigma_normal;
-    const float ex = pq.x - pp.x, ey = pq.y - pp.y, ez = pq.z - pp.z;
-    const float d = (np.x * ex + np.y * ey) + np.z * ez;
-    const float s_p = (d * d) / plane_den;
-    const float S = s_n + s_p;
+    const float S = guide_score(np, pp, nq, pq, sigma_normal, plane_den);
     const float one_s = 1.f - S;
     wq = S < 1.f ? k * (one_s * one_s) : 0.f;
   }
@@ -188,14 +182,9 @@ int vimg_infill_reconstruct(const VimgInfillFrames* f, const VimgInfillParams* a
   if (const int rc = check_float("sigma_normal", a->sigma_normal, 0.f, true, false)) return rc;
   if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
   if (const int rc = check_float("albedo_floor", a->albedo_floor, 0.f, true, false)) return rc;
-  if (!d_workspace) return fail(VIMG_E_INVALID, "infill: null workspace");
   const uint32_t w = f->width, h = f->height;
   const uint64_t need = vimg_infill_workspace(w, h);
-  if (workspace_bytes < need)
-    return fail(VIMG_E_INVALID, "infill: the workspace has %llu bytes, %u x %u needs %llu",
-                static_cast<unsigned long long>(workspace_bytes), w, h, static_cast<unsigned long long>(need));
-  if (reinterpret_cast<uintptr_t>(d_workspace) % 16)
-    return fail(VIMG_E_INVALID, "infill: the workspace must be 16-byte aligned");
+  if (const int rc = check_workspace(d_workspace, workspace_bytes, need, w, h)) return rc;
   // other lanes read the planes, and pack reads every frame before fill writes: only the colour frame itself may be
   // the output
   const uint64_t frame = uint64_t(12) * w * h, plane = uint64_t(4) * w * h, codes = uint64_t(w) * h;

@@ -8,11 +8,9 @@ tensor check and stream rule (hip.FrameCall: hip._device_tensor, hip._Launch).  
 """
 import ctypes as C
 
-import numpy as np
-
 from . import _abi as abi
 from . import temporal
-from .hip import FrameCall, _checker
+from .hip import FrameCall, FrameHistory, _checker, library_params
 from .temporal import FRAMES, world_to_pixel
 
 PARAMS = ("max_history", "current_weight", "sigma_normal", "sigma_plane", "min_history")
@@ -24,39 +22,25 @@ _check = _checker(_lib, "vimg_moments_last_error")
 def params(max_history=None, current_weight=None, sigma_normal=None, sigma_plane=None, min_history=None):
     """An abi.MomentsParams: the library's defaults (vimg_moments_defaults; include/vimg_moments.h names them) with
     the given values in place of them."""
-    p = abi.MomentsParams()
-    _lib().vimg_moments_defaults(C.byref(p))
-    for name, v in zip(PARAMS, (max_history, current_weight, sigma_normal, sigma_plane, min_history)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return _params(zip(PARAMS, (max_history, current_weight, sigma_normal, sigma_plane, min_history)))
+
+
+def _params(given):
+    return library_params("moments", abi.MomentsParams, _lib().vimg_moments_defaults, PARAMS, given)
 
 
 def history_bytes(width, height):
     return int(_lib().vimg_moments_history_bytes(width, height))
 
 
-class History:
+class History(FrameHistory):
     """One history of vimg_moments_accumulate: ``tensor`` [4, H, W, 4] float32 (planes A = {rgb, length},
     G0 = {normal, depth}, G1 = {position, 0}, M = {m1, m2, V, 0}; a CUDA tensor, or a numpy array after a call with
     numpy frames) and ``world_to_pixel``, the matrix of the camera its frame was rendered under (None: unknown, the
     history cannot be reprojected).  ``color`` [H, W, 3], ``length`` [H, W], ``moments`` [H, W, 2] and ``variance``
     [H, W] (NaN: unknown) are views; ``temporal`` is a temporal.History over planes 0..2, a view too, with the same
     matrix."""
-
-    def __init__(self, tensor, world_to_pixel=None):
-        if len(tensor.shape) != 4 or tensor.shape[0] != 4 or tensor.shape[3] != 4:
-            raise ValueError(f"History: shape must be (4, H, W, 4), not {tuple(tensor.shape)}")
-        self.tensor = tensor
-        self.world_to_pixel = None if world_to_pixel is None else np.ascontiguousarray(world_to_pixel, dtype=np.float32).reshape(12)
-
-    @property
-    def color(self):
-        return self.tensor[0, :, :, :3]
-
-    @property
-    def length(self):
-        return self.tensor[0, :, :, 3]
+    PLANES = 4
 
     @property
     def moments(self):
@@ -84,22 +68,12 @@ def accumulate(color, normal, position, depth, variance=None, history=None, worl
     sigma_plane, min_history, default the library's (include/vimg_moments.h).  The call only enqueues, on ``stream`` or
     torch's current stream."""
     c = FrameCall("moments", color)
-    unknown = sorted(set(params_kw) - set(PARAMS))
-    if unknown:
-        raise TypeError(f"moments: unknown parameters {unknown}; expected some of {PARAMS}")
     h, w = c.h, c.w
-    p = params(**params_kw)
+    p = _params(params_kw.items())
     t = c.frames(FRAMES, (color, normal, position, depth))
     if variance is not None:
         t["variance"] = c.take(variance, "moments variance", ("float32",), (h, w))
-    prev = matrix = None
-    if history is not None:
-        if not isinstance(history, History):
-            raise ValueError("moments: history must be a moments.History")
-        if history.world_to_pixel is None:
-            raise ValueError("moments: the history does not know its world_to_pixel matrix")
-        prev = c.take(history.tensor, "moments history", ("float32",), (4, h, w, 4), aligned=True)
-        matrix = (abi.f32 * 12)(*history.world_to_pixel.tolist())
+    prev, matrix = c.history(history, History)
     next_history = c.output(next_history, "moments next_history", "float32", (4, h, w, 4), aligned=True)
     if out is not None:
         c.output(out, "moments", "float32", (h, w, 3))

@@ -5,8 +5,8 @@
 //   G0   {n.x, n.y, n.z, z}
 //   G1   {P.x, P.y, P.z, 0}
 //   M    {m1, m2, V, 0}       accumulated moments of luminance, variance of Y(A.rgb) (NaN: unknown)
-// Planes A, G0, G1 and the rgb output are vimg_temporal_accumulate's (temporal/reproject.hip), restated here operation
-// for operation: a frame library calls no other.  Launch shape of frames/frame_lib.h: one lane per pixel, blockDim
+// Planes A, G0, G1 and the rgb output are vimg_temporal_accumulate's: both kernels get the reprojection from
+// frames/reproject.h and end it with the same blend.  Launch shape of frames/frame_lib.h: one lane per pixel, blockDim
 // (64, 4), so a wave is 64 consecutive pixels of one row.  The current frame's reads (packed triples, one float of
 // variance) and all writes are contiguous per wave; the up to four history taps are gathers wherever the old camera saw
 // the pixel's surface point - a float4 of plane A, of each guide plane and, for a tap that counts, of plane M, which is
@@ -19,14 +19,16 @@
 
 #define FRAME_LIB "moments"
 #include "../frames/frame_lib.h"
+#include "../frames/guides.h"
+#include "../frames/reproject.h"
 
 namespace vimg_moments {
 
 using namespace vimg_frames;
 
 struct Constants {
-  float m[12];     // prev_world_to_pixel, row-major 3 x 4
-  float max_history, current_weight, sigma_normal, sigma_plane, min_history;
+  Reprojection r;
+  float max_history, current_weight, min_history;
 };
 
 // `color` and `out`, `variance` and `out_var` may be the same buffer: none of them is __restrict__, and a lane reads
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void moments_accumulate_kernel(
   next[2 * n + p] = make_float4(px, py, pz, 0.f);
 
   const float unknown = __int_as_float(0x7fc00000);
-  const float lc = (cr * 0.212671f + cg * 0.715160f) + cb * 0.072169f;
+  const float lc = lum(cr, cg, cb);
   float x2 = lc * lc;
   if (vk) x2 = x2 + v * (k.current_weight - 1.f);
 
@@ -57,68 +59,32 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void moments_accumulate_kernel(
   if (z > 0.f) {
     a.w = 1.f;                                  // live without history
     m.z = vk ? v : unknown;
-    if (prev) {
-      const float hx = ((k.m[0] * px + k.m[1] * py) + k.m[2] * pz) + k.m[3];
-      const float hy = ((k.m[4] * px + k.m[5] * py) + k.m[6] * pz) + k.m[7];
-      const float hw = ((k.m[8] * px + k.m[9] * py) + k.m[10] * pz) + k.m[11];
-      if (hw > 0.f) {
-        const float fx = hx / hw - 0.5f, fy = hy / hw - 0.5f;
-        if (fx > -1.f && fx < float(w) && fy > -1.f && fy < float(h)) {
-          const float x0 = floorf(fx), y0 = floorf(fy);      // -1 .. w - 1, -1 .. h - 1: exact as int
-          const float tx = fx - x0, ty = fy - y0;
-          const float ux = 1.f - tx, uy = 1.f - ty;
-          const float b[4] = {ux * uy, tx * uy, ux * ty, tx * ty};
-          const int ix = int(x0), iy = int(y0);
-          const float sz = k.sigma_plane * z;
-          const float plane = sz * sz;
-          float sumb = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int qx = ix + (i & 1), qy = iy + (i >> 1);
-            if (uint32_t(qx) >= w || uint32_t(qy) >= h) continue;
-            if (!(b[i] > 0.f)) continue;
-            const size_t q = size_t(qy) * w + size_t(qx);
-            const float4 hq = prev[q];
-            if (!(hq.w > 0.f)) continue;
-            const float4 nq = prev[n + q];
-            const float dn = 1.f - ((nx * nq.x + ny * nq.y) + nz * nq.z);
-            if (!(dn < k.sigma_normal)) continue;
-            const float4 pq = prev[2 * n + q];
-            const float ex = pq.x - px, ey = pq.y - py, ez = pq.z - pz;
-            const float d = (nx * ex + ny * ey) + nz * ez;
-            if (!(d * d < plane)) continue;
-            const float4 mq = prev[3 * n + q];
-            sumb = sumb + b[i];
-            sr = sr + b[i] * hq.x;
-            sg = sg + b[i] * hq.y;
-            sb = sb + b[i] * hq.z;
-            sl = sl + b[i] * hq.w;
-            s1 = s1 + b[i] * mq.x;
-            s2 = s2 + b[i] * mq.y;
-          }
-          if (sumb > 0.f) {
-            const float hr = sr / sumb, hg = sg / sumb, hb = sb / sumb, len = sl / sumb;
-            float cnt = len + k.current_weight;
-            if (cnt > k.max_history) cnt = k.max_history;
-            float al = k.current_weight / cnt;
-            if (al > 1.f) al = 1.f;
-            a = make_float4(hr + (cr - hr) * al, hg + (cg - hg) * al, hb + (cb - hb) * al, cnt);
+    Reprojected hst;
+    float s1 = 0.f, s2 = 0.f;
+    const auto moments_of = [&](float b, size_t q) {      // plane M, of a tap that counts alone
+      const float4 mq = prev[3 * n + q];
+      s1 = s1 + b * mq.x;
+      s2 = s2 + b * mq.y;
+    };
+    if (reproject(w, h, prev, k.r, nx, ny, nz, px, py, pz, z, hst, moments_of)) {
+      float cnt = hst.len + k.current_weight;
+      if (cnt > k.max_history) cnt = k.max_history;
+      float al = k.current_weight / cnt;
+      if (al > 1.f) al = 1.f;
+      a = make_float4(hst.hr + (cr - hst.hr) * al, hst.hg + (cg - hst.hg) * al, hst.hb + (cb - hst.hb) * al, cnt);
 
-            const float m1h = s1 / sumb, m2h = s2 / sumb;
-            float sh = m2h - m1h * m1h;
-            if (sh < 0.f) sh = 0.f;
-            const float vh = sh / len;
-            const float m1 = m1h + (lc - m1h) * al, m2 = m2h + (x2 - m2h) * al;
-            float sc = m2 - m1 * m1;
-            if (sc < 0.f) sc = 0.f;
-            const float vc = vk ? v : sc / k.current_weight;
-            const float u = 1.f - al;
-            float var = (u * u) * vh + (al * al) * vc;
-            if (!(cnt >= k.min_history)) var = unknown;      // too short a history to trust: the filter estimates spatially
-            m = make_float4(m1, m2, var, 0.f);
-          }
-        }
-      }
+      const float m1h = s1 / hst.sumb, m2h = s2 / hst.sumb;
+      float sh = m2h - m1h * m1h;
+      if (sh < 0.f) sh = 0.f;
+      const float vh = sh / hst.len;
+      const float m1 = m1h + (lc - m1h) * al, m2 = m2h + (x2 - m2h) * al;
+      float sc = m2 - m1 * m1;
+      if (sc < 0.f) sc = 0.f;
+      const float vc = vk ? v : sc / k.current_weight;
+      const float u = 1.f - al;
+      float var = (u * u) * vh + (al * al) * vc;
+      if (!(cnt >= k.min_history)) var = unknown;      // too short a history to trust: the filter estimates spatially
+      m = make_float4(m1, m2, var, 0.f);
     }
   }
   next[p] = a;
@@ -164,61 +130,17 @@ int vimg_moments_accumulate(const VimgMomentsFrames* f, const void* d_prev_histo
   if (const int rc = check_float("min_history", a->min_history, 1.f, false, false)) return rc;
   if (a->min_history > a->max_history)
     return fail(VIMG_E_INVALID, "moments: min_history %g is above max_history %g", double(a->min_history), double(a->max_history));
-  if (reinterpret_cast<uintptr_t>(d_next_history) % 16)
-    return fail(VIMG_E_INVALID, "moments: the next history must be 16-byte aligned");
-  Constants k{};
-  if (d_prev_history) {
-    if (reinterpret_cast<uintptr_t>(d_prev_history) % 16)
-      return fail(VIMG_E_INVALID, "moments: the previous history must be 16-byte aligned");
-    if (!prev_world_to_pixel)
-      return fail(VIMG_E_INVALID, "moments: a previous history needs its world-to-pixel matrix");
-  }
-  if (prev_world_to_pixel)
-    for (int i = 0; i < 12; ++i) {
-      if (!std::isfinite(prev_world_to_pixel[i]))
-        return fail(VIMG_E_INVALID, "moments: world-to-pixel entry %d is not finite (%g)", i, double(prev_world_to_pixel[i]));
-      k.m[i] = prev_world_to_pixel[i];
-    }
   const uint32_t w = f->width, h = f->height;
-  const uint64_t hist = vimg_moments_history_bytes(w, h), frame = uint64_t(12) * w * h, plane = uint64_t(4) * w * h;
-  if (d_prev_history && overlaps(d_next_history, hist, d_prev_history, hist))
-    return fail(VIMG_E_INVALID, "moments: the next history overlaps the previous one");
-  const void* frames[4] = {f->color, f->normal, f->position, f->depth};
-  const char* names[4] = {"color", "normal", "position", "depth"};
-  for (int i = 0; i < 4; ++i)
-    if (overlaps(d_next_history, hist, frames[i], frame))
-      return fail(VIMG_E_INVALID, "moments: the next history overlaps the %s frame", names[i]);
-  if (f->variance && overlaps(d_next_history, hist, f->variance, plane))
-    return fail(VIMG_E_INVALID, "moments: the next history overlaps the variance frame");
-  if (d_out_rgb) {      // other lanes gather from prev and read the guides; only the colour frame itself may be the output
-    if (d_prev_history && overlaps(d_out_rgb, frame, d_prev_history, hist))
-      return fail(VIMG_E_INVALID, "moments: the output overlaps the previous history");
-    if (overlaps(d_out_rgb, frame, d_next_history, hist))
-      return fail(VIMG_E_INVALID, "moments: the output overlaps the next history");
-    for (int i = 0; i < 4; ++i)
-      if (overlaps(d_out_rgb, frame, frames[i], frame) && !(i == 0 && d_out_rgb == f->color))
-        return fail(VIMG_E_INVALID, i == 0 ? "moments: the output overlaps the %s frame without being it"
-                                           : "moments: the output overlaps the %s frame", names[i]);
-    if (f->variance && overlaps(d_out_rgb, frame, f->variance, plane))
-      return fail(VIMG_E_INVALID, "moments: the output overlaps the variance frame");
-  }
-  if (d_out_variance) {      // the same rule: only the variance frame itself may be the output variance
-    if (d_prev_history && overlaps(d_out_variance, plane, d_prev_history, hist))
-      return fail(VIMG_E_INVALID, "moments: the output variance overlaps the previous history");
-    if (overlaps(d_out_variance, plane, d_next_history, hist))
-      return fail(VIMG_E_INVALID, "moments: the output variance overlaps the next history");
-    for (int i = 0; i < 4; ++i)
-      if (overlaps(d_out_variance, plane, frames[i], frame))
-        return fail(VIMG_E_INVALID, "moments: the output variance overlaps the %s frame", names[i]);
-    if (d_out_rgb && overlaps(d_out_variance, plane, d_out_rgb, frame))
-      return fail(VIMG_E_INVALID, "moments: the output variance overlaps the output");
-    if (f->variance && d_out_variance != f->variance && overlaps(d_out_variance, plane, f->variance, plane))
-      return fail(VIMG_E_INVALID, "moments: the output variance overlaps the variance frame without being it");
-  }
+  const uint64_t plane = uint64_t(4) * w * h;
+  const ReadFrame reads[] = {{f->variance, plane, "variance"}};
+  Constants k{};      // only the variance frame itself may be the output variance
+  if (const int rc = check_reprojection(f, d_prev_history, prev_world_to_pixel, d_next_history, vimg_moments_history_bytes(w, h), reads,
+                                        d_out_rgb, {d_out_variance, plane, "output variance overlaps", 0}, k.r))
+    return rc;
   k.max_history = a->max_history;
   k.current_weight = a->current_weight;
-  k.sigma_normal = a->sigma_normal;
-  k.sigma_plane = a->sigma_plane;
+  k.r.sigma_normal = a->sigma_normal;
+  k.r.sigma_plane = a->sigma_plane;
   k.min_history = a->min_history;
 
   clear_stale_error();

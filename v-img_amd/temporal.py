@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _abi as abi
-from .hip import FrameCall, GuideCache, _checker
+from .hip import FrameCall, FrameHistory, GuideCache, _checker, library_params
 
 FRAMES = ("color", "normal", "position", "depth")
 PARAMS = ("max_history", "current_weight", "sigma_normal", "sigma_plane")
@@ -25,12 +25,11 @@ _check = _checker(_lib, "vimg_temporal_last_error")
 def temporal_params(max_history=None, current_weight=None, sigma_normal=None, sigma_plane=None):
     """An abi.TemporalParams: the library's defaults (vimg_temporal_defaults; include/vimg_temporal.h names them) with
     the given values in place of them."""
-    p = abi.TemporalParams()
-    _lib().vimg_temporal_defaults(C.byref(p))
-    for name, v in zip(PARAMS, (max_history, current_weight, sigma_normal, sigma_plane)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return _params(zip(PARAMS, (max_history, current_weight, sigma_normal, sigma_plane)))
+
+
+def _params(given):
+    return library_params("temporal", abi.TemporalParams, _lib().vimg_temporal_defaults, PARAMS, given)
 
 
 def history_bytes(width, height):
@@ -56,25 +55,12 @@ def world_to_pixel(camera):
     return m.astype(np.float32).reshape(12)
 
 
-class History:
+class History(FrameHistory):
     """One history of vimg_temporal_accumulate: ``tensor`` [3, H, W, 4] float32 (planes A = {rgb, length},
     G0 = {normal, depth}, G1 = {position, 0}; a CUDA tensor, or a numpy array after a call with numpy frames) and
     ``world_to_pixel``, the matrix of the camera its frame was rendered under (None: unknown, the history cannot be
     reprojected).  ``color`` [H, W, 3] and ``length`` [H, W] are views."""
-
-    def __init__(self, tensor, world_to_pixel=None):
-        if len(tensor.shape) != 4 or tensor.shape[0] != 3 or tensor.shape[3] != 4:
-            raise ValueError(f"History: shape must be (3, H, W, 4), not {tuple(tensor.shape)}")
-        self.tensor = tensor
-        self.world_to_pixel = None if world_to_pixel is None else np.ascontiguousarray(world_to_pixel, dtype=np.float32).reshape(12)
-
-    @property
-    def color(self):
-        return self.tensor[0, :, :, :3]
-
-    @property
-    def length(self):
-        return self.tensor[0, :, :, 3]
+    PLANES = 3
 
 
 def accumulate(color, normal, position, depth, history=None, world_to_pixel=None, out=None, next_history=None, stream=None,
@@ -90,20 +76,10 @@ def accumulate(color, normal, position, depth, history=None, world_to_pixel=None
     holds), allocated when None.  ``params``: max_history, current_weight, sigma_normal, sigma_plane, default the
     library's (include/vimg_temporal.h).  The call only enqueues, on ``stream`` or torch's current stream."""
     c = FrameCall("temporal", color)
-    unknown = sorted(set(params) - set(PARAMS))
-    if unknown:
-        raise TypeError(f"temporal: unknown parameters {unknown}; expected some of {PARAMS}")
     h, w = c.h, c.w
-    p = temporal_params(**params)
+    p = _params(params.items())
     t = c.frames(FRAMES, (color, normal, position, depth))
-    prev = matrix = None
-    if history is not None:
-        if not isinstance(history, History):
-            raise ValueError("temporal: history must be a temporal.History")
-        if history.world_to_pixel is None:
-            raise ValueError("temporal: the history does not know its world_to_pixel matrix")
-        prev = c.take(history.tensor, "temporal history", ("float32",), (3, h, w, 4), aligned=True)
-        matrix = (abi.f32 * 12)(*history.world_to_pixel.tolist())
+    prev, matrix = c.history(history, History)
     next_history = c.output(next_history, "temporal next_history", "float32", (3, h, w, 4), aligned=True)
     if out is not None:
         c.output(out, "temporal", "float32", (h, w, 3))

@@ -4,10 +4,12 @@
 //   A    {r, g, b, L}         accumulated radiance, history length (0: no surface)
 //   G0   {n.x, n.y, n.z, z}
 //   G1   {P.x, P.y, P.z, 0}
-// Launch shape of frames/frame_lib.h: one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of
-// one row.  The current frame's reads (packed triples) and all writes are contiguous per wave; the up to four history
-// taps are gathers wherever the old camera saw the pixel's surface point, a whole float4 of plane A and xyz of the guide planes.  The tail is a
-// bounds test.  The matrix and the parameters travel as kernel arguments.
+// The reprojection itself - the projection, the tap tests, the means of the accepted taps - is frames/reproject.h's,
+// which the moments and the weighted library build on too, and so are the checks of the histories and the output.
+// Launch shape of frames/frame_lib.h: one lane per pixel, blockDim (64, 4), so a wave is 64 consecutive pixels of one
+// row.  The current frame's reads (packed triples) and all writes are contiguous per wave; the up to four history taps
+// are gathers wherever the old camera saw the pixel's surface point, a whole float4 of plane A and xyz of the guide
+// planes.  The tail is a bounds test.  The matrix and the parameters travel as kernel arguments.
 //
 // The arithmetic is the header's contract, operation for operation: built with -ffp-contract=off and without
 // fast-math, so + - * / round once each, and the select forms below are the contract's comparisons (a NaN compares
@@ -16,22 +18,23 @@
 
 #define FRAME_LIB "temporal"
 #include "../frames/frame_lib.h"
+#include "../frames/reproject.h"
 
 namespace vimg_temporal {
 
 using namespace vimg_frames;
 
 struct Constants {
-  float m[12];     // prev_world_to_pixel, row-major 3 x 4
-  float max_history, current_weight, sigma_normal, sigma_plane;
+  Reprojection r;
+  float max_history, current_weight;
 };
 
 // `color` and `out` may be the same buffer: neither is __restrict__, and a lane reads its colour before it writes
 __global__ __launch_bounds__(WAVE_X * ROWS) void temporal_accumulate_kernel(
     uint32_t w, uint32_t h, const float* color, const float* __restrict__ normal, const float* __restrict__ position,
     const float* __restrict__ depth, const float4* __restrict__ prev, Constants k, float4* __restrict__ next, float* out) {
-  const int x = int(blockIdx.x * WAVE_X + threadIdx.x), y = int(blockIdx.y * ROWS + threadIdx.y);
-  if (uint32_t(x) >= w || uint32_t(y) >= h) return;
+  int x, y;
+  if (!pixel_of(w, h, x, y)) return;
   const size_t n = size_t(w) * h, p = size_t(y) * w + size_t(x), t = 3 * p;
   const float z = depth[t];
   const float cr = color[t], cg = color[t + 1], cb = color[t + 2];
@@ -43,52 +46,13 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void temporal_accumulate_kernel(
   float4 a = make_float4(cr, cg, cb, 0.f);      // not live: a miss or a NaN depth
   if (z > 0.f) {
     a.w = 1.f;                                  // live without history
-    if (prev) {
-      const float hx = ((k.m[0] * px + k.m[1] * py) + k.m[2] * pz) + k.m[3];
-      const float hy = ((k.m[4] * px + k.m[5] * py) + k.m[6] * pz) + k.m[7];
-      const float hw = ((k.m[8] * px + k.m[9] * py) + k.m[10] * pz) + k.m[11];
-      if (hw > 0.f) {
-        const float fx = hx / hw - 0.5f, fy = hy / hw - 0.5f;
-        if (fx > -1.f && fx < float(w) && fy > -1.f && fy < float(h)) {
-          const float x0 = floorf(fx), y0 = floorf(fy);      // -1 .. w - 1, -1 .. h - 1: exact as int
-          const float tx = fx - x0, ty = fy - y0;
-          const float ux = 1.f - tx, uy = 1.f - ty;
-          const float b[4] = {ux * uy, tx * uy, ux * ty, tx * ty};
-          const int ix = int(x0), iy = int(y0);
-          const float sz = k.sigma_plane * z;
-          const float plane = sz * sz;
-          float sumb = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int qx = ix + (i & 1), qy = iy + (i >> 1);
-            if (uint32_t(qx) >= w || uint32_t(qy) >= h) continue;
-            if (!(b[i] > 0.f)) continue;
-            const size_t q = size_t(qy) * w + size_t(qx);
-            const float4 hq = prev[q];
-            if (!(hq.w > 0.f)) continue;
-            const float4 nq = prev[n + q];
-            const float dn = 1.f - ((nx * nq.x + ny * nq.y) + nz * nq.z);
-            if (!(dn < k.sigma_normal)) continue;
-            const float4 pq = prev[2 * n + q];
-            const float ex = pq.x - px, ey = pq.y - py, ez = pq.z - pz;
-            const float d = (nx * ex + ny * ey) + nz * ez;
-            if (!(d * d < plane)) continue;
-            sumb = sumb + b[i];
-            sr = sr + b[i] * hq.x;
-            sg = sg + b[i] * hq.y;
-            sb = sb + b[i] * hq.z;
-            sl = sl + b[i] * hq.w;
-          }
-          if (sumb > 0.f) {
-            const float hr = sr / sumb, hg = sg / sumb, hb = sb / sumb, len = sl / sumb;
-            float cnt = len + k.current_weight;
-            if (cnt > k.max_history) cnt = k.max_history;
-            float al = k.current_weight / cnt;
-            if (al > 1.f) al = 1.f;
-            a = make_float4(hr + (cr - hr) * al, hg + (cg - hg) * al, hb + (cb - hb) * al, cnt);
-          }
-        }
-      }
+    Reprojected hst;
+    if (reproject(w, h, prev, k.r, nx, ny, nz, px, py, pz, z, hst, [](float, size_t) {})) {
+      float cnt = hst.len + k.current_weight;
+      if (cnt > k.max_history) cnt = k.max_history;
+      float al = k.current_weight / cnt;
+      if (al > 1.f) al = 1.f;
+      a = make_float4(hst.hr + (cr - hst.hr) * al, hst.hg + (cg - hst.hg) * al, hst.hb + (cb - hst.hb) * al, cnt);
     }
   }
   next[p] = a;
@@ -127,44 +91,15 @@ int vimg_temporal_accumulate(const VimgTemporalFrames* f, const void* d_prev_his
   if (const int rc = check_float("current_weight", a->current_weight, 1.f, false, false)) return rc;
   if (const int rc = check_float("sigma_normal", a->sigma_normal, 0.f, true, false)) return rc;
   if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
-  if (reinterpret_cast<uintptr_t>(d_next_history) % 16)
-    return fail(VIMG_E_INVALID, "temporal: the next history must be 16-byte aligned");
-  Constants k{};
-  if (d_prev_history) {
-    if (reinterpret_cast<uintptr_t>(d_prev_history) % 16)
-      return fail(VIMG_E_INVALID, "temporal: the previous history must be 16-byte aligned");
-    if (!prev_world_to_pixel)
-      return fail(VIMG_E_INVALID, "temporal: a previous history needs its world-to-pixel matrix");
-  }
-  if (prev_world_to_pixel)
-    for (int i = 0; i < 12; ++i) {
-      if (!std::isfinite(prev_world_to_pixel[i]))
-        return fail(VIMG_E_INVALID, "temporal: world-to-pixel entry %d is not finite (%g)", i, double(prev_world_to_pixel[i]));
-      k.m[i] = prev_world_to_pixel[i];
-    }
   const uint32_t w = f->width, h = f->height;
-  const uint64_t hist = vimg_temporal_history_bytes(w, h), frame = uint64_t(12) * w * h;
-  if (d_prev_history && overlaps(d_next_history, hist, d_prev_history, hist))
-    return fail(VIMG_E_INVALID, "temporal: the next history overlaps the previous one");
-  const void* frames[4] = {f->color, f->normal, f->position, f->depth};
-  const char* names[4] = {"color", "normal", "position", "depth"};
-  for (int i = 0; i < 4; ++i)
-    if (overlaps(d_next_history, hist, frames[i], frame))
-      return fail(VIMG_E_INVALID, "temporal: the next history overlaps the %s frame", names[i]);
-  if (d_out_rgb) {      // other lanes gather from prev and read the guides; only the colour frame itself may be the output
-    if (d_prev_history && overlaps(d_out_rgb, frame, d_prev_history, hist))
-      return fail(VIMG_E_INVALID, "temporal: the output overlaps the previous history");
-    if (overlaps(d_out_rgb, frame, d_next_history, hist))
-      return fail(VIMG_E_INVALID, "temporal: the output overlaps the next history");
-    for (int i = 0; i < 4; ++i)
-      if (overlaps(d_out_rgb, frame, frames[i], frame) && !(i == 0 && d_out_rgb == f->color))
-        return fail(VIMG_E_INVALID, i == 0 ? "temporal: the output overlaps the %s frame without being it"
-                                           : "temporal: the output overlaps the %s frame", names[i]);
-  }
+  Constants k{};
+  if (const int rc = check_reprojection(f, d_prev_history, prev_world_to_pixel, d_next_history, vimg_temporal_history_bytes(w, h), {},
+                                        d_out_rgb, {}, k.r))
+    return rc;
   k.max_history = a->max_history;
   k.current_weight = a->current_weight;
-  k.sigma_normal = a->sigma_normal;
-  k.sigma_plane = a->sigma_plane;
+  k.r.sigma_normal = a->sigma_normal;
+  k.r.sigma_plane = a->sigma_plane;
 
   clear_stale_error();
   temporal_accumulate_kernel<<<pixel_grid(w, h), pixel_block(), 0, static_cast<hipStream_t>(stream)>>>(

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi as abi
 from .filter import FRAMES, GUIDES
-from .hip import FrameCall, _Tensors, _checker
+from .hip import FrameCall, _Tensors, _checker, library_params
 
 _lib = abi.varfilter_lib
 _check = _checker(_lib, "vimg_varfilter_last_error")
@@ -23,16 +23,9 @@ FLOATS = ("sigma_luminance", "sigma_normal", "sigma_plane", "albedo_floor", "var
 def params(iterations=None, sigma_luminance=None, sigma_normal=None, sigma_plane=None, albedo_floor=None, variance_floor=None):
     """An abi.VarFilterParams: the library's defaults (vimg_varfilter_defaults; include/vimg_varfilter.h names them)
     with the given values in place of them."""
-    p = abi.VarFilterParams()
-    _lib().vimg_varfilter_defaults(C.byref(p))
-    if iterations is not None:
-        if not 0 <= int(iterations) < 2 ** 32:
-            raise ValueError(f"varfilter: iterations must be 1..12, not {iterations}")
-        p.iterations = int(iterations)
-    for name, v in zip(FLOATS, (sigma_luminance, sigma_normal, sigma_plane, albedo_floor, variance_floor)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return library_params("varfilter", abi.VarFilterParams, _lib().vimg_varfilter_defaults, FLOATS,
+                          zip(FLOATS, (sigma_luminance, sigma_normal, sigma_plane, albedo_floor, variance_floor)),
+                          ("iterations", iterations, "1..12"))
 
 
 def workspace_bytes(width, height):
@@ -50,7 +43,6 @@ def atrous(color, normal, position, depth, albedo=None, variance=None, iteration
     may be ``color`` itself and ``out_variance`` may be ``variance`` itself; ``workspace``: a contiguous, 16-byte
     aligned CUDA tensor of at least workspace_bytes(W, H) bytes (64 per pixel), allocated here when None.  The call
     only enqueues, on ``stream`` or torch's current stream."""
-    import torch
     c = FrameCall("varfilter", color)
     h, w = c.h, c.w
     p = params(iterations, sigma_luminance, sigma_normal, sigma_plane, albedo_floor, variance_floor)
@@ -59,12 +51,7 @@ def atrous(color, normal, position, depth, albedo=None, variance=None, iteration
         t["variance"] = c.take(variance, "varfilter variance", ("float32",), (h, w))
     out = c.output(out, "varfilter", "float32", (h, w, 3))
     out_variance = c.output(out_variance, "varfilter out_variance", "float32", (h, w))
-    if workspace is None:
-        workspace = c.own(torch.empty((workspace_bytes(w, h),), dtype=torch.uint8, device="cuda"))
-    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("varfilter: workspace must be a contiguous CUDA tensor")
-    else:
-        c.use(workspace)
+    workspace = c.workspace(workspace, workspace_bytes(w, h))
     frames = abi.VarFilterFrames(width=w, height=h, **{k: v.data_ptr() for k, v in t.items()})
     with c.launch(stream) as sp:
         _check(_lib().vimg_varfilter_atrous(C.byref(frames), C.byref(p), C.c_void_p(out.data_ptr()),

@@ -18,25 +18,13 @@
 
 #define FRAME_LIB "varfilter"
 #include "../frames/frame_lib.h"
+#include "../frames/guides.h"
 
 namespace vimg_varfilter {
 
 using namespace vimg_frames;
 
-__device__ inline float floored(float a, float floor) { return a > floor ? a : floor; }
-__device__ inline float lum(float x, float y, float z) { return (x * 0.212671f + y * 0.715160f) + z * 0.072169f; }
 __device__ inline float w_of(const float4* plane, size_t p) { return reinterpret_cast<const float*>(plane)[4 * p + 3]; }
-
-// s_n + s_p of the tap q for the pixel p (normal np, position pp, plane_den = (sigma_plane z_p)^2)
-__device__ inline float guide_score(const float4& np, const float4& pp, const float4& nq, const float4& pq, float sigma_normal,
-                                    float plane_den) {
-  const float dn = 1.f - ((np.x * nq.x + np.y * nq.y) + np.z * nq.z);
-  const float s_n = dn < 0.f ? 0.f : dn / sigma_normal;
-  const float ex = pq.x - pp.x, ey = pq.y - pp.y, ez = pq.z - pp.z;
-  const float d = (np.x * ex + np.y * ey) + np.z * ez;
-  const float s_p = (d * d) / plane_den;
-  return s_n + s_p;
-}
 
 __global__ __launch_bounds__(WAVE_X * ROWS) void varfilter_pack_kernel(
     uint32_t w, uint32_t h, const float* __restrict__ color, const float* __restrict__ normal,
@@ -267,15 +255,9 @@ int vimg_varfilter_atrous(const VimgVarFilterFrames* f, const VimgVarFilterParam
   if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
   if (const int rc = check_float("albedo_floor", a->albedo_floor, 0.f, true, false)) return rc;
   if (const int rc = check_float("variance_floor", a->variance_floor, 0.f, true, false)) return rc;
-  if (!d_workspace) return fail(VIMG_E_INVALID, "varfilter: null workspace");
-  const uint64_t need = vimg_varfilter_workspace(f->width, f->height);
-  if (workspace_bytes < need)
-    return fail(VIMG_E_INVALID, "varfilter: the workspace has %llu bytes, %u x %u needs %llu",
-                static_cast<unsigned long long>(workspace_bytes), f->width, f->height, static_cast<unsigned long long>(need));
-  if (reinterpret_cast<uintptr_t>(d_workspace) % 16)
-    return fail(VIMG_E_INVALID, "varfilter: the workspace must be 16-byte aligned");
-
   const uint32_t w = f->width, h = f->height;
+  if (const int rc = check_workspace(d_workspace, workspace_bytes, vimg_varfilter_workspace(w, h), w, h)) return rc;
+
   const size_t n = size_t(w) * h;
   float4* base = static_cast<float4*>(d_workspace);
   float4 *c0 = base, *c1 = base + n, *g0 = base + 2 * n, *g1 = base + 3 * n;

@@ -11,7 +11,7 @@ There is no CPU fallback.
 import ctypes as C
 
 from . import _abi as abi
-from .hip import FrameCall, _checker
+from .hip import FrameCall, _checker, library_params
 from .temporal import FRAMES, History, history_bytes, world_to_pixel
 
 PARAMS = ("max_history", "sigma_normal", "sigma_plane")
@@ -26,12 +26,11 @@ _check = _checker(_lib, "vimg_wtemporal_last_error")
 def wtemporal_params(max_history=None, sigma_normal=None, sigma_plane=None):
     """An abi.WTemporalParams: the library's defaults (vimg_wtemporal_defaults; include/vimg_wtemporal.h names them)
     with the given values in place of them."""
-    p = abi.WTemporalParams()
-    _lib().vimg_wtemporal_defaults(C.byref(p))
-    for name, v in zip(PARAMS, (max_history, sigma_normal, sigma_plane)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return _params(zip(PARAMS, (max_history, sigma_normal, sigma_plane)))
+
+
+def _params(given):
+    return library_params("wtemporal", abi.WTemporalParams, _lib().vimg_wtemporal_defaults, PARAMS, given)
 
 
 def sparse_weights(count, code, batches=None, fill_weight=FILL_WEIGHT):
@@ -68,21 +67,11 @@ def accumulate(color, normal, position, depth, weight, history=None, world_to_pi
     default the library's (include/vimg_wtemporal.h).  The call only enqueues, on ``stream`` or torch's current
     stream."""
     c = FrameCall("wtemporal", color)
-    unknown = sorted(set(params) - set(PARAMS))
-    if unknown:
-        raise TypeError(f"wtemporal: unknown parameters {unknown}; expected some of {PARAMS}")
     h, w = c.h, c.w
-    p = wtemporal_params(**params)
+    p = _params(params.items())
     t = c.frames(FRAMES, (color, normal, position, depth))
     t["weight"] = c.take(weight, "wtemporal weight", ("float32",), (h, w))
-    prev = matrix = None
-    if history is not None:
-        if not isinstance(history, History):
-            raise ValueError("wtemporal: history must be a temporal.History")
-        if history.world_to_pixel is None:
-            raise ValueError("wtemporal: the history does not know its world_to_pixel matrix")
-        prev = c.take(history.tensor, "wtemporal history", ("float32",), (3, h, w, 4), aligned=True)
-        matrix = (abi.f32 * 12)(*history.world_to_pixel.tolist())
+    prev, matrix = c.history(history, History)
     next_history = c.output(next_history, "wtemporal next_history", "float32", (3, h, w, 4), aligned=True)
     if out is not None:
         c.output(out, "wtemporal", "float32", (h, w, 3))
