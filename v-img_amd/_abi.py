@@ -1,5 +1,6 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
-include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h and include/vimg_wtemporal.h.
+include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h
+and include/vimg_antilag.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -455,6 +456,31 @@ WTEMPORAL_SYMBOLS = {
 }
 
 
+class AntilagFrames(_Sized, C.Structure):
+    """VimgAntilagFrames (include/vimg_antilag.h): VimgTemporalFrames, the CURRENT picture a history is compared with."""
+    _fields_ = TemporalFrames._fields_
+
+
+class AntilagParams(_Sized, C.Structure):
+    """VimgAntilagParams (include/vimg_antilag.h); vimg_antilag_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("radius", u32), ("t_low", f32), ("t_high", f32), ("min_matches", f32),
+                ("sigma_normal", f32), ("sigma_plane", f32)]
+
+
+ANTILAG_WORKSPACE_PER_PIXEL = 8
+ANTILAG_MAX_RADIUS = 8
+
+# the list of symbols include/vimg_antilag.h declares: libvimg_antilag.so, which shortens a history (the first three
+# planes: TEMPORAL_HISTORY_PER_PIXEL) where the current picture disagrees with it
+ANTILAG_SYMBOLS = {
+    "vimg_antilag_defaults": (None, [C.POINTER(AntilagParams)]),
+    "vimg_antilag_workspace_bytes": (C.c_uint64, [u32, u32]),
+    "vimg_antilag_rescale": (C.c_int, [C.POINTER(AntilagFrames), Pf32, C.c_void_p, C.POINTER(AntilagParams), C.c_void_p,
+                                       C.c_uint64, C.c_void_p, C.c_void_p]),
+    "vimg_antilag_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -475,6 +501,7 @@ _LIBRARIES = {
     "moments": ("libvimg_moments.so", (MOMENTS_SYMBOLS,), "moments", "; there is no CPU fallback for temporal accumulation", True),
     "infill": ("libvimg_infill.so", (INFILL_SYMBOLS,), "infill", "; there is no CPU fallback for the reconstruction", True),
     "wtemporal": ("libvimg_wtemporal.so", (WTEMPORAL_SYMBOLS,), "wtemporal", "; there is no CPU fallback for temporal accumulation", True),
+    "antilag": ("libvimg_antilag.so", (ANTILAG_SYMBOLS,), "antilag", "; there is no CPU fallback for the history rescaling", True),
 }
 _loaded = {}
 
@@ -536,3 +563,8 @@ def infill_lib():
 def wtemporal_lib():
     """The temporal accumulation library with per-pixel weights (include/vimg_wtemporal.h)."""
     return _load("wtemporal")
+
+
+def antilag_lib():
+    """The library that shortens a history where the picture has changed (include/vimg_antilag.h)."""
+    return _load("antilag")

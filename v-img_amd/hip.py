@@ -362,7 +362,7 @@ class DeviceScene:
                           stream=stream, **filter_kw)
 
     def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
-                         fill_weight=None, **temporal_kw):
+                         fill_weight=None, antilag=False, **temporal_kw):
         """A preview that survives a moving camera (vimg_amd.temporal.TemporalPreview, include/vimg_temporal.h): its
         ``frame()`` renders ``samples`` more samples of the scene as it now stands and returns the [H, W, 3] picture -
         after set_camera or an edit blended with the last picture reprojected into the new camera, while nothing
@@ -374,10 +374,14 @@ class DeviceScene:
         too and ``scale_sigma_color`` is refused.  ``sparse`` (a stride 2..4): a frame samples one pixel in sparse^2,
         on a lattice that cycles, fills the others from the guides (vimg_amd.infill) and accumulates with per-pixel
         weights (vimg_amd.wtemporal, include/vimg_wtemporal.h) - a filled pixel, worth ``fill_weight`` samples, takes
-        its reprojected history where it has one; not with ``variance_guided``.  Whole frames only."""
+        its reprojected history where it has one; not with ``variance_guided``.  ``antilag`` (True, or a dict of
+        antilag.rescale's parameters): on the frame after set_camera or an edit, the history's lengths are first cut
+        where the new picture disagrees with it by more than its noise (vimg_amd.antilag, include/vimg_antilag.h), so
+        a relit region starts over and the rest keeps its history.  Whole frames only."""
         from . import temporal
         return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
-                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, **temporal_kw)
+                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
+                                        **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,

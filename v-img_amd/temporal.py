@@ -127,11 +127,24 @@ class TemporalPreview:
     frames of a standing camera the accumulator is bit for bit a Progressive after one render(samples).  ``history``
     stays a History; ``variance_guided`` is refused with it (the moments history is not weighted per pixel).
 
-    Limits: history from before a geometry or material edit is reprojected all the same and fades at 1 / max_history
-    per frame (``reset()`` drops it); a thin lens is treated as its pinhole; see include/vimg_temporal.h."""
+    ``antilag`` (True: the library's defaults; a dict: antilag.rescale's parameters): on the frame()
+    on which the scene had changed and a history freezes, that frozen history's lengths are rescaled once
+    (vimg_amd.antilag, include/vimg_antilag.h) - after this camera's first increment is rendered (with ``sparse``:
+    rendered and filled) and before it is accumulated, against that increment and under the current camera's matrix:
+    where the new picture disagrees with the history by more than its noise the lengths are cut, to 0 where it clearly
+    does, and accumulate's taps there find a short history or none; everywhere else they find what they found before.
+    ``last_scale`` is the [H, W] scale frame of the last such call, in the frozen history's pixel coordinates (None
+    before the first).  Standing frames make no call and the accumulator stays bit for bit a Progressive.  With
+    ``variance_guided`` only plane A's lengths are rescaled, NOT the moments of plane M: a scaled length below
+    min_history makes the variance NaN there, which the filter estimates from the pixel's surroundings.
+
+    Limits: without ``antilag``, history from before a geometry or material edit is reprojected all the same and
+    fades at 1 / max_history per frame (``reset()`` drops all of it); with it, a change smaller than the noise of one
+    increment over the test's window is not seen and fades as before; a thin lens is treated as its pinhole; see
+    include/vimg_temporal.h."""
 
     def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
-                 variance_guided=False, sparse=None, fill_weight=None, **temporal_kw):
+                 variance_guided=False, sparse=None, fill_weight=None, antilag=False, **temporal_kw):
         import torch
         from . import filter as flt
         if params.tile_world != 1:
@@ -179,6 +192,13 @@ class TemporalPreview:
             self._workspace = torch.empty((flt.atrous_workspace_bytes(w, h),), dtype=torch.uint8, device="cuda") if denoise else None
             self._sigma_color = float(self.filter_kw.pop("sigma_color", None) or flt.atrous_params().sigma_color) if denoise else None
         self._max_history = float(temporal_params(max_history=temporal_kw.get("max_history")).max_history)
+        self.antilag, self.last_scale = None, None
+        if antilag is not False and antilag is not None:
+            from . import antilag as lag
+            self.antilag = {} if antilag is True else dict(antilag)
+            lag._params(self.antilag.get("radius"), ((k, v) for k, v in self.antilag.items() if k != "radius"))      # (refuses an unknown name now)
+            self._antilag_workspace = torch.empty((lag.workspace_bytes(w, h),), dtype=torch.uint8, device="cuda")
+            self._scale = torch.empty((h, w), dtype=torch.float32, device="cuda")
         self._guides = GuideCache(dev)
         self.reset()
 
@@ -198,16 +218,21 @@ class TemporalPreview:
         tensor (``out`` when given)."""
         from . import filter as flt
         dev, acc = self._dev, self.acc
+        froze = False
         if self._generation != dev.generation:
             acc.reset(stream=stream)
             if self.history is not None:           # the last frame's history freezes; the other buffer is written from now on
-                self._frozen, self._write = self.history, 1 - self._write
+                self._frozen, self._write, froze = self.history, 1 - self._write, True
             self._generation, self._k = dev.generation, 0
         g = self._guides.get(acc.params, self.feature_samples, self._features, stream=stream)
         if self.sparse:
             mean = self._render_sparse(g, stream)
         else:
             mean = acc.render(self.samples, stream=stream)
+        if froze and self.antilag is not None:     # once per freeze: the frozen history is never written otherwise
+            from . import antilag as lag
+            self.last_scale = lag.rescale(mean, g["normal"], g["position"], g["depth"], self._frozen, world_to_pixel(dev.camera),
+                                          out_scale=self._scale, workspace=self._antilag_workspace, stream=stream, **self.antilag)[1]
         self._k += 1
         target = mean if out is None else out
         if self.variance_guided:
