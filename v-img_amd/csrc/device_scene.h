@@ -196,6 +196,13 @@ struct RenderArgs {
   // start of the workgroup's dynamic LDS (a multiple of 16) and its rows
   uint32_t lds_tables;
   uint32_t tab_off[TAB_COUNT], tab_rows[TAB_COUNT];
+  // CU scheduler: the leaf records once more for the rays of major axis kz == 0 and kz == 1, triangles' vertices
+  // permuted as the watertight test permutes them, staged behind the tables when the launch starts (render_cu_kernel.h:
+  // stage_leaf_perm; the leaf table itself serves kz == 2).  leaf_perm: 1 = a build that folds PF_LEAF_PERM may run
+  // (both copies staged, or a scene without triangles, which needs none).  Copy k starts leaf_perm_off + k *
+  // leaf_perm_stride bytes behind the start of the leaf table; a scene without triangles has 0 and 0: every "copy"
+  // is the leaf table, and nothing more is laid out
+  uint32_t leaf_perm, leaf_perm_off, leaf_perm_stride;
 };
 
 struct DeviceStats {

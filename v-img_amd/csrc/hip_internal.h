@@ -107,7 +107,7 @@ struct LaunchCfg {
   const char* error;   // nullptr, or why no launch can be made of the scene's options (make_launch_cu): VIMG_E_INVALID
   RenderArgs args;
   uint32_t grid, lds_bytes;
-  uint32_t table_bytes;   // CU scheduler: the part of lds_bytes that holds the shading tables (the end of the layout)
+  uint32_t table_bytes;   // CU scheduler: the part of lds_bytes that holds the shading tables and the permuted leaf copies (the end of the layout)
   int sched;     // VIMG_SCHED_CU or VIMG_SCHED_LANE
   int wps;       // register-budget build (waves per SIMD of __launch_bounds__)
   bool deep;     // CU scheduler: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)

@@ -199,6 +199,25 @@ LaunchCfg cu_launch_with(const VimgDeviceScene* s, const VimgRenderParams* p, in
       a.lds_tables |= gr.bit;
     }
   }
+  // The permuted copies of the leaf records (plain_build.h: PF_LEAF_PERM; render_cu_kernel.h: stage_leaf_perm) are one
+  // more group by the same rules: behind the table groups, in the room pool and tables leave, both copies or none,
+  // never at the price of a slot or of a table group, and only for a launch a PLAIN build serves.  A scene without
+  // triangles needs none (the sphere test permutes nothing): its launch is ready with a layout that is the parent's.
+  a.leaf_perm = 0u, a.leaf_perm_off = 0u, a.leaf_perm_stride = 0u;
+  if ((PLAIN_FOLD & PF_LEAF_PERM) && a.lds_leaf != 0u &&
+      plain_build_serves(plain_launch_of(true, s->textured, c.deep, c.cu_waves, false, s->force_general, a))) {
+    const uint32_t leaf_off = node_bytes + stack_bytes + cu_pool_bytes(slots, nw);   // (CU_STAGE_LOCALS: lds_leaf)
+    const uint64_t used = uint64_t(c.lds_bytes) + 64u;
+    const uint32_t stride = a.lds_leaf * 48u;
+    if (s->num_tris == 0u) {
+      a.leaf_perm = 1u;
+    } else if (used + 2u * uint64_t(stride) <= share) {
+      a.leaf_perm = 1u;
+      a.leaf_perm_off = c.lds_bytes - leaf_off, a.leaf_perm_stride = stride;
+      c.lds_bytes += 2u * stride;
+      c.table_bytes += 2u * stride;
+    }
+  }
   int per_cu = 0;
   // (asked of the build that will run, as far as the policy knows the launch: an item list or statistics come later
   // and take the general or the statistics build, of the same workgroup shape)
@@ -267,16 +286,18 @@ const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
 // (enqueue_render asks after it has set the item list and the statistics flag) against plain_build.h's list.
 bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
   return plain_build_serves(plain_launch_of(c.sched == VIMG_SCHED_CU, s->textured, c.deep, c.cu_waves, stats, s->force_general, c.args)) &&
-         plain_tables_serve(c.args.lds_tables);
+         plain_tables_serve(c.args.lds_tables) && plain_leaf_perm_serves(c.args.leaf_perm);
 }
 
 // A launch whose arguments, now complete, send it to the general or the statistics build reads no table from LDS:
-// their room goes back (they are the last thing in the layout) and RenderArgs::lds_tables says what is staged
+// and no permuted leaf copy: their room goes back (they are the last things in the layout) and RenderArgs::lds_tables
+// and ::leaf_perm say what is staged
 void drop_unread_tables(const VimgDeviceScene* s, LaunchCfg& c, bool stats) {
-  if (c.sched != VIMG_SCHED_CU || c.args.lds_tables == 0u || plain_launch_serves(s, c, stats)) return;
+  if (c.sched != VIMG_SCHED_CU || (c.args.lds_tables == 0u && c.args.leaf_perm == 0u) || plain_launch_serves(s, c, stats)) return;
   c.lds_bytes -= c.table_bytes;
   c.table_bytes = 0u;
   c.args.lds_tables = 0u;
+  c.args.leaf_perm = 0u, c.args.leaf_perm_off = 0u, c.args.leaf_perm_stride = 0u;
 }
 
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {

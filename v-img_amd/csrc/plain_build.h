@@ -30,12 +30,16 @@ enum : uint32_t {
   PF_TAB_MAT = 128u,    // materials: materials, dmaterials.  NOT folded by default (it costs the PLAIN
                         // kernels their 128th register; a sweep bit, like every other, through -DVIMG_PLAIN_FOLD)
   PF_TABLES = PF_TAB_HIT | PF_TAB_MAT,   // (the emitter tables stay in global memory: DESIGN.md 4.4)
+  // The leaf records once more per major axis of a ray (kz == 0, kz == 1; the leaf table itself is kz == 2), their
+  // triangles' vertices permuted as the watertight test permutes them: a lane reads the copy of its ray's axis and
+  // the test permutes nothing.  A scene without triangles needs no copy
+  PF_LEAF_PERM = 256u,
 };
 // What the PLAIN builds fold (DESIGN.md 4.4 has the times of the candidates)
 #ifdef VIMG_PLAIN_FOLD   // (sweeps: -DVIMG_PLAIN_FOLD=<mask> on the units that include this header)
 constexpr uint32_t PLAIN_FOLD = VIMG_PLAIN_FOLD;
 #else
-constexpr uint32_t PLAIN_FOLD = PF_INTEGRATOR | PF_CLASSES | PF_LEAF_LDS | PF_SINGLE | PF_ITEMS | PF_FLEX | PF_TAB_HIT;
+constexpr uint32_t PLAIN_FOLD = PF_INTEGRATOR | PF_CLASSES | PF_LEAF_LDS | PF_SINGLE | PF_ITEMS | PF_FLEX | PF_TAB_HIT | PF_LEAF_PERM;
 #endif
 
 // what the predicate needs to know of a launch (plain_launch_of below fills it)
@@ -69,6 +73,13 @@ constexpr bool plain_build_serves(const PlainLaunch& l, uint32_t fold = PLAIN_FO
 // serves only launches that staged it; a launch whose tables do not fit runs the general build.
 constexpr bool plain_tables_serve(uint32_t staged, uint32_t fold = PLAIN_FOLD) {
   return (staged & fold & PF_TABLES) == (fold & PF_TABLES);
+}
+
+// The permuted leaf copies likewise: `ready` is the launch's RenderArgs::leaf_perm (the policy staged the two copies,
+// or the scene has no triangle and needs none).  A build that reads a lane's leaves from the copy of its ray's axis
+// serves only launches where that copy is there; a launch whose copies do not fit runs the general build.
+constexpr bool plain_leaf_perm_serves(uint32_t ready, uint32_t fold = PLAIN_FOLD) {
+  return !(fold & PF_LEAF_PERM) || ready != 0u;
 }
 
 // The description of a launch from what the policy knows of it: the kernel family and the build class, whether

@@ -164,6 +164,7 @@ template <uint32_t PLAIN> VD bool opt_has_items(const RenderArgs& A) {
 template <uint32_t PLAIN> VD uint32_t opt_flex(const RenderArgs& A) {   // (without the early bit: EARLY is a parameter of its own)
   if constexpr (PLAIN & PF_FLEX) return PLAIN_FLEX_DEFAULT; else return A.cu_flex;
 }
+template <uint32_t PLAIN> constexpr bool opt_leaf_perm = (PLAIN & PF_LEAF_PERM) != 0u;   // (only ever a constant: no general build reads the copies)
 // (the table groups PF_TAB_* are folded through the type of the scene the vertex stages read: LdsTables<PLAIN & PF_TABLES>)
 
 // The workgroup's copies of the launch-constant shading tables (device_scene.h: TAB_*), made once when the launch
@@ -191,6 +192,27 @@ VD void stage_tables(const DScene& g, const RenderArgs& A, VIMG_LDS unsigned cha
   if (A.lds_tables & PF_TAB_MAT) {
     stage_rows(lds_raw, A, TAB_MATERIALS, g.materials);
     stage_rows(lds_raw, A, TAB_DMATERIALS, g.dmaterials);
+  }
+}
+// The workgroup's leaf records once more for the rays of major axis kz == 0 and kz == 1 (the leaf table itself serves
+// kz == 2, where permute is the identity): record (p0.xyz, p1.x)(p1.yz, p2.xy)(p2.z, prim, kind, class) with p0, p1, p2
+// each run through permute(., k); a sphere's record word for word.  Made when the launch starts, from the resident
+// records as they stand then, like the tables above.  A scene without triangles has stride 0 and stages nothing.
+VD void stage_leaf_perm(const DScene& g, const RenderArgs& A, VIMG_LDS v4f* lds_leaf) {
+  if (A.leaf_perm_stride == 0u) return;
+  const uint32_t n = A.lds_leaf;
+  for (uint32_t i = threadIdx.x; i < 2u * n; i += blockDim.x) {
+    const int k = i < n ? 0 : 1;
+    const uint32_t r = i - (k ? n : 0u);
+    gptr<v4f> src = reinterpret_cast<gptr<v4f>>(g.leaf_prims) + r * 3u;
+    v4f a = src[0], b = src[1], c = src[2];
+    if (__float_as_uint(c.z) == 0u) {   // kind: a triangle
+      const f3 p0 = permute(f3{a.x, a.y, a.z}, k), p1 = permute(f3{a.w, b.x, b.y}, k), p2 = permute(f3{b.z, b.w, c.x}, k);
+      a = v4f{p0.x, p0.y, p0.z, p1.x}, b = v4f{p1.y, p1.z, p2.x, p2.y}, c.x = p2.z;
+    }
+    VIMG_LDS v4f* dst = reinterpret_cast<VIMG_LDS v4f*>(reinterpret_cast<VIMG_LDS unsigned char*>(lds_leaf) + A.leaf_perm_off +
+                                                        uint32_t(k) * A.leaf_perm_stride) + r * 3u;
+    dst[0] = a, dst[1] = b, dst[2] = c;
   }
 }
 
@@ -1029,6 +1051,10 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
   TravRay ray{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 1.f}, 0.0001f, VIMG_INF};
   f3 w_inv{1.f, 1.f, 1.f};
   TriRayConst rc{0.f, 0.f, 1.f, 2};
+  // PF_LEAF_PERM: the origin permuted for the ray's major axis, and where the leaf copy of that axis starts (bytes
+  // behind the leaf table; kz == 2 reads the table itself)
+  [[maybe_unused]] f3 w_o_perm{0.f, 0.f, 0.f};
+  [[maybe_unused]] uint32_t w_leaf_off = 0u;
   float w_dir_len2 = 1.f;
   HitRec rec;
   rec.prim = 0xffffffffu, rec.kind = 0;
@@ -1091,6 +1117,10 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
         w_inv = f3{1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z};
         w_exact = (ray.d.x == 0.f) || (ray.d.y == 0.f) || (ray.d.z == 0.f);
         rc = tri_ray_const(ray.d, w_inv);
+        if constexpr (opt_leaf_perm<PLAIN>) {
+          w_o_perm = permute(ray.o, rc.kz);
+          w_leaf_off = rc.kz == 2 ? 0u : A.leaf_perm_off + uint32_t(rc.kz) * A.leaf_perm_stride;
+        }
         w_dir_len2 = dot(ray.d, ray.d);
         const float root = slab(load3k(g.root_min), load3k(g.root_max), ray.o, w_inv, ray.min_t, ray.max_t);
         cur = is_inf(root) ? REF_DONE : g.root_ref;
@@ -1167,10 +1197,16 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
         const uint32_t first = ref_index(cur), count = ref_count(cur);
         c_leaf += stat_inc;
         bool stop = false;
+        // (PF_LEAF_PERM: the lane's copy of the leaf records, its offset added once per leaf)
+        [[maybe_unused]] const VIMG_LDS v4f* leaf0 =
+            reinterpret_cast<const VIMG_LDS v4f*>(reinterpret_cast<const VIMG_LDS unsigned char*>(lds_leaf) + w_leaf_off) + first * 3u;
         for (uint32_t i = 0; i < count && !stop; ++i) {
           gptr<DLeafPrim> lp = g.leaf_prims + (first + i);
           v4f a, b, cc;
-          if (leaf_in_lds) {
+          if constexpr (opt_leaf_perm<PLAIN>) {
+            const VIMG_LDS v4f* ll = leaf0 + i * 3u;
+            a = ll[0], b = ll[1], cc = ll[2];
+          } else if (leaf_in_lds) {
             const VIMG_LDS v4f* ll = lds_leaf + (first + i) * 3u;
             a = ll[0], b = ll[1], cc = ll[2];
           } else {
@@ -1183,7 +1219,10 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
           bool hit = false;
           float t = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f, idet = 0.f;
           if (kind == 0) {
-            hit = tri_test_flat(f3{a.x, a.y, a.z}, f3{a.w, b.x, b.y}, f3{b.z, b.w, c0}, ray, rc, t, e0, e1, e2, idet);
+            if constexpr (opt_leaf_perm<PLAIN>)
+              hit = tri_test_permuted(f3{a.x, a.y, a.z}, f3{a.w, b.x, b.y}, f3{b.z, b.w, c0}, w_o_perm, ray, rc, t, e0, e1, e2, idet);
+            else
+              hit = tri_test_flat(f3{a.x, a.y, a.z}, f3{a.w, b.x, b.y}, f3{b.z, b.w, c0}, ray, rc, t, e0, e1, e2, idet);
           } else if (kind == 1) {
             c_sphere += stat_inc;
             hit = sphere_test(f3{a.x, a.y, a.z}, a.w, ray, w_dir_len2, t);
@@ -1283,6 +1322,7 @@ render_cu_kernel(const CuKArgs ka) {
     for (uint32_t i = lane; i < sizeof(CuWaveRec) / 4u; i += 64u) reinterpret_cast<VIMG_LDS uint32_t*>(wrec)[i] = 0u;
     for (uint32_t i = threadIdx.x; i < A.lds_leaf * 3u; i += blockDim.x)
       lds_leaf[i] = reinterpret_cast<gptr<v4f>>(g.leaf_prims)[i];
+    if constexpr (opt_leaf_perm<PLAIN>) stage_leaf_perm(g, A, lds_leaf);   // (the builds that read a lane's leaves from the copy of its ray's axis)
     if constexpr ((PLAIN & PF_TABLES) != 0u) stage_tables(g, A, (VIMG_LDS unsigned char*)lds_raw);   // (the builds that read them there)
     // every slot starts "fresh" in the finisher queue: it needs a pixel
     for (uint32_t s = threadIdx.x; s < P; s += blockDim.x) {

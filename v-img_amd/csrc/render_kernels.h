@@ -431,11 +431,22 @@ VD float diff_of_products_double(float a, float b, float c, float d) {
 // into one predicate (one exec-mask region for the hit instead of one per early return: the primitive
 // loop of the walk is dominated by mask bookkeeping otherwise).  Comparisons keep the reference's form, so NaN operands take the same
 // way out (every ordered comparison false -> accepted, as in the reference).
-VD bool tri_test_flat(f3 p0, f3 p1, f3 p2, const TravRay& ray, const TriRayConst& rc, float& t_out,
+//
+// Where the vertices come from is a compile-time choice of the accessor tri_vertex<PERMUTED>: false = a vertex and
+// the ray's origin as the scene has them, permuted here; true = both permuted already (a leaf copy made for the ray's
+// kz and the origin permuted at ray set-up: render_cu_kernel.h, PF_LEAF_PERM).  Permutation and subtraction act by
+// component, so permute(p - o, kz) and permute(p, kz) - permute(o, kz) are the same three subtractions of the same
+// operands: one text of the test, the same arithmetic in the same order, the same bits.
+template <bool PERMUTED>
+VD f3 tri_vertex(f3 p, f3 o, int kz) {
+  if constexpr (PERMUTED) return p - o; else return permute(p - o, kz);
+}
+template <bool PERMUTED>
+VD bool tri_test_body(f3 p0, f3 p1, f3 p2, f3 o, const TravRay& ray, const TriRayConst& rc, float& t_out,
                       float& e0o, float& e1o, float& e2o, float& inv_det_o) {
-  f3 p0t = permute(p0 - ray.o, rc.kz);
-  f3 p1t = permute(p1 - ray.o, rc.kz);
-  f3 p2t = permute(p2 - ray.o, rc.kz);
+  f3 p0t = tri_vertex<PERMUTED>(p0, o, rc.kz);
+  f3 p1t = tri_vertex<PERMUTED>(p1, o, rc.kz);
+  f3 p2t = tri_vertex<PERMUTED>(p2, o, rc.kz);
   p0t.x += rc.sx * p0t.z;
   p0t.y += rc.sy * p0t.z;
   p1t.x += rc.sx * p1t.z;
@@ -463,6 +474,15 @@ VD bool tri_test_flat(f3 p0, f3 p1, f3 p2, const TravRay& ray, const TriRayConst
     e0o = e0, e1o = e1, e2o = e2, inv_det_o = inv_det;
   }
   return hit;
+}
+VD bool tri_test_flat(f3 p0, f3 p1, f3 p2, const TravRay& ray, const TriRayConst& rc, float& t_out,
+                      float& e0o, float& e1o, float& e2o, float& inv_det_o) {
+  return tri_test_body<false>(p0, p1, p2, ray.o, ray, rc, t_out, e0o, e1o, e2o, inv_det_o);
+}
+// ... with p0, p1, p2 from the leaf copy of rc.kz and `o_perm` = permute(ray.o, rc.kz)
+VD bool tri_test_permuted(f3 p0, f3 p1, f3 p2, f3 o_perm, const TravRay& ray, const TriRayConst& rc, float& t_out,
+                          float& e0o, float& e1o, float& e2o, float& inv_det_o) {
+  return tri_test_body<true>(p0, p1, p2, o_perm, ray, rc, t_out, e0o, e1o, e2o, inv_det_o);
 }
 // Sphere::sphere_hit_template + solveQuadratic: reference include/geometry/sphere.h:13-100.
 // `q` is a double there (unqualified sqrt) — kept, FP64 is half rate on this chip.
