@@ -1,6 +1,6 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
-include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h
-and include/vimg_antilag.h.
+include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h,
+include/vimg_antilag.h and include/vimg_motion.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -481,6 +481,30 @@ ANTILAG_SYMBOLS = {
 }
 
 
+class MotionFrames(_Sized, C.Structure):
+    """VimgMotionFrames (include/vimg_motion.h): the position frame and the pixel-centre hits and rays, DEVICE pointers."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("position", C.c_void_p),
+                ("hits", C.c_void_p), ("rays", C.c_void_p)]
+
+
+class MotionGeometry(_Sized, C.Structure):
+    """VimgMotionGeometry (include/vimg_motion.h): the counts and the DEVICE tables; an old / new pair is both set or both
+    None (that table did not move)."""
+    _fields_ = [("struct_size", u32), ("num_prims", u32), ("num_tris", u32), ("num_vertices", u32), ("num_spheres", u32),
+                ("reserved", u32), ("prims", C.c_void_p), ("tri_vertices", C.c_void_p), ("old_vertices", C.c_void_p),
+                ("new_vertices", C.c_void_p), ("old_spheres", C.c_void_p), ("new_spheres", C.c_void_p)]
+
+
+MOTION_STATIC, MOTION_TRIANGLE, MOTION_SPHERE, MOTION_OUT_OF_RANGE = 0, 1, 2, 3
+
+# the list of symbols include/vimg_motion.h declares: libvimg_motion.so, the previous-world positions of moved geometry
+MOTION_SYMBOLS = {
+    "vimg_motion_previous_position": (C.c_int, [C.POINTER(MotionFrames), C.POINTER(MotionGeometry), C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "vimg_motion_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -503,14 +527,20 @@ _LIBRARIES = {
     "wtemporal": ("libvimg_wtemporal.so", (WTEMPORAL_SYMBOLS,), "wtemporal", "; there is no CPU fallback for temporal accumulation", True),
     "antilag": ("libvimg_antilag.so", (ANTILAG_SYMBOLS,), "antilag", "; there is no CPU fallback for the history rescaling", True),
 }
+# the libraries that came after those nine, in the same shape: _load looks here too.  (_LIBRARIES is a closed list that
+# earlier ABI tests name key by key; a next library goes here.)
+_LATER_LIBRARIES = {
+    "motion": ("libvimg_motion.so", (MOTION_SYMBOLS,), "motion", "; there is no CPU fallback for the previous-world positions", True),
+}
 _loaded = {}
 
 
 def _load(name, path=None):
-    """The library ``name`` of _LIBRARIES, loaded and bound once.  A missing library raises: there is no fallback."""
+    """The library ``name`` of _LIBRARIES or _LATER_LIBRARIES, loaded and bound once.  A missing library raises: there is
+    no fallback."""
     lib = _loaded.get(name)
     if lib is None:
-        file, tables, target, tail, torch_first = _LIBRARIES[name]
+        file, tables, target, tail, torch_first = _LIBRARIES[name] if name in _LIBRARIES else _LATER_LIBRARIES[name]
         path = path or os.path.join(LIB_DIR, file)
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: run `make {target}` (or __graft_entry__.build()){tail}")
@@ -568,3 +598,8 @@ def wtemporal_lib():
 def antilag_lib():
     """The library that shortens a history where the picture has changed (include/vimg_antilag.h)."""
     return _load("antilag")
+
+
+def motion_lib():
+    """The library that writes the previous-world positions of moved geometry (include/vimg_motion.h)."""
+    return _load("motion")

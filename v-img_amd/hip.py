@@ -291,6 +291,9 @@ class DeviceScene:
                              if v.textures[i].type == abi.TEX_IMAGE}
         self.camera = abi.Camera.from_buffer_copy(v.camera)      # the camera of the next launch (set_camera replaces it)
         self.generation = 0      # counts the edits of the resident scene: what a cached feature frame was rendered from
+        # the vertex and sphere tables update_geometry / update_materials were last given, as device tensors (None: not
+        # since the upload).  A new tensor object per call, never written in place: a held reference is a snapshot
+        self.vertices_given, self.spheres_given = None, None
 
     @property
     def bytes(self):
@@ -362,7 +365,7 @@ class DeviceScene:
                           stream=stream, **filter_kw)
 
     def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
-                         fill_weight=None, antilag=False, **temporal_kw):
+                         fill_weight=None, antilag=False, motion=None, **temporal_kw):
         """A preview that survives a moving camera (vimg_amd.temporal.TemporalPreview, include/vimg_temporal.h): its
         ``frame()`` renders ``samples`` more samples of the scene as it now stands and returns the [H, W, 3] picture -
         after set_camera or an edit blended with the last picture reprojected into the new camera, while nothing
@@ -377,11 +380,14 @@ class DeviceScene:
         its reprojected history where it has one; not with ``variance_guided``.  ``antilag`` (True, or a dict of
         antilag.rescale's parameters): on the frame after set_camera or an edit, the history's lengths are first cut
         where the new picture disagrees with it by more than its noise (vimg_amd.antilag, include/vimg_antilag.h), so
-        a relit region starts over and the rest keeps its history.  Whole frames only."""
+        a relit region starts over and the rest keeps its history.  ``motion`` (the HostScene this scene was uploaded
+        from, its positions the resident ones): after update_geometry the history is looked up where each pixel's
+        surface point WAS (vimg_amd.motion, include/vimg_motion.h), so a moved object keeps its samples.  Whole frames
+        only."""
         from . import temporal
         return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
                                         variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
-                                        **temporal_kw)
+                                        motion=motion, **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,
@@ -460,6 +466,7 @@ class DeviceScene:
         scene is the upload of the host scene edited the same way; progressive accumulators must be reset."""
         upd = abi.GeometryUpdate()
         c, keep = _Tensors(), []     # the device tables (copies of numpy ones, the caller's tensors), the ctypes tables
+        given = {}                   # the position tables of this call, for vertices_given / spheres_given
 
         def table(a, rows, cols, what):
             return _ptr(c.take(a, what, ("float32",), (rows, cols)))
@@ -467,11 +474,16 @@ class DeviceScene:
         for name, a, rows, cols in (("vertices", vertices, self.num_vertices, 3), ("normals", normals, self.num_vertices, 3),
                                     ("spheres", spheres, self.num_spheres, 4)):
             if a is not None:
-                setattr(upd, name, table(a, rows, cols, name))
+                t = c.take(a, name, ("float32",), (rows, cols))
+                setattr(upd, name, _ptr(t))
+                if name != "normals":      # the uploaded copy of a numpy table, a clone of a caller's tensor
+                    given[name] = t if isinstance(a, np.ndarray) else t.clone()
         self._fill_material_update(upd, table, keep, materials, textures, lights, background, images)
         self.generation += 1
         with c.launch(stream) as sp:     # (blocking: the tables stay alive until it returns)
             _check(self._lib.vimg_hip_scene_update_geometry(self._h, C.byref(upd), sp))
+        self.vertices_given = given.get("vertices", self.vertices_given)
+        self.spheres_given = given.get("spheres", self.spheres_given)
 
     def update_from(self, host_scene, stream=None):
         """The four tables of ``host_scene`` (materials, texture records, emitters, background) as they now stand:
