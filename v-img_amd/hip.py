@@ -352,42 +352,22 @@ class DeviceScene:
         (vimg_amd.varfilter.atrous, include/vimg_varfilter.h) instead, with ``filter_kw`` its parameters; a one-shot
         render has no variance, so every pixel's is estimated from its surroundings.  Returns the filtered [H, W, 3]
         image (``out`` when given); whole frames only."""
-        from . import filter as flt
+        from . import preview
         if params.tile_world != 1:
             raise ValueError("render_denoised: the filter reads whole frames, not shards (tile_world must be 1)")
         noisy = self.render(params, stats=False, stream=stream)
-        guides = self.render_features(params, flt.GUIDES, stream=stream)
-        if variance_guided:
-            from . import varfilter
-            return varfilter.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
-                                    stream=stream, **filter_kw)[0]
-        return flt.atrous(noisy, guides["normal"], guides["position"], guides["depth"], albedo=guides["albedo"], out=out,
-                          stream=stream, **filter_kw)
+        guides = self.render_features(params, preview.GUIDES, stream=stream)
+        return preview.denoise(noisy, guides, variance_guided, out=out, stream=stream, **filter_kw)
 
     def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
                          fill_weight=None, antilag=False, motion=None, **temporal_kw):
-        """A preview that survives a moving camera (vimg_amd.temporal.TemporalPreview, include/vimg_temporal.h): its
-        ``frame()`` renders ``samples`` more samples of the scene as it now stands and returns the [H, W, 3] picture -
-        after set_camera or an edit blended with the last picture reprojected into the new camera, while nothing
-        changes the plain progressive stream blended with that history - filtered by filter.atrous when ``denoise``, its sigma_color divided by the square root of the frames accumulated.
-        ``temporal_kw``: max_history, sigma_normal, sigma_plane, ``filter_kw`` (a dict for filter.atrous),
-        ``scale_sigma_color`` (False: the filter's sigma_color as it is).  ``variance_guided``: the histories carry the
-        moments of luminance (vimg_amd.moments, include/vimg_moments.h) and varfilter.atrous filters each pixel by the
-        variance of its own accumulated mean; ``filter_kw`` are then its parameters, ``temporal_kw`` takes min_history
-        too and ``scale_sigma_color`` is refused.  ``sparse`` (a stride 2..4): a frame samples one pixel in sparse^2,
-        on a lattice that cycles, fills the others from the guides (vimg_amd.infill) and accumulates with per-pixel
-        weights (vimg_amd.wtemporal, include/vimg_wtemporal.h) - a filled pixel, worth ``fill_weight`` samples, takes
-        its reprojected history where it has one; not with ``variance_guided``.  ``antilag`` (True, or a dict of
-        antilag.rescale's parameters): on the frame after set_camera or an edit, the history's lengths are first cut
-        where the new picture disagrees with it by more than its noise (vimg_amd.antilag, include/vimg_antilag.h), so
-        a relit region starts over and the rest keeps its history.  ``motion`` (the HostScene this scene was uploaded
-        from, its positions the resident ones): after update_geometry the history is looked up where each pixel's
-        surface point WAS (vimg_amd.motion, include/vimg_motion.h), so a moved object keeps its samples.  Whole frames
-        only."""
-        from . import temporal
-        return temporal.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
-                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
-                                        motion=motion, **temporal_kw)
+        """A preview that survives a moving camera: a vimg_amd.preview.TemporalPreview of this scene, which tells what its
+        ``frame()`` returns and what every argument chooses (``temporal_kw`` also carries ``filter_kw`` and
+        ``scale_sigma_color``).  Whole frames only."""
+        from . import preview
+        return preview.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
+                                       variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
+                                       motion=motion, **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,
@@ -765,16 +745,13 @@ class Progressive:
         Whole frames only.  ``filter_kw``: the parameters of filter.atrous.  ``variance_guided``: render(samples) +
         ``variance()`` + the variance-guided filter (vimg_amd.varfilter.atrous, ``filter_kw`` its parameters) on the
         same guides - each pixel is filtered by its own noise, whatever its count."""
-        from . import filter as flt
+        from . import preview
         if self.params.tile_world != 1:
             raise ValueError("preview: the filter reads whole frames, not shards (tile_world must be 1)")
         noisy = self.render(samples, stream=stream)
-        g = self._guide_cache.get(self.params, feature_samples, flt.GUIDES, stream=stream)
-        if variance_guided:
-            from . import varfilter
-            return varfilter.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], variance=self.variance(stream),
-                                    out=out, stream=stream, **filter_kw)[0]
-        return flt.atrous(noisy, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=out, stream=stream, **filter_kw)
+        g = self._guide_cache.get(self.params, feature_samples, preview.GUIDES, stream=stream)
+        return preview.denoise(noisy, g, variance_guided, variance=self.variance(stream) if variance_guided else None, out=out,
+                               stream=stream, **filter_kw)
 
     def render_sparse(self, samples, stride=2, radius=None, out=None, stream=None, feature_samples=4, **infill_kw):
         """``samples`` more samples for ONE pixel in stride^2 - the lattice infill.lattice_mask(H, W, stride, phase)
