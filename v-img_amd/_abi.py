@@ -1,6 +1,6 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
 include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h,
-include/vimg_antilag.h and include/vimg_motion.h.
+include/vimg_antilag.h, include/vimg_motion.h and include/vimg_despeckle.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -505,6 +505,31 @@ MOTION_SYMBOLS = {
 }
 
 
+class DespeckleFrames(_Sized, C.Structure):
+    """VimgDespeckleFrames (include/vimg_despeckle.h): the fields of VimgFilterFrames."""
+    _fields_ = FilterFrames._fields_
+
+
+class DespeckleParams(_Sized, C.Structure):
+    """VimgDespeckleParams (include/vimg_despeckle.h); vimg_despeckle_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("radius", u32), ("rank", u32), ("min_taps", u32), ("gain", f32), ("sigma_normal", f32),
+                ("sigma_plane", f32), ("albedo_floor", f32)]
+
+
+DESPECKLE_WORKSPACE_PER_PIXEL = 32
+DESPECKLE_MAX_RADIUS, DESPECKLE_MAX_RANK = 3, 4
+DESPECKLE_KEPT, DESPECKLE_CLAMPED, DESPECKLE_FEW_TAPS, DESPECKLE_NOT_LIVE = 0, 1, 2, 3
+
+# the list of symbols include/vimg_despeckle.h declares: libvimg_despeckle.so, the clamp of fireflies before a filter
+DESPECKLE_SYMBOLS = {
+    "vimg_despeckle_defaults": (None, [C.POINTER(DespeckleParams)]),
+    "vimg_despeckle_workspace": (C.c_uint64, [u32, u32]),
+    "vimg_despeckle_clamp": (C.c_int, [C.POINTER(DespeckleFrames), C.POINTER(DespeckleParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_uint64, C.c_void_p]),
+    "vimg_despeckle_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -531,6 +556,7 @@ _LIBRARIES = {
 # earlier ABI tests name key by key; a next library goes here.)
 _LATER_LIBRARIES = {
     "motion": ("libvimg_motion.so", (MOTION_SYMBOLS,), "motion", "; there is no CPU fallback for the previous-world positions", True),
+    "despeckle": ("libvimg_despeckle.so", (DESPECKLE_SYMBOLS,), "despeckle", "; there is no CPU fallback for the clamp", True),
 }
 _loaded = {}
 
@@ -603,3 +629,8 @@ def antilag_lib():
 def motion_lib():
     """The library that writes the previous-world positions of moved geometry (include/vimg_motion.h)."""
     return _load("motion")
+
+
+def despeckle_lib():
+    """The library that clamps fireflies before a frame is filtered (include/vimg_despeckle.h)."""
+    return _load("despeckle")

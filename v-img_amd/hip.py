@@ -345,29 +345,33 @@ class DeviceScene:
             res[name] = self.render(p, out=given, stats=False, stream=stream)
         return res
 
-    def render_denoised(self, params, out=None, stream=None, variance_guided=False, **filter_kw):
+    def render_denoised(self, params, out=None, stream=None, variance_guided=False, despeckle=None, **filter_kw):
         """``render`` followed by the a-trous filter (vimg_amd.filter.atrous, include/vimg_filter.h) guided by the
         frame's own feature frames: exactly render(params) + render_features(params, ("albedo", "normal",
         "position", "depth")) + filter.atrous(..., **filter_kw).  ``variance_guided``: the variance-guided filter
         (vimg_amd.varfilter.atrous, include/vimg_varfilter.h) instead, with ``filter_kw`` its parameters; a one-shot
-        render has no variance, so every pixel's is estimated from its surroundings.  Returns the filtered [H, W, 3]
+        render has no variance, so every pixel's is estimated from its surroundings.  ``despeckle`` (True: the library's
+        defaults; a dict: its parameters; None or False: no call): the rendered frame's fireflies are clamped
+        (vimg_amd.despeckle.clamp, include/vimg_despeckle.h) before the filter.  Returns the filtered [H, W, 3]
         image (``out`` when given); whole frames only."""
         from . import preview
         if params.tile_world != 1:
             raise ValueError("render_denoised: the filter reads whole frames, not shards (tile_world must be 1)")
+        clamp = preview.despeckle_kw(despeckle, "render_denoised")
         noisy = self.render(params, stats=False, stream=stream)
         guides = self.render_features(params, preview.GUIDES, stream=stream)
+        preview.clamp_fireflies(noisy, guides, clamp, stream=stream)
         return preview.denoise(noisy, guides, variance_guided, out=out, stream=stream, **filter_kw)
 
     def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
-                         fill_weight=None, antilag=False, motion=None, **temporal_kw):
+                         fill_weight=None, antilag=False, motion=None, despeckle=None, **temporal_kw):
         """A preview that survives a moving camera: a vimg_amd.preview.TemporalPreview of this scene, which tells what its
         ``frame()`` returns and what every argument chooses (``temporal_kw`` also carries ``filter_kw`` and
         ``scale_sigma_color``).  Whole frames only."""
         from . import preview
         return preview.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
-                                       motion=motion, **temporal_kw)
+                                       motion=motion, despeckle=despeckle, **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,
@@ -736,7 +740,7 @@ class Progressive:
         img = None if out is False else out
         return (img, st) if stats else img
 
-    def preview(self, samples, out=None, stream=None, feature_samples=4, variance_guided=False, **filter_kw):
+    def preview(self, samples, out=None, stream=None, feature_samples=4, variance_guided=False, despeckle=None, **filter_kw):
         """``render(samples)`` followed by the a-trous filter (vimg_amd.filter.atrous) on the running mean: the
         denoised picture of the frame so far.  The accumulator is advanced exactly as by ``render`` and keeps the
         unfiltered sums, so later increments and renders give the bits they would have given.  The guides -
@@ -744,12 +748,17 @@ class Progressive:
         the increments: they are rendered once and kept until the scene is edited (DeviceScene.generation).
         Whole frames only.  ``filter_kw``: the parameters of filter.atrous.  ``variance_guided``: render(samples) +
         ``variance()`` + the variance-guided filter (vimg_amd.varfilter.atrous, ``filter_kw`` its parameters) on the
-        same guides - each pixel is filtered by its own noise, whatever its count."""
+        same guides - each pixel is filtered by its own noise, whatever its count.  ``despeckle`` (True: the library's
+        defaults; a dict: its parameters; None or False: no call): the fireflies of the running mean ``render``
+        returned - a frame of its own, the sums are not touched - are clamped (vimg_amd.despeckle.clamp,
+        include/vimg_despeckle.h) before the filter."""
         from . import preview
         if self.params.tile_world != 1:
             raise ValueError("preview: the filter reads whole frames, not shards (tile_world must be 1)")
+        clamp = preview.despeckle_kw(despeckle, "preview")
         noisy = self.render(samples, stream=stream)
         g = self._guide_cache.get(self.params, feature_samples, preview.GUIDES, stream=stream)
+        preview.clamp_fireflies(noisy, g, clamp, stream=stream)
         return preview.denoise(noisy, g, variance_guided, variance=self.variance(stream) if variance_guided else None, out=out,
                                stream=stream, **filter_kw)
 

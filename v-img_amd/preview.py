@@ -1,8 +1,8 @@
 """The previews of a resident scene, composed from the frame libraries: ``denoise``, the filter choice of
 every preview, and TemporalPreview, whose frame() is one straight line over parts chosen once - an increment, an
-accumulation, a filter, and the options anti-lag and motion.  A part owns its buffers and its state and imports the
-libraries it needs and no others; a new mode is a new part and one line of TemporalPreview.__init__.  There is no CPU
-fallback."""
+accumulation, a filter, and the options despeckle, anti-lag and motion.  A part owns its buffers and its state and
+imports the libraries it needs and no others; a new mode is a new part and one line of TemporalPreview.__init__.  There
+is no CPU fallback."""
 import math
 
 from .filter import GUIDES
@@ -21,6 +21,29 @@ def denoise(color, g, variance_guided=False, variance=None, **kw):
         return varfilter.atrous(color, g["normal"], g["position"], g["depth"], albedo=g["albedo"], variance=variance, **kw)[0]
     from . import filter as flt
     return flt.atrous(color, g["normal"], g["position"], g["depth"], albedo=g["albedo"], **kw)
+
+
+def despeckle_kw(given, what):
+    """The ``despeckle`` argument of a preview (``what`` names it in a refusal): None or False - no clamp, None is
+    returned; True - the library's defaults, {}; a dict - despeckle.params' keywords, checked here."""
+    if given is None or given is False:
+        return None
+    if given is not True and not isinstance(given, dict):
+        raise ValueError(f"{what}: despeckle must be None, a bool or a dict of vimg_amd.despeckle's parameters, not {type(given).__name__}")
+    from . import despeckle
+    kw = {} if given is True else dict(given)
+    despeckle.params(**kw)           # (refuses an unknown name now)
+    return kw
+
+
+def clamp_fireflies(color, g, kw, **call):
+    """``color`` with its fireflies clamped IN PLACE (vimg_amd.despeckle.clamp, include/vimg_despeckle.h) by the feature
+    frames ``g``, before any filter sees it; ``kw``: despeckle_kw's answer, None: nothing is done.  ``call``: ``workspace``,
+    ``stream``.  ``color`` must be the caller's own frame, never a buffer of the accumulator."""
+    if kw is not None:
+        from . import despeckle
+        despeckle.clamp(color, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=color, out_code=False, **call, **kw)
+    return color
 
 
 def _empty(dtype, *shape):
@@ -138,6 +161,23 @@ def _variance_filter(dev, kw, variance):
     return run
 
 
+class _Despeckle:
+    """``despeckle`` (True: the library's defaults; a dict: despeckle.clamp's parameters): every frame()'s
+    increment - the running mean acc.render returned, a frame of its own, never the accumulator's sums - has its fireflies
+    clamped in place (vimg_amd.despeckle, include/vimg_despeckle.h) right after it is rendered, on moving and standing
+    frames alike: the anti-lag test, the moments, the history and the filter all see the clamped frame, and the
+    accumulator stays bit for bit a Progressive.  It is refused with ``sparse``: a lattice pixel's neighbours carry no
+    samples."""
+
+    def __init__(self, dev, kw):
+        from . import despeckle
+        self.params = kw
+        self._workspace = _empty("uint8", despeckle.workspace_bytes(*dev.resolution))
+
+    def __call__(self, mean, g, stream):
+        clamp_fireflies(mean, g, self.params, workspace=self._workspace, stream=stream)
+
+
 class _Antilag:
     """``antilag`` (True: the library's defaults; a dict: antilag.rescale's parameters): on the frame()
     on which the scene had changed and a history freezes, that frozen history's lengths are rescaled once
@@ -239,7 +279,7 @@ class TemporalPreview:
 
     The modes are parts of this module, chosen once here, and each tells its own contract: ``denoise`` and
     ``scale_sigma_color`` in _fixed_filter, ``variance_guided`` in _moments_accumulation, ``sparse`` and ``fill_weight``
-    in _SparseIncrement, ``antilag`` in _Antilag, ``motion`` in _Motion.
+    in _SparseIncrement, ``despeckle`` in _Despeckle, ``antilag`` in _Antilag, ``motion`` in _Motion.
 
     Limits: without ``antilag``, history from before a material edit is reprojected all the same and fades at
     1 / max_history per frame (``reset()`` drops all of it), and so is history from before a geometry edit, which
@@ -253,10 +293,11 @@ class TemporalPreview:
     object's lighting lags as any edit's does."""
     sparse, fill_weight = _of("_increment", "stride"), _of("_increment", "fill_weight")
     antilag, last_scale = _of("_cut", "params"), _of("_cut", "last_scale")
+    despeckle = _of("_clamp", "params")
     last_motion_code, _previous = _of("_motion", "last_code"), _of("_motion", "previous")
 
     def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
-                 variance_guided=False, sparse=None, fill_weight=None, antilag=False, motion=None, **temporal_kw):
+                 variance_guided=False, sparse=None, fill_weight=None, antilag=False, motion=None, despeckle=None, **temporal_kw):
         if params.tile_world != 1:
             raise ValueError("temporal_preview: reprojection reads whole frames, not shards (tile_world must be 1)")
         if int(samples) < 1 or int(feature_samples) < 1:
@@ -270,6 +311,9 @@ class TemporalPreview:
             raise ValueError("temporal_preview: sparse does not go with variance_guided: the moments history has no per-pixel weights")
         if sparse is None and fill_weight is not None:
             raise ValueError("temporal_preview: fill_weight is the weight of a filled pixel: it needs sparse")
+        clamp = despeckle_kw(despeckle, "temporal_preview")
+        if clamp is not None and sparse is not None:
+            raise ValueError("temporal_preview: despeckle does not go with sparse: a lattice pixel's neighbours carry no samples")
         self._increment = _full_increment if sparse is None else _SparseIncrement(dev, sparse, fill_weight)
         unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"} - ({"min_history"} if variance_guided else set()))
         if unknown:
@@ -282,10 +326,11 @@ class TemporalPreview:
         w, h = dev.resolution
         self._buffers = [_empty("float32", 4 if self.variance_guided else 3, h, w, 4) for _ in range(2)]
         self._variance = _empty("float32", h, w) if self.variance_guided else None
-        self._features = GUIDES if denoise or sparse is not None else ("normal", "position", "depth")
+        self._features = GUIDES if denoise or sparse is not None or clamp is not None else ("normal", "position", "depth")
         max_history = float(temporal_params(max_history=temporal_kw.get("max_history")).max_history)
         self._filter = (_no_filter if not denoise else _variance_filter(dev, self.filter_kw, self._variance) if self.variance_guided else
                         _fixed_filter(dev, self.filter_kw, self.scale_sigma_color, max_history))
+        self._clamp = _absent if clamp is None else _Despeckle(dev, clamp)
         self._cut = _absent if antilag is False or antilag is None else _Antilag(dev, antilag)
         self._motion = _absent if motion is None else _Motion(dev, motion)
         self._resets = [part.reset for part in (self._increment, self._cut, self._motion) if hasattr(part, "reset")]
@@ -316,6 +361,7 @@ class TemporalPreview:
         g = self._guides.get(acc.params, self.feature_samples, self._features, stream=stream)
         previous = self._motion(g, froze, stream)          # Q, or None
         mean, weight, self.phase = self._increment(acc, self.samples, g, self._frames, stream)
+        self._clamp(mean, g, stream)
         if froze:
             self._cut(mean, g, self._frozen, stream)
         self._k += 1
