@@ -1,6 +1,6 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
 include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h,
-include/vimg_antilag.h, include/vimg_motion.h and include/vimg_despeckle.h.
+include/vimg_antilag.h, include/vimg_motion.h, include/vimg_despeckle.h and include/vimg_exposure.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -530,6 +530,32 @@ DESPECKLE_SYMBOLS = {
 }
 
 
+class ExposureFrames(_Sized, C.Structure):
+    """VimgExposureFrames (include/vimg_exposure.h): the colour frame and, optionally, the depth frame."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("color", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class ExposureParams(_Sized, C.Structure):
+    """VimgExposureParams (include/vimg_exposure.h); vimg_exposure_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("low_permille", u32), ("high_permille", u32), ("key", f32), ("min_exposure", f32),
+                ("max_exposure", f32), ("rate_brighten", f32), ("rate_darken", f32)]
+
+
+class ExposureState(C.Structure):
+    """The 1040 bytes of exposure state in device memory (include/vimg_exposure.h), as a host copy of them reads."""
+    _fields_ = [("hist", u32 * 256), ("exposure", f32), ("frames", u32), ("metered", f32), ("counted", u32)]
+
+
+EXPOSURE_BINS, EXPOSURE_STATE_BYTES, EXPOSURE_MAX_WORKGROUPS = 256, 1040, 256
+
+# the list of symbols include/vimg_exposure.h declares: libvimg_exposure.so, histogram auto-exposure with device state
+EXPOSURE_SYMBOLS = {
+    "vimg_exposure_defaults": (None, [C.POINTER(ExposureParams)]),
+    "vimg_exposure_adapt": (C.c_int, [C.POINTER(ExposureFrames), C.POINTER(ExposureParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vimg_exposure_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -557,6 +583,7 @@ _LIBRARIES = {
 _LATER_LIBRARIES = {
     "motion": ("libvimg_motion.so", (MOTION_SYMBOLS,), "motion", "; there is no CPU fallback for the previous-world positions", True),
     "despeckle": ("libvimg_despeckle.so", (DESPECKLE_SYMBOLS,), "despeckle", "; there is no CPU fallback for the clamp", True),
+    "exposure": ("libvimg_exposure.so", (EXPOSURE_SYMBOLS,), "exposure", "; there is no CPU fallback for the exposure", True),
 }
 _loaded = {}
 
@@ -634,3 +661,8 @@ def motion_lib():
 def despeckle_lib():
     """The library that clamps fireflies before a frame is filtered (include/vimg_despeckle.h)."""
     return _load("despeckle")
+
+
+def exposure_lib():
+    """The library that meters a frame and scales it by an exposure kept in device memory (include/vimg_exposure.h)."""
+    return _load("exposure")

@@ -345,33 +345,35 @@ class DeviceScene:
             res[name] = self.render(p, out=given, stats=False, stream=stream)
         return res
 
-    def render_denoised(self, params, out=None, stream=None, variance_guided=False, despeckle=None, **filter_kw):
+    def render_denoised(self, params, out=None, stream=None, variance_guided=False, despeckle=None, exposure=None, **filter_kw):
         """``render`` followed by the a-trous filter (vimg_amd.filter.atrous, include/vimg_filter.h) guided by the
         frame's own feature frames: exactly render(params) + render_features(params, ("albedo", "normal",
         "position", "depth")) + filter.atrous(..., **filter_kw).  ``variance_guided``: the variance-guided filter
         (vimg_amd.varfilter.atrous, include/vimg_varfilter.h) instead, with ``filter_kw`` its parameters; a one-shot
         render has no variance, so every pixel's is estimated from its surroundings.  ``despeckle`` (True: the library's
         defaults; a dict: its parameters; None or False: no call): the rendered frame's fireflies are clamped
-        (vimg_amd.despeckle.clamp, include/vimg_despeckle.h) before the filter.  Returns the filtered [H, W, 3]
-        image (``out`` when given); whole frames only."""
+        (vimg_amd.despeckle.clamp, include/vimg_despeckle.h) before the filter.  ``exposure`` (True, a dict, None or
+        False likewise): the filtered frame is scaled in place by the exposure it is metered to, from a fresh state
+        (vimg_amd.exposure.adapt, include/vimg_exposure.h).  Returns the filtered [H, W, 3] image (``out`` when given);
+        whole frames only."""
         from . import preview
         if params.tile_world != 1:
             raise ValueError("render_denoised: the filter reads whole frames, not shards (tile_world must be 1)")
-        clamp = preview.despeckle_kw(despeckle, "render_denoised")
+        clamp, exposed = preview.despeckle_kw(despeckle, "render_denoised"), preview.exposure_kw(exposure, "render_denoised")
         noisy = self.render(params, stats=False, stream=stream)
         guides = self.render_features(params, preview.GUIDES, stream=stream)
         preview.clamp_fireflies(noisy, guides, clamp, stream=stream)
-        return preview.denoise(noisy, guides, variance_guided, out=out, stream=stream, **filter_kw)
+        return preview.expose(preview.denoise(noisy, guides, variance_guided, out=out, stream=stream, **filter_kw), exposed, stream=stream)
 
     def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
-                         fill_weight=None, antilag=False, motion=None, despeckle=None, **temporal_kw):
+                         fill_weight=None, antilag=False, motion=None, despeckle=None, exposure=None, **temporal_kw):
         """A preview that survives a moving camera: a vimg_amd.preview.TemporalPreview of this scene, which tells what its
         ``frame()`` returns and what every argument chooses (``temporal_kw`` also carries ``filter_kw`` and
         ``scale_sigma_color``).  Whole frames only."""
         from . import preview
         return preview.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
-                                       motion=motion, despeckle=despeckle, **temporal_kw)
+                                       motion=motion, despeckle=despeckle, exposure=exposure, **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,

@@ -1,6 +1,6 @@
 """The previews of a resident scene, composed from the frame libraries: ``denoise``, the filter choice of
 every preview, and TemporalPreview, whose frame() is one straight line over parts chosen once - an increment, an
-accumulation, a filter, and the options despeckle, anti-lag and motion.  A part owns its buffers and its state and
+accumulation, a filter, and the options despeckle, anti-lag, motion and exposure.  A part owns its buffers and its state and
 imports the libraries it needs and no others; a new mode is a new part and one line of TemporalPreview.__init__.  There
 is no CPU fallback."""
 import math
@@ -44,6 +44,29 @@ def clamp_fireflies(color, g, kw, **call):
         from . import despeckle
         despeckle.clamp(color, g["normal"], g["position"], g["depth"], albedo=g["albedo"], out=color, out_code=False, **call, **kw)
     return color
+
+
+def exposure_kw(given, what):
+    """The ``exposure`` argument of a preview (``what`` names it in a refusal): None or False - the frame stays linear,
+    None is returned; True - the library's defaults, {}; a dict - exposure.params' keywords, checked here."""
+    if given is None or given is False:
+        return None
+    if given is not True and not isinstance(given, dict):
+        raise ValueError(f"{what}: exposure must be None, a bool or a dict of vimg_amd.exposure's parameters, not {type(given).__name__}")
+    from . import exposure
+    kw = {} if given is True else dict(given)
+    exposure.params(**kw)            # (refuses an unknown name now)
+    return kw
+
+
+def expose(frame, kw, state=None, stream=None):
+    """``frame`` scaled IN PLACE by the exposure it is metered to (vimg_amd.exposure.adapt, include/vimg_exposure.h): the
+    last stage of a preview, on its output alone.  ``kw``: exposure_kw's answer, None: nothing is done.  ``state``: the
+    exposure state to carry on, None: a fresh one.  Every pixel is metered, misses too: they are part of the picture."""
+    if kw is not None:
+        from . import exposure
+        exposure.adapt(frame, state=state, out=frame, stream=stream, **kw)
+    return frame
 
 
 def _empty(dtype, *shape):
@@ -178,6 +201,29 @@ class _Despeckle:
         clamp_fireflies(mean, g, self.params, workspace=self._workspace, stream=stream)
 
 
+# ---- the exposure: (the picture frame() is about to return, stream) -> the picture ------------------------------------------
+_linear = lambda frame, stream: frame
+
+
+class _Exposure:
+    """``exposure`` (True: the library's defaults; a dict: exposure.adapt's parameters): the frame that
+    frame() returns - after the accumulation and the filter, a buffer of its own - is metered and scaled in place by an
+    exposure that lives in ``state``, 1040 bytes of device memory, and moves toward key / metered from frame to frame
+    (vimg_amd.exposure, include/vimg_exposure.h): nothing is read back.  It is the last stage and touches the output
+    alone: the accumulator, the history and every filter input stay linear and bit for bit what they are without it.
+    reset() zeroes the state: the next frame is scaled to its own target."""
+
+    def __init__(self, dev, kw):
+        from . import exposure
+        self.params, self.state = kw, exposure.new_state()
+
+    def reset(self):
+        self.state.zero_()
+
+    def __call__(self, frame, stream):
+        return expose(frame, self.params, self.state, stream)
+
+
 class _Antilag:
     """``antilag`` (True: the library's defaults; a dict: antilag.rescale's parameters): on the frame()
     on which the scene had changed and a history freezes, that frozen history's lengths are rescaled once
@@ -279,7 +325,8 @@ class TemporalPreview:
 
     The modes are parts of this module, chosen once here, and each tells its own contract: ``denoise`` and
     ``scale_sigma_color`` in _fixed_filter, ``variance_guided`` in _moments_accumulation, ``sparse`` and ``fill_weight``
-    in _SparseIncrement, ``despeckle`` in _Despeckle, ``antilag`` in _Antilag, ``motion`` in _Motion.
+    in _SparseIncrement, ``despeckle`` in _Despeckle, ``antilag`` in _Antilag, ``motion`` in _Motion, ``exposure`` in
+    _Exposure.
 
     Limits: without ``antilag``, history from before a material edit is reprojected all the same and fades at
     1 / max_history per frame (``reset()`` drops all of it), and so is history from before a geometry edit, which
@@ -295,9 +342,11 @@ class TemporalPreview:
     antilag, last_scale = _of("_cut", "params"), _of("_cut", "last_scale")
     despeckle = _of("_clamp", "params")
     last_motion_code, _previous = _of("_motion", "last_code"), _of("_motion", "previous")
+    exposure, exposure_state = _of("_expose", "params"), _of("_expose", "state")
 
     def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
-                 variance_guided=False, sparse=None, fill_weight=None, antilag=False, motion=None, despeckle=None, **temporal_kw):
+                 variance_guided=False, sparse=None, fill_weight=None, antilag=False, motion=None, despeckle=None, exposure=None,
+                 **temporal_kw):
         if params.tile_world != 1:
             raise ValueError("temporal_preview: reprojection reads whole frames, not shards (tile_world must be 1)")
         if int(samples) < 1 or int(feature_samples) < 1:
@@ -314,6 +363,7 @@ class TemporalPreview:
         clamp = despeckle_kw(despeckle, "temporal_preview")
         if clamp is not None and sparse is not None:
             raise ValueError("temporal_preview: despeckle does not go with sparse: a lattice pixel's neighbours carry no samples")
+        exposed = exposure_kw(exposure, "temporal_preview")
         self._increment = _full_increment if sparse is None else _SparseIncrement(dev, sparse, fill_weight)
         unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"} - ({"min_history"} if variance_guided else set()))
         if unknown:
@@ -333,7 +383,8 @@ class TemporalPreview:
         self._clamp = _absent if clamp is None else _Despeckle(dev, clamp)
         self._cut = _absent if antilag is False or antilag is None else _Antilag(dev, antilag)
         self._motion = _absent if motion is None else _Motion(dev, motion)
-        self._resets = [part.reset for part in (self._increment, self._cut, self._motion) if hasattr(part, "reset")]
+        self._expose = _linear if exposed is None else _Exposure(dev, exposed)
+        self._resets = [part.reset for part in (self._increment, self._cut, self._motion, self._expose) if hasattr(part, "reset")]
         self._guides = GuideCache(dev)
         self.reset()
 
@@ -374,7 +425,7 @@ class TemporalPreview:
             with torch.cuda.stream(stream):
                 self.history.tensor[2, :, :, :3].copy_(g["position"])
         self._frames += 1
-        return self._filter(target, g, self._frames, stream)
+        return self._expose(self._filter(target, g, self._frames, stream), stream)
 
     def close(self):
         self.acc.close()
