@@ -1,6 +1,6 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
 include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h,
-include/vimg_antilag.h, include/vimg_motion.h, include/vimg_despeckle.h and include/vimg_exposure.h.
+include/vimg_antilag.h, include/vimg_motion.h, include/vimg_despeckle.h, include/vimg_exposure.h and include/vimg_demand.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -556,6 +556,30 @@ EXPOSURE_SYMBOLS = {
 }
 
 
+class DemandFrames(_Sized, C.Structure):
+    """VimgDemandFrames (include/vimg_demand.h): the guides of the picture about to be rendered; there is no colour frame."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("normal", C.c_void_p),
+                ("position", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class DemandParams(_Sized, C.Structure):
+    """VimgDemandParams (include/vimg_demand.h); vimg_demand_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("stride", u32), ("phase", u32), ("reserved", u32), ("min_history", f32),
+                ("sigma_normal", f32), ("sigma_plane", f32)]
+
+
+DEMAND_MAX_STRIDE, DEMAND_COUNTS = 4, 4
+
+# the list of symbols include/vimg_demand.h declares: libvimg_demand.so, the sampling mask of a sparse preview, read from
+# libvimg_temporal's history (TEMPORAL_HISTORY_PER_PIXEL) before the frame is rendered
+DEMAND_SYMBOLS = {
+    "vimg_demand_defaults": (None, [C.POINTER(DemandParams)]),
+    "vimg_demand_mask": (C.c_int, [C.POINTER(DemandFrames), C.c_void_p, Pf32, C.POINTER(DemandParams), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "vimg_demand_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -584,6 +608,7 @@ _LATER_LIBRARIES = {
     "motion": ("libvimg_motion.so", (MOTION_SYMBOLS,), "motion", "; there is no CPU fallback for the previous-world positions", True),
     "despeckle": ("libvimg_despeckle.so", (DESPECKLE_SYMBOLS,), "despeckle", "; there is no CPU fallback for the clamp", True),
     "exposure": ("libvimg_exposure.so", (EXPOSURE_SYMBOLS,), "exposure", "; there is no CPU fallback for the exposure", True),
+    "demand": ("libvimg_demand.so", (DEMAND_SYMBOLS,), "demand", "; there is no CPU fallback for the sampling mask", True),
 }
 _loaded = {}
 
@@ -666,3 +691,8 @@ def despeckle_lib():
 def exposure_lib():
     """The library that meters a frame and scales it by an exposure kept in device memory (include/vimg_exposure.h)."""
     return _load("exposure")
+
+
+def demand_lib():
+    """The library that says which pixels of a sparse preview to sample now (include/vimg_demand.h)."""
+    return _load("demand")

@@ -1,6 +1,6 @@
 """The previews of a resident scene, composed from the frame libraries: ``denoise``, the filter choice of
 every preview, and TemporalPreview, whose frame() is one straight line over parts chosen once - an increment, an
-accumulation, a filter, and the options despeckle, anti-lag, motion and exposure.  A part owns its buffers and its state and
+accumulation, a filter, and the options despeckle, anti-lag, motion, exposure and demand.  A part owns its buffers and its state and
 imports the libraries it needs and no others; a new mode is a new part and one line of TemporalPreview.__init__.  There
 is no CPU fallback."""
 import math
@@ -69,6 +69,21 @@ def expose(frame, kw, state=None, stream=None):
     return frame
 
 
+def demand_kw(given, what):
+    """The ``demand`` argument of a preview (``what`` names it in a refusal): None or False - the lattice alone, None is
+    returned; True - the library's defaults, {}; a dict - it carries ``min_history``, checked here."""
+    if given is None or given is False:
+        return None
+    if given is not True and not isinstance(given, dict):
+        raise ValueError(f"{what}: demand must be None, a bool or a dict with min_history, not {type(given).__name__}")
+    from . import demand
+    kw = {} if given is True else dict(given)
+    if set(kw) - {"min_history"}:
+        raise TypeError(f"demand: unknown parameters {sorted(set(kw) - {'min_history'})}; expected some of ('min_history',)")
+    demand.params(**kw)
+    return kw
+
+
 def _empty(dtype, *shape):
     import torch
     return torch.empty(shape, dtype=getattr(torch, dtype), device="cuda")
@@ -115,15 +130,67 @@ class _SparseIncrement:
         import torch
         from . import infill, wtemporal
         phase = frames % (self.stride * self.stride)
-        with torch.cuda.stream(stream):          # (the mask is filled where the increment reads it)
-            lattice = infill.lattice_mask(*acc.pixel_shape, self.stride, phase)
-        noisy = acc.render(samples, stream=stream, mask=lattice)
+        noisy = acc.render(samples, stream=stream, mask=self._lattice(acc, samples, g, phase, stream))
         state = acc.state(stream)
         filled, code = infill.reconstruct(noisy, g["normal"], g["position"], g["depth"], state["count"], albedo=g["albedo"], radius=self.stride,
                                           out=noisy, workspace=self._workspace, stream=stream)
         with torch.cuda.stream(stream):
             weight = wtemporal.sparse_weights(state["count"], code, state["batches"], fill_weight=self.fill_weight)
         return filled, weight, phase
+
+    def _lattice(self, acc, samples, g, phase, stream):
+        import torch
+        from . import infill
+        with torch.cuda.stream(stream):          # (the mask is filled where the increment reads it)
+            return infill.lattice_mask(*acc.pixel_shape, self.stride, phase)
+
+
+class _DemandIncrement(_SparseIncrement):
+    """``demand`` (True: the library's defaults; a dict: ``min_history``), with ``sparse``: the frame
+    that renders first after a change - a scene change, reset(), the first frame - samples, beside its lattice, every live
+    pixel whose lookup in the frozen history finds less than min_history (vimg_amd.demand, include/vimg_demand.h): the
+    mask is demand.mask of the cached guides against the frozen history, with the position frame the accumulate call will
+    get (with ``motion``: Q), at this frame's lattice phase and with ``temporal_kw``'s sigmas, so the lengths it reads are
+    the accumulate call's own.  A pixel the camera has uncovered has a sample on the frame it appears on instead of up to
+    sparse^2 frames later, and the first frame after reset() is a full one.  On standing frame k >= 1 (k: frames since
+    the change) the mask is lattice(phase) & (count <= samples (k // sparse^2)), in torch on the stream: a pixel that was
+    sampled on demand skips its lattice turn in the first cycle, every masked launch still sees one count, and after
+    sparse^2 frames of a standing camera the accumulator is, as without ``demand``, bit for bit a Progressive after one
+    render(samples).  The rest of the frame is _SparseIncrement's.  ``last_demand`` is (mask, length, counts) of the last
+    library call: [H, W] uint8, [H, W] float32 and the four device words demand.read() names (None before the first).
+    ``antilag`` cuts the history AFTER the increment is rendered, so demand sees the uncut lengths: a pixel antilag cuts
+    is demanded one frame later, on the next change."""
+
+    def __init__(self, dev, stride, fill_weight, kw, sigmas):
+        from . import demand
+        super().__init__(dev, stride, fill_weight)
+        w, h = dev.resolution
+        self.demand, self._sigmas = kw, sigmas
+        self._mask, self._length, self._counts = _empty("uint8", h, w), _empty("float32", h, w), demand.new_counts()
+        self.reset()
+
+    def reset(self):
+        self.last = None           # last_demand
+        self._asked = (None, None, 0)
+
+    def ask(self, frozen, position, k):
+        """What frame() knows and the increment's signature does not carry: the frozen history, the position frame of
+        this frame's accumulate call and the frames since the change."""
+        self._asked = (frozen, position, k)
+
+    def _lattice(self, acc, samples, g, phase, stream):
+        import torch
+        from . import demand, infill
+        frozen, position, k = self._asked
+        if k == 0:
+            self.last = demand.mask(g["normal"], position, g["depth"], history=frozen, stride=self.stride, phase=phase,
+                                    out=self._mask, out_length=self._length, counts=self._counts, stream=stream,
+                                    **self._sigmas, **self.demand)
+            return self.last[0]
+        count = acc.counts(stream)
+        with torch.cuda.stream(stream):
+            lattice = infill.lattice_mask(*acc.pixel_shape, self.stride, phase)
+            return lattice & (count <= samples * (k // (self.stride * self.stride))).to(torch.uint8)
 
 
 # ---- the accumulation: (acc, k, the picture, guides, the position frame, the increment's weight frame, the variance frame to
@@ -325,7 +392,7 @@ class TemporalPreview:
 
     The modes are parts of this module, chosen once here, and each tells its own contract: ``denoise`` and
     ``scale_sigma_color`` in _fixed_filter, ``variance_guided`` in _moments_accumulation, ``sparse`` and ``fill_weight``
-    in _SparseIncrement, ``despeckle`` in _Despeckle, ``antilag`` in _Antilag, ``motion`` in _Motion, ``exposure`` in
+    in _SparseIncrement, ``demand`` in _DemandIncrement, ``despeckle`` in _Despeckle, ``antilag`` in _Antilag, ``motion`` in _Motion, ``exposure`` in
     _Exposure.
 
     Limits: without ``antilag``, history from before a material edit is reprojected all the same and fades at
@@ -343,10 +410,11 @@ class TemporalPreview:
     despeckle = _of("_clamp", "params")
     last_motion_code, _previous = _of("_motion", "last_code"), _of("_motion", "previous")
     exposure, exposure_state = _of("_expose", "params"), _of("_expose", "state")
+    demand, last_demand = _of("_increment", "demand"), _of("_increment", "last")
 
     def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
                  variance_guided=False, sparse=None, fill_weight=None, antilag=False, motion=None, despeckle=None, exposure=None,
-                 **temporal_kw):
+                 demand=None, **temporal_kw):
         if params.tile_world != 1:
             raise ValueError("temporal_preview: reprojection reads whole frames, not shards (tile_world must be 1)")
         if int(samples) < 1 or int(feature_samples) < 1:
@@ -364,7 +432,13 @@ class TemporalPreview:
         if clamp is not None and sparse is not None:
             raise ValueError("temporal_preview: despeckle does not go with sparse: a lattice pixel's neighbours carry no samples")
         exposed = exposure_kw(exposure, "temporal_preview")
-        self._increment = _full_increment if sparse is None else _SparseIncrement(dev, sparse, fill_weight)
+        demanded = demand_kw(demand, "temporal_preview")
+        if demanded is not None and sparse is None:
+            raise ValueError("temporal_preview: demand chooses the pixels a sparse frame samples: it needs sparse")
+        sigmas = {k: temporal_kw[k] for k in ("sigma_normal", "sigma_plane") if k in temporal_kw}
+        self._increment = (_full_increment if sparse is None else _SparseIncrement(dev, sparse, fill_weight) if demanded is None else
+                           _DemandIncrement(dev, sparse, fill_weight, demanded, sigmas))
+        self._ask = getattr(self._increment, "ask", _absent)
         unknown = sorted(set(temporal_kw) - {"max_history", "sigma_normal", "sigma_plane"} - ({"min_history"} if variance_guided else set()))
         if unknown:
             raise TypeError(f"temporal_preview: unknown parameters {unknown}")
@@ -411,6 +485,7 @@ class TemporalPreview:
             self._generation, self._k = dev.generation, 0
         g = self._guides.get(acc.params, self.feature_samples, self._features, stream=stream)
         previous = self._motion(g, froze, stream)          # Q, or None
+        self._ask(self._frozen, g["position"] if previous is None else previous, self._k)
         mean, weight, self.phase = self._increment(acc, self.samples, g, self._frames, stream)
         self._clamp(mean, g, stream)
         if froze:
