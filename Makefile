@@ -64,7 +64,8 @@ $(OBJDIR)/%.o: v-img_amd/csrc/%.hip $(HIPHDR) Makefile
 # of them (the f64 polynomial coefficients of acos / atan2 / pow ...) in front of the loop, where they
 # no longer fit the register file: 533 spilled registers and 700 bytes of scratch per lane with the
 # pass, 80 / 72 without (tools/kres.sh)
-$(OBJDIR)/k_cu.o $(OBJDIR)/k_cu_early.o $(OBJDIR)/k_cu_diag.o $(OBJDIR)/k_cu_plain.o $(OBJDIR)/k_cu_plain_early.o: \
+$(OBJDIR)/k_cu.o $(OBJDIR)/k_cu_early.o $(OBJDIR)/k_cu_diag.o $(OBJDIR)/k_cu_plain.o $(OBJDIR)/k_cu_plain_early.o \
+$(OBJDIR)/k_cu_plain_other.o $(OBJDIR)/k_cu_plain_other_early.o: \
     HIPCFLAGS += -mllvm -disable-machine-licm
 # feature_kernel: the same pass hoists the constants of generate_ray, the hit record and the texture lookup in
 # front of the sample loop: 201 / 182 registers (TEX / not) and two waves per SIMD with it, 99 / 84 and four /

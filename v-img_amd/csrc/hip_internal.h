@@ -33,6 +33,7 @@ struct VimgDeviceScene {
   bool too_wide = false;       // resolution beyond the 16-bit pixel coordinates of the slot records
   bool force_general = false;  // VIMG_HIP_PLAIN=0 at upload: never a PLAIN build of render_cu_kernel (tests, A/B runs)
   bool no_lds_tables = false;  // VIMG_HIP_LDS_TABLES=0 at upload: no launch stages the shading tables in LDS (tests, A/B runs)
+  bool has_other = false;      // a material of class 3 is in the table (scene_bake.h: table_holds_other; upload and every material edit)
   uint32_t num_cus = 0;
   uint32_t num_leaf_prims = 0;   // records in d.leaf_prims (= primitives of the scene)
   // scratch owned by the scene; the last four grow to what a launch asks for and never shrink
@@ -214,6 +215,7 @@ const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c);
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
 // whether the launch, as its arguments stand, runs a PLAIN build (plain_build.h)
 bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
+uint32_t plain_fold_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);   // the serving build's fold (plain_build.h), 0 = none
 // takes the shading tables out of a launch that will not run a PLAIN build (call once its arguments are complete)
 void drop_unread_tables(const VimgDeviceScene* s, LaunchCfg& c, bool stats);
 

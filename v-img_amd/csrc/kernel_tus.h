@@ -17,5 +17,8 @@ CuKernel vimg_cu_kernel_diag(bool tex, bool deep, int nw);    // ... <..., true,
 // the PLAIN builds (plain_build.h: launch-constant options compiled in) of the two untextured builds for trees in LDS
 CuKernel vimg_cu_kernel_plain();                              // render_cu_kernel<false, false, 16, 4, false, 0, PLAIN_FOLD>
 CuKernel vimg_cu_kernel_plain_early();                        // ... <..., false, 1, PLAIN_FOLD>
+// ... and the same two for scenes that hold a material of class 3 (PLAIN_FOLD_OTHER: the fourth vertex ring stays)
+CuKernel vimg_cu_kernel_plain_other();
+CuKernel vimg_cu_kernel_plain_other_early();
 
 }  // namespace vimg

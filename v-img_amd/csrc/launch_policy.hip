@@ -59,8 +59,10 @@ uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint6
 
 namespace {
 
-CuKernel pick_cu_kernel(const VimgDeviceScene* s, bool deep, int nw, bool diag = false, bool early = false, bool plain = false) {
-  if (plain) return early ? vimg_cu_kernel_plain_early() : vimg_cu_kernel_plain();
+// (`plain`: the fold of the PLAIN build that serves the launch, plain_fold_of; 0 = none does)
+CuKernel pick_cu_kernel(const VimgDeviceScene* s, bool deep, int nw, bool diag = false, bool early = false, uint32_t plain = 0u) {
+  if (plain == PLAIN_FOLD) return early ? vimg_cu_kernel_plain_early() : vimg_cu_kernel_plain();
+  if (plain != 0u) return early ? vimg_cu_kernel_plain_other_early() : vimg_cu_kernel_plain_other();
   return diag ? vimg_cu_kernel_diag(s->textured, deep, nw)
               : (early ? vimg_cu_kernel_early(s->textured, deep, nw) : vimg_cu_kernel(s->textured, deep, nw));
 }
@@ -284,10 +286,15 @@ const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c) {
 
 // The one place that decides between a PLAIN build and the general one: the launch as its arguments stand
 // (enqueue_render asks after it has set the item list and the statistics flag) against plain_build.h's list.
-bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
-  return plain_build_serves(plain_launch_of(c.sched == VIMG_SCHED_CU, s->textured, c.deep, c.cu_waves, stats, s->force_general, c.args)) &&
-         plain_tables_serve(c.args.lds_tables) && plain_leaf_perm_serves(c.args.leaf_perm);
+// plain_fold_of: which of them - PLAIN_FOLD, or PLAIN_FOLD_OTHER where the resident scene holds a material of class 3
+// (VimgDeviceScene::has_other: set at upload, again by every material edit); 0 = the general build.  The two folds
+// differ in PF_NO_OTHER only, so tables and leaf copies serve both alike.
+uint32_t plain_fold_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
+  if (!plain_tables_serve(c.args.lds_tables) || !plain_leaf_perm_serves(c.args.leaf_perm)) return 0u;
+  return plain_fold_serving(plain_launch_of(c.sched == VIMG_SCHED_CU, s->textured, c.deep, c.cu_waves, stats, s->force_general, c.args,
+                                            s->has_other));
 }
+bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) { return plain_fold_of(s, c, stats) != 0u; }
 
 // A launch whose arguments, now complete, send it to the general or the statistics build reads no table from LDS:
 // and no permuted leaf copy: their room goes back (they are the last things in the layout) and RenderArgs::lds_tables
@@ -303,7 +310,7 @@ void drop_unread_tables(const VimgDeviceScene* s, LaunchCfg& c, bool stats) {
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats) {
   if (c.sched != VIMG_SCHED_CU) return kernel_of(s, c);
   return reinterpret_cast<const void*>(pick_cu_kernel(s, c.deep, c.cu_waves, stats, (c.args.cu_flex & 32u) != 0u,
-                                                      plain_launch_serves(s, c, stats)));
+                                                      plain_fold_of(s, c, stats)));
 }
 
 namespace {

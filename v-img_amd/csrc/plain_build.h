@@ -34,13 +34,21 @@ enum : uint32_t {
   // triangles' vertices permuted as the watertight test permutes them: a lane reads the copy of its ray's axis and
   // the test permutes nothing.  A scene without triangles needs no copy
   PF_LEAF_PERM = 256u,
+  // The resident scene holds no material of class 3 ("other": what is neither an emitter nor Lambertian nor Principled,
+  // scene_bake.h: bake_material_class), so no slot ever goes to the fourth vertex ring: the hand-over, the main loop's
+  // look and the dispatch drop that ring, and the "any material" vertex stage is not instantiated.  The only bit that
+  // describes the SCENE: a scene that does hold such a material runs the build without it (PLAIN_FOLD_OTHER).  It needs
+  // the integrator and the classes folded (another integrator, fewer classes route differently): opt_no_other
+  PF_NO_OTHER = 512u,
 };
 // What the PLAIN builds fold (DESIGN.md 4.4 has the times of the candidates)
 #ifdef VIMG_PLAIN_FOLD   // (sweeps: -DVIMG_PLAIN_FOLD=<mask> on the units that include this header)
 constexpr uint32_t PLAIN_FOLD = VIMG_PLAIN_FOLD;
 #else
-constexpr uint32_t PLAIN_FOLD = PF_INTEGRATOR | PF_CLASSES | PF_LEAF_LDS | PF_SINGLE | PF_ITEMS | PF_FLEX | PF_TAB_HIT | PF_LEAF_PERM;
+constexpr uint32_t PLAIN_FOLD = PF_INTEGRATOR | PF_CLASSES | PF_LEAF_LDS | PF_SINGLE | PF_ITEMS | PF_FLEX | PF_TAB_HIT | PF_LEAF_PERM | PF_NO_OTHER;
 #endif
+// ... and what the PLAIN builds of a scene with a material of class 3 fold (k_cu_plain_other*.hip): the same without the bit
+constexpr uint32_t PLAIN_FOLD_OTHER = PLAIN_FOLD & ~PF_NO_OTHER;
 
 // what the predicate needs to know of a launch (plain_launch_of below fills it)
 struct PlainLaunch {
@@ -52,6 +60,7 @@ struct PlainLaunch {
   uint32_t integrator, pool_classes, lds_leaf, cu_flex;
   int single_x;
   bool has_item_list;
+  bool has_other = false;   // the resident scene holds a material of class 3 (known at upload, again after a material edit)
 };
 constexpr uint32_t PLAIN_INTEGRATOR_MIS = 3u;   // (VIMG_INTEGRATOR_MIS; render_cu_kernel.h asserts they agree)
 constexpr uint32_t PLAIN_FLEX_DEFAULT = 1u;     // cu_flex without the early bit
@@ -65,7 +74,12 @@ constexpr bool plain_build_serves(const PlainLaunch& l, uint32_t fold = PLAIN_FO
   if ((fold & PF_SINGLE) && l.single_x >= 0) return false;
   if ((fold & PF_ITEMS) && l.has_item_list) return false;
   if ((fold & PF_FLEX) && (l.cu_flex & ~32u) != PLAIN_FLEX_DEFAULT) return false;
+  if ((fold & PF_NO_OTHER) && l.has_other) return false;
   return true;
+}
+// The fold of the PLAIN build that serves the launch: PLAIN_FOLD, else PLAIN_FOLD_OTHER (the scene holds class 3); 0 = none
+constexpr uint32_t plain_fold_serving(const PlainLaunch& l) {
+  return plain_build_serves(l, PLAIN_FOLD) ? PLAIN_FOLD : (plain_build_serves(l, PLAIN_FOLD_OTHER) ? PLAIN_FOLD_OTHER : 0u);
 }
 
 // The table groups are one more folded constant, with a predicate of their own beside the one above: `staged` is
@@ -87,9 +101,9 @@ constexpr bool plain_leaf_perm_serves(uint32_t ready, uint32_t fold = PLAIN_FOLD
 // stays plain C++ and the mapping can be tested without the device headers).
 template <class Args>
 constexpr PlainLaunch plain_launch_of(bool cu_sched, bool textured, bool deep, int cu_waves, bool stats, bool force_general,
-                                      const Args& a) {
+                                      const Args& a, bool has_other = false) {
   return PlainLaunch{cu_sched, textured, deep, cu_waves, stats || a.full_stats != 0u, force_general,
-                     a.integrator, a.pool_classes, a.lds_leaf, a.cu_flex, a.single_x, a.item_list != nullptr};
+                     a.integrator, a.pool_classes, a.lds_leaf, a.cu_flex, a.single_x, a.item_list != nullptr, has_other};
 }
 
 }  // namespace vimg

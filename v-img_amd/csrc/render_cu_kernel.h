@@ -142,6 +142,17 @@ VD uint32_t lds_add_rtn(VIMG_LDS uint32_t* p, uint32_t v) { return __hip_atomic_
 VD uint32_t lds_load(VIMG_LDS uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 VD int32_t lds_load(VIMG_LDS int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 VD uint32_t cu_uni(uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); }
+// The lanes of a predicate as a wave-uniform mask in scalar registers that the optimiser cannot trace back to the
+// predicate (an empty asm on the pair, as cu_kargs has on its address), and the lanes of such a mask as the
+// condition of a region.  A loop that tests the mask against 0 and enters `if (cu_lanes(m))` compiles to a scalar
+// compare and branch and one exec region; written on the predicate itself, the compiler follows the lanes for which
+// it is false round the back edge and carries the loop as a divergent one.
+VD unsigned long long cu_mask(bool p) {
+  unsigned long long m = __builtin_amdgcn_ballot_w64(p);
+  asm volatile("" : "+s"(m));
+  return m;
+}
+VD bool cu_lanes(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
 // Launch-constant options: the constant in a build whose PLAIN mask folds the option, else the argument
 // (plain_build.h has the list and the host's predicate).  The stage bodies read the options through these only.
@@ -164,6 +175,10 @@ template <uint32_t PLAIN> VD bool opt_has_items(const RenderArgs& A) {
 template <uint32_t PLAIN> VD uint32_t opt_flex(const RenderArgs& A) {   // (without the early bit: EARLY is a parameter of its own)
   if constexpr (PLAIN & PF_FLEX) return PLAIN_FLEX_DEFAULT; else return A.cu_flex;
 }
+// (the fourth vertex ring is out of the build: the scene holds no class 3, and with the mis integrator and classes as
+// the leaf records name them nothing else routes a slot there)
+template <uint32_t PLAIN> constexpr bool opt_no_other =
+    (PLAIN & (PF_NO_OTHER | PF_INTEGRATOR | PF_CLASSES)) == (PF_NO_OTHER | PF_INTEGRATOR | PF_CLASSES);
 template <uint32_t PLAIN> constexpr bool opt_leaf_perm = (PLAIN & PF_LEAF_PERM) != 0u;   // (only ever a constant: no general build reads the copies)
 // (the table groups PF_TAB_* are folded through the type of the scene the vertex stages read: LdsTables<PLAIN & PF_TABLES>)
 
@@ -333,24 +348,26 @@ VD CuKPtr cu_kargs() {
         else if (opt_classes<PLAIN>(A) == 2) cls_ = (cls_ == 2) ? 2u : 1u;                                              \
       }                                                                                                                 \
     }                                                                                                                   \
+    /* (opt_no_other: no slot of this scene is of class 3 - three rings, three of everything) */                        \
+    constexpr bool four_ = !opt_no_other<PLAIN>;                                                                        \
     const unsigned long long m0_ = __ballot(complete && cls_ == 0), m1_ = __ballot(complete && cls_ == 1),              \
-                             m2_ = __ballot(complete && cls_ == 2), m3_ = __ballot(complete && cls_ == 3);              \
+                             m2_ = __ballot(complete && cls_ == 2), m3_ = four_ ? __ballot(complete && cls_ == 3) : 0ull;\
     if ((m0_ | m1_ | m2_ | m3_) == 0ull) return;                                                                        \
-    const uint32_t n_me_ = static_cast<uint32_t>(__popcll(lane == 0 ? m0_ : (lane == 1 ? m1_ : (lane == 2 ? m2_ : m3_)))); \
+    const uint32_t n_me_ = static_cast<uint32_t>(__popcll(lane == 0 ? m0_ : (lane == 1 ? m1_ : ((!four_ || lane == 2) ? m2_ : m3_))));\
     uint32_t t_me_ = 0;                                                                                                 \
-    if (lane < 4u && n_me_ != 0u) {                                                                                     \
+    if (lane < (four_ ? 4u : 3u) && n_me_ != 0u) {                                                                      \
       t_me_ = lds_add_rtn(&G->tail[lane], n_me_);                                                                       \
       if (t_me_ > 0x7ff00000u) raise(8u);                                                                               \
     }                                                                                                                   \
-    const uint32_t t0_ = __shfl(t_me_, 0), t1_ = __shfl(t_me_, 1), t2_ = __shfl(t_me_, 2), t3_ = __shfl(t_me_, 3);      \
+    const uint32_t t0_ = __shfl(t_me_, 0), t1_ = __shfl(t_me_, 1), t2_ = __shfl(t_me_, 2), t3_ = four_ ? __shfl(t_me_, 3) : 0u;\
     if (complete) {                                                                                                     \
-      const uint32_t tt_ = cls_ == 0 ? t0_ : (cls_ == 1 ? t1_ : (cls_ == 2 ? t2_ : t3_));                               \
-      const unsigned long long mm_ = cls_ == 0 ? m0_ : (cls_ == 1 ? m1_ : (cls_ == 2 ? m2_ : m3_));                     \
+      const uint32_t tt_ = cls_ == 0 ? t0_ : (cls_ == 1 ? t1_ : ((!four_ || cls_ == 2) ? t2_ : t3_));                   \
+      const unsigned long long mm_ = cls_ == 0 ? m0_ : (cls_ == 1 ? m1_ : ((!four_ || cls_ == 2) ? m2_ : m3_));         \
       *ring_at(cls_, tt_ + lane_rank(mm_, lane)) = static_cast<uint16_t>(slot_);                                        \
       if (full_stats) tq[slot_] = static_cast<uint32_t>(__builtin_readcyclecounter());                                  \
     }                                                                                                                   \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");                                                              \
-    if (lane < 4u && n_me_ != 0u) lds_add_rtn(&G->avail[lane], static_cast<int32_t>(n_me_));                            \
+    if (lane < (four_ ? 4u : 3u) && n_me_ != 0u) lds_add_rtn(&G->avail[lane], static_cast<int32_t>(n_me_));                            \
   };                                                                                                                    \
   /* the rays of the lanes of `ms_` (shadow rays) and `mr_` (path rays) into the walk ring, one reservation, shadow    \
      rays first (an occluded one is the shorter walk, and rays of a kind are then walked together) */                   \
@@ -1138,11 +1155,13 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
     const bool exact_round = __any(w_exact && w_slot != SLOT_IDLE);
     for (;;) {
       auto box_loop = [&](auto exact_possible) {
+        // wave-uniform by construction: the descending lanes as one scalar mask per trip (cu_mask), tested against 0
+        // for the exit and entered as the pass's one exec region
         for (;;) {
-          const bool act = cur != REF_DONE && ref_count(cur) == 0;
-          if (!__any(act)) break;
-          if (full_stats) d_box += 1u, d_boxl += static_cast<uint32_t>(__popcll(__ballot(act)));
-          if (act) {
+          const unsigned long long m_act = cu_mask(cur != REF_DONE && ref_count(cur) == 0);
+          if (m_act == 0ull) break;
+          if (full_stats) d_box += 1u, d_boxl += static_cast<uint32_t>(__popcll(m_act));
+          if (cu_lanes(m_act)) {
             v4f na, nb, nc;
             v2u refs;
             if (!DEEP || cur < L.n_nodes) {
@@ -1178,11 +1197,15 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
               if (!any && sp_below >= S) popped = ovf0[(sp_below - S) * 64];
             }
             const uint32_t one_c = in1 ? c1 : c2;
-            cur = both ? near_c : (any ? one_c : (sp != 0 ? popped : REF_DONE));
-            sp = both ? sp + 1 : (any ? sp : sp_below);
+            // (selects of values that all stand in registers, one per line: written as one nested expression they
+            // come out as three exec-mask regions round a v_cndmask each)
+            const uint32_t pop_c = sp != 0 ? popped : REF_DONE;
+            const uint32_t part_c = any ? one_c : pop_c, part_sp = any ? sp : sp_below;
+            cur = both ? near_c : part_c;
+            sp = both ? sp + 1 : part_sp;
           }
           if constexpr (DEEP) {
-            if (static_cast<uint32_t>(__popcll(__ballot(cur != REF_DONE && ref_count(cur) == 0))) < box_min) break;
+            if (static_cast<uint32_t>(__popcll(__builtin_amdgcn_ballot_w64(cur != REF_DONE && ref_count(cur) == 0))) < box_min) break;
           }
         }
       };
@@ -1247,9 +1270,8 @@ VD void cu_walk(uint32_t& n_closest, uint32_t& n_shadow) {
         sp = sp_below;
       }
       wlap(wc2);
-      const uint32_t n_fin = static_cast<uint32_t>(__popcll(__ballot(w_slot != SLOT_IDLE && cur == REF_DONE)));
-      const uint32_t n_act = static_cast<uint32_t>(__popcll(__ballot(w_slot != SLOT_IDLE && cur != REF_DONE)));
-      if (n_act == 0 || n_fin >= A.pool_refill) break;
+      const uint32_t n_fin = static_cast<uint32_t>(__popcll(__builtin_amdgcn_ballot_w64(w_slot != SLOT_IDLE && cur == REF_DONE)));
+      if (__builtin_amdgcn_ballot_w64(w_slot != SLOT_IDLE && cur != REF_DONE) == 0ull || n_fin >= A.pool_refill) break;
     }
 
     // (4) finished rays: result into the slot, OR into its flag word; whoever completes the slot - a
@@ -1361,7 +1383,7 @@ render_cu_kernel(const CuKArgs ka) {
     if (cu_uni(lds_load(&G->abort)) != 0u) break;
     const v4u av4 = *reinterpret_cast<VIMG_LDS v4u*>(&G->avail[0]);
     const int32_t a0 = skip_fin ? 0 : static_cast<int32_t>(cu_uni(av4.x)), a1 = static_cast<int32_t>(cu_uni(av4.y)),
-                  a2 = static_cast<int32_t>(cu_uni(av4.z)), a3 = static_cast<int32_t>(cu_uni(av4.w));
+                  a2 = static_cast<int32_t>(cu_uni(av4.z)), a3 = opt_no_other<PLAIN> ? 0 : static_cast<int32_t>(cu_uni(av4.w));
     const int32_t aw = static_cast<int32_t>(cu_uni(static_cast<uint32_t>(lds_load(&G->avail[CQ_WALK]))));
     const int32_t m01 = a0 > a1 ? a0 : a1, m23 = a2 > a3 ? a2 : a3, qmax = m01 > m23 ? m01 : m23;
     if (full_stats && lane == 0) {
@@ -1411,9 +1433,9 @@ render_cu_kernel(const CuKArgs ka) {
         cu_vertex<TEX, NW, DIAG, EARLY, true, -1, PLAIN>(n, e, all_pending, n_nan, n_dead);
       else if (cls == 1u && by_class)
         cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_LAMBERTIAN), PLAIN>(n, e, all_pending, n_nan, n_dead);
-      else if (cls == 2u && by_class)
+      else if ((cls == 2u && by_class) || opt_no_other<PLAIN>)   // (without the fourth ring a batch that is neither 0 nor 1 is 2)
         cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_PRINCIPLED), PLAIN>(n, e, all_pending, n_nan, n_dead);
-      else
+      else if constexpr (!opt_no_other<PLAIN>)
         cu_vertex<TEX, NW, DIAG, EARLY, false, -1, PLAIN>(n, e, all_pending, n_nan, n_dead);
       if (opt_flex<PLAIN>(A) & 2u) __builtin_amdgcn_s_setprio(0);
       skip_fin = all_pending;

@@ -461,13 +461,15 @@ VD bool tri_test_body(f3 p0, f3 p1, f3 p2, f3 o, const TravRay& ray, const TriRa
     e1 = diff_of_products_double(p2t.x, p0t.y, p2t.y, p0t.x);
     e2 = diff_of_products_double(p0t.x, p1t.y, p0t.y, p1t.x);
   }
-  const bool mixed = (e0 < 0 || e1 < 0 || e2 < 0) && (e0 > 0 || e1 > 0 || e2 > 0);
+  // (the comparisons combined with & and |, not && and ||: every one of them is evaluated whatever the others say,
+  // in the lane masks they leave; the short-circuit forms cost an exec-mask region each for out_neg and out_pos)
+  const bool mixed = ((e0 < 0) | (e1 < 0) | (e2 < 0)) & ((e0 > 0) | (e1 > 0) | (e2 > 0));
   const float det = e0 + e1 + e2;
   const float t_scaled = e0 * (p0t.z * rc.sz) + e1 * (p1t.z * rc.sz) + e2 * (p2t.z * rc.sz);
   const float hi = ray.max_t * det, lo = ray.min_t * det;
-  const bool out_neg = det < 0 && (t_scaled >= 0 || t_scaled < hi || t_scaled > lo);
-  const bool out_pos = det > 0 && (t_scaled <= 0 || t_scaled > hi || t_scaled < lo);
-  const bool hit = !mixed && !(det == 0) && !out_neg && !out_pos;
+  const bool out_neg = (det < 0) & ((t_scaled >= 0) | (t_scaled < hi) | (t_scaled > lo));
+  const bool out_pos = (det > 0) & ((t_scaled <= 0) | (t_scaled > hi) | (t_scaled < lo));
+  const bool hit = !(mixed | (det == 0) | out_neg | out_pos);
   if (hit) {
     const float inv_det = 1.f / det;
     t_out = t_scaled * inv_det;

@@ -67,6 +67,12 @@ VHD void bake_light_sphere(const VimgSphere& sp, DLight& L) {
 VHD uint32_t bake_material_class(uint32_t type) {
   return type == VIMG_MAT_DIFFUSE_LIGHT ? 0u : type == VIMG_MAT_LAMBERTIAN ? 1u : type == VIMG_MAT_PRINCIPLED ? 2u : 3u;
 }
+// whether the table holds a material of class 3, "other" (plain_build.h: PF_NO_OTHER asks)
+inline bool table_holds_other(const VimgMaterial* materials, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (bake_material_class(materials[i].type) == 3u) return true;
+  return false;
+}
 VHD uint32_t bake_material_flags(const VimgMaterial& m, const VimgTexture* textures) {
   uint32_t f = 0;
   if (m.type == VIMG_MAT_PRINCIPLED) f |= MATF_NEEDS_FRAME;

@@ -209,7 +209,10 @@ int enqueue_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan
 void commit_relight(VimgDeviceScene* s, const VimgGeometryUpdate* u, RelightPlan* plan) {
   DScene& d = s->d;
   if (u->textures) s->textures.assign(u->textures, u->textures + s->textures.size());
-  if (u->materials) s->materials.assign(u->materials, u->materials + s->materials.size());
+  if (u->materials) {
+    s->materials.assign(u->materials, u->materials + s->materials.size());
+    s->has_other = table_holds_other(s->materials.data(), s->materials.size());   // (a type may have changed: PF_NO_OTHER)
+  }
   if (u->background) {
     d.background = *u->background;
     d.background_emissive = background_is_emissive(d.background);

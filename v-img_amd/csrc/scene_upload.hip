@@ -437,6 +437,7 @@ int upload_tables(VimgDeviceScene* s, const VimgScene* sc, const Tree& t, const 
 // tables a material update is checked against
 void record_for_updates(VimgDeviceScene* s, const VimgScene* sc) {
   s->materials.assign(sc->materials, sc->materials + sc->num_materials);
+  s->has_other = table_holds_other(s->materials.data(), s->materials.size());
   s->textures.assign(sc->textures, sc->textures + sc->num_textures);
   s->lights.assign(sc->lights, sc->lights + sc->num_lights);
   s->num_rg_textures = sc->num_rg_textures;

@@ -412,6 +412,19 @@ int vimg_hip_time_renders(VimgDeviceScene* s, const VimgRenderParams* p, void* d
 int vimg_hip_probe(VimgDeviceScene* s, int kind, int n, const float* in_host, float* out_host) {
   static const int n_in[11] = {0, 4, 6, 7, 12, 8, 4, 5, 1, 8, 12};
   static const int n_out[11] = {0, 8, 28, 1, 5, 7, 10, 4, 5, 8, 8};
+  // 11 LAUNCH_BUILD (host only): in integrator samples depth tile_rank tile_world, out the fold of the PLAIN build a frame
+  // with these parameters is launched with (plain_build.h: a mask of PF_*; 0 = the general build, or no CU launch at all)
+  if (s && kind == 11 && n > 0 && in_host && out_host) {
+    for (int i = 0; i < n; ++i) {
+      const float* v = in_host + size_t(i) * 5;
+      const VimgRenderParams p{uint32_t(v[0]), uint32_t(v[1]), uint32_t(v[2]), uint32_t(v[3]), uint32_t(v[4])};
+      out_host[i] = 0.f;
+      if (p.tile_world == 0 || p.tile_rank >= p.tile_world || is_feature_integrator(p.integrator)) continue;
+      const LaunchCfg c = make_launch(s, &p, -1, -1);
+      if (!c.error && c.sched == VIMG_SCHED_CU) out_host[i] = float(plain_fold_of(s, c, false));
+    }
+    return VIMG_OK;
+  }
   if (!s || kind < 1 || kind > 10 || n <= 0 || !in_host || !out_host)
     return fail(VIMG_E_INVALID, "probe: bad arguments");
   DevBuf d_in, d_out;

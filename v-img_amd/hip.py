@@ -13,7 +13,8 @@ from .host import HostScene, camera_lookat, make_params
 
 
 # floats per item of DeviceScene.probe, kind -> (in, out): the n_in / n_out tables of vimg_hip_probe (csrc/vimg_hip.hip)
-PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 8: (1, 5), 9: (8, 8), 10: (12, 8)}
+PROBE_IO = {1: (4, 8), 2: (6, 28), 3: (7, 1), 4: (12, 5), 5: (8, 7), 6: (4, 10), 7: (5, 4), 8: (1, 5), 9: (8, 8), 10: (12, 8), 11: (5, 1)}
+PROBE_LAUNCH_BUILD = 11
 
 
 class HipError(RuntimeError):
@@ -306,6 +307,12 @@ class DeviceScene:
     def kernel_for(self, params):
         """Name of the kernel a launch with these parameters gets (the scheduler is chosen per launch)."""
         return self._lib.vimg_hip_launch_kernel(self._h, C.byref(params)).decode()
+
+    def plain_fold_for(self, params):
+        """The launch-constant options compiled into the build a frame with these parameters runs (probe 11: a mask of
+        plain_build.h's PF_* bits; 0 = the general build)."""
+        p = params
+        return int(self.probe(PROBE_LAUNCH_BUILD, [[p.integrator, p.samples, p.depth & 0xFFFFFF, p.tile_rank, p.tile_world]])[0, 0])
 
     def shard_pixels(self, params):
         return _check(self._lib.vimg_hip_shard_pixels(self._h, C.byref(params)))
