@@ -1,4 +1,4 @@
-# Build of the fourteen shared libraries (no cmake: plain make + hipcc/g++).
+# Build of the fifteen shared libraries (no cmake: plain make + hipcc/g++).
 #   v-img_amd/lib/libvimg_hip.so   hand-written gfx950 kernels + C ABI   (the product)
 #   v-img_amd/lib/libvimg_filter.so  scene-free filters over device frames (the a-trous denoiser)       }
 #   v-img_amd/lib/libvimg_temporal.so  scene-free temporal accumulation over device frames (reprojection) } the frame
@@ -11,6 +11,7 @@
 #   v-img_amd/lib/libvimg_despeckle.so  scene-free clamp of fireflies in a frame before it is filtered     }
 #   v-img_amd/lib/libvimg_exposure.so  scene-free histogram auto-exposure, its state in device memory     }
 #   v-img_amd/lib/libvimg_demand.so  scene-free sampling mask of a sparse preview, from the history's lengths }
+#   v-img_amd/lib/libvimg_rectify.so  scene-free clamp of a long history to a short history beside it      }
 #   v-img_amd/lib/libvimg_host.so  host side: scene loading, SAH BVH, post (the product's host)
 #   oracle/liboracle.so            CPU restatement of the reference path  (test infrastructure)
 ROOT    := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
@@ -34,6 +35,7 @@ FRAMELIBS += motion
 FRAMELIBS += despeckle
 FRAMELIBS += exposure
 FRAMELIBS += demand
+FRAMELIBS += rectify
 
 # -ffp-contract=off everywhere: +,-,*,/,sqrt must round identically on CPU and GPU; fused
 # multiply-adds appear only where the reference writes std::fma.
@@ -75,7 +77,7 @@ $(LIBDIR)/libvimg_hip.so: $(HIPOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIPOBJ) -o $@
 
-# the frame libraries (DESIGN.md 4.18 - 4.24, 4.26, 4.28, 4.30, 4.31, 4.32), one per name in FRAMELIBS: libvimg_<name>.so from its own sources
+# the frame libraries (DESIGN.md 4.18 - 4.24, 4.26, 4.28, 4.30, 4.31, 4.32, 4.33), one per name in FRAMELIBS: libvimg_<name>.so from its own sources
 # v-img_amd/<name>/*.hip (NOT the csrc wildcard of libvimg_hip.so), the shared host skeleton v-img_amd/frames/*.h and
 # the public headers; each links the HIP runtime and nothing of the other libraries.  The same HIPFLAGS: their
 # bit-level contracts rest on -ffp-contract=off, -fno-fast-math and hipcc's correctly rounded divide.  No

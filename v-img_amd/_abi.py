@@ -1,6 +1,7 @@
 """ctypes mirror of include/vimg_scene.h, include/vimg_host.h, include/vimg_hip.h, include/vimg_filter.h,
 include/vimg_temporal.h, include/vimg_varfilter.h, include/vimg_moments.h, include/vimg_infill.h, include/vimg_wtemporal.h,
-include/vimg_antilag.h, include/vimg_motion.h, include/vimg_despeckle.h, include/vimg_exposure.h and include/vimg_demand.h.
+include/vimg_antilag.h, include/vimg_motion.h, include/vimg_despeckle.h, include/vimg_exposure.h, include/vimg_demand.h and
+include/vimg_rectify.h.
 
 Only declarations live here: struct layouts, library loading and argtypes.  The product
 libraries are loaded from ``v-img_amd/lib`` (built in-tree by ``make``); a missing library is an
@@ -580,6 +581,32 @@ DEMAND_SYMBOLS = {
 }
 
 
+class RectifyFrames(_Sized, C.Structure):
+    """VimgRectifyFrames (include/vimg_rectify.h): the long and the short history of one picture and its albedo frame."""
+    _fields_ = [("struct_size", u32), ("width", u32), ("height", u32), ("reserved", u32), ("slow", C.c_void_p),
+                ("fast", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+class RectifyParams(_Sized, C.Structure):
+    """VimgRectifyParams (include/vimg_rectify.h); vimg_rectify_defaults fills it."""
+    _fields_ = [("struct_size", u32), ("radius", u32), ("min_taps", u32), ("reserved", u32), ("k", f32), ("cut", f32),
+                ("sigma_normal", f32), ("sigma_plane", f32), ("albedo_floor", f32)]
+
+
+RECTIFY_MAX_RADIUS = 3
+RECTIFY_KEPT, RECTIFY_CLAMPED, RECTIFY_FEW_TAPS, RECTIFY_NOT_LIVE = 0, 1, 2, 3
+
+# the list of symbols include/vimg_rectify.h declares: libvimg_rectify.so, the clamp of a long history (the first three
+# planes: TEMPORAL_HISTORY_PER_PIXEL) to a short history beside it
+RECTIFY_SYMBOLS = {
+    "vimg_rectify_defaults": (None, [C.POINTER(RectifyParams)]),
+    "vimg_rectify_workspace": (C.c_uint64, [u32, u32]),
+    "vimg_rectify_clamp": (C.c_int, [C.POINTER(RectifyFrames), C.POINTER(RectifyParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p]),
+    "vimg_rectify_last_error": (C.c_char_p, []),
+}
+
+
 def _bind(lib, table):
     for name, (res, args) in table.items():
         fn = getattr(lib, name)
@@ -609,6 +636,7 @@ _LATER_LIBRARIES = {
     "despeckle": ("libvimg_despeckle.so", (DESPECKLE_SYMBOLS,), "despeckle", "; there is no CPU fallback for the clamp", True),
     "exposure": ("libvimg_exposure.so", (EXPOSURE_SYMBOLS,), "exposure", "; there is no CPU fallback for the exposure", True),
     "demand": ("libvimg_demand.so", (DEMAND_SYMBOLS,), "demand", "; there is no CPU fallback for the sampling mask", True),
+    "rectify": ("libvimg_rectify.so", (RECTIFY_SYMBOLS,), "rectify", "; there is no CPU fallback for the history clamp", True),
 }
 _loaded = {}
 
@@ -696,3 +724,8 @@ def exposure_lib():
 def demand_lib():
     """The library that says which pixels of a sparse preview to sample now (include/vimg_demand.h)."""
     return _load("demand")
+
+
+def rectify_lib():
+    """The library that clamps a long history to a short history beside it (include/vimg_rectify.h)."""
+    return _load("rectify")

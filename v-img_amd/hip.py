@@ -373,14 +373,15 @@ class DeviceScene:
         return preview.expose(preview.denoise(noisy, guides, variance_guided, out=out, stream=stream, **filter_kw), exposed, stream=stream)
 
     def temporal_preview(self, params, samples=4, denoise=True, feature_samples=4, variance_guided=False, sparse=None,
-                         fill_weight=None, antilag=False, motion=None, despeckle=None, exposure=None, demand=None, **temporal_kw):
+                         fill_weight=None, antilag=False, motion=None, despeckle=None, exposure=None, demand=None, rectify=None,
+                         **temporal_kw):
         """A preview that survives a moving camera: a vimg_amd.preview.TemporalPreview of this scene, which tells what its
         ``frame()`` returns and what every argument chooses (``temporal_kw`` also carries ``filter_kw`` and
         ``scale_sigma_color``).  Whole frames only."""
         from . import preview
         return preview.TemporalPreview(self, params, samples=samples, denoise=denoise, feature_samples=feature_samples,
                                        variance_guided=variance_guided, sparse=sparse, fill_weight=fill_weight, antilag=antilag,
-                                       motion=motion, despeckle=despeckle, exposure=exposure, demand=demand, **temporal_kw)
+                                       motion=motion, despeckle=despeckle, exposure=exposure, demand=demand, rectify=rectify, **temporal_kw)
 
     def render_sparse(self, params, stride=2, **kw):
         """A sparse preview in one call: a fresh accumulator, one ``Progressive.render_sparse(params.samples, stride,

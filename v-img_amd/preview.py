@@ -1,6 +1,6 @@
 """The previews of a resident scene, composed from the frame libraries: ``denoise``, the filter choice of
 every preview, and TemporalPreview, whose frame() is one straight line over parts chosen once - an increment, an
-accumulation, a filter, and the options despeckle, anti-lag, motion, exposure and demand.  A part owns its buffers and its state and
+accumulation, a filter, and the options despeckle, anti-lag, motion, exposure, demand and rectify.  A part owns its buffers and its state and
 imports the libraries it needs and no others; a new mode is a new part and one line of TemporalPreview.__init__.  There
 is no CPU fallback."""
 import math
@@ -379,6 +379,69 @@ class _Motion:
         return self.previous
 
 
+FAST_HISTORY = 2.0      # _Rectify's default fast_history, by the sweep of DESIGN.md 4.33
+
+
+def rectify_kw(given, what):
+    """The ``rectify`` argument of a preview (``what`` names it in a refusal): None or False - no clamp, None is
+    returned; True - the defaults, (FAST_HISTORY, {}); a dict - ``fast_history`` and rectify.params' keywords, checked
+    here.  Returns (fast_history, the library's keywords)."""
+    if given is None or given is False:
+        return None
+    if given is not True and not isinstance(given, dict):
+        raise ValueError(f"{what}: rectify must be None, a bool or a dict of fast_history and vimg_amd.rectify's parameters, "
+                         f"not {type(given).__name__}")
+    from . import rectify
+    kw = {} if given is True else dict(given)
+    fast_history = kw.pop("fast_history", None)
+    fast_history = FAST_HISTORY if fast_history is None else float(fast_history)
+    if not 1.0 <= fast_history < math.inf:
+        raise ValueError(f"{what}: rectify's fast_history must be >= 1 and finite, not {fast_history:g}")
+    rectify.params(**kw)             # (refuses an unknown name now)
+    return fast_history, kw
+
+
+class _Rectify:
+    """``rectify`` (True: the defaults; a dict: ``fast_history`` and rectify.clamp's parameters): beside
+    the history of up to max_history frames a second one of ``fast_history`` frames (default FAST_HISTORY) is kept - the
+    same temporal.accumulate call on the same colour, guides, position frame, current_weight and matrix, with
+    max_history = fast_history, on two buffers of this part's own that freeze and swap exactly as the slow ones do -
+    and right after the accumulation (with ``motion``: after plane G1 has its current positions back, which the fast
+    history's G1 gets as well) the slow history's colour is clamped IN PLACE to the fast one's statistics around each
+    pixel (vimg_amd.rectify, include/vimg_rectify.h), with the albedo frame for demodulation; the clamped colour is
+    what the filter and the exposure then see and what frame() returns.  The slow accumulate call is then given no
+    picture to write - the increment must reach the fast call as it was rendered - and the clamp writes the picture.  The fast history is always a temporal.History,
+    also with ``variance_guided``, whose plane M stays what it is.  Stale radiance - an edit that ``antilag`` does not
+    see, a moved object's shading, view-dependent shading - is then bounded within about fast_history frames.
+    ``last_rectify_code`` is the [H, W] uint8 code frame of the last call.  The accumulator stays bit for bit a
+    Progressive.  It is refused with ``sparse``: a filled pixel's weight would have to enter the fast history as well."""
+
+    def __init__(self, dev, fast_history, kw):
+        self.params, self.fast_history = kw, fast_history
+        w, h = dev.resolution
+        self._buffers = [_empty("float32", 3, h, w, 4) for _ in range(2)]
+        self._code = _empty("uint8", h, w)
+        self.reset()
+
+    def reset(self):
+        self._frozen = self.fast = None     # the fast History frozen at the last change, and the last frame()'s
+        self._write = 0
+        self.last_code = None               # last_rectify_code
+
+    def __call__(self, froze, k, mean, g, position, moved, slow, target, matrix, sigmas, stream):
+        from . import rectify
+        if froze:
+            self._frozen, self._write = self.fast, 1 - self._write
+        self.fast = accumulate(mean, g["normal"], position, g["depth"], history=self._frozen, world_to_pixel=matrix,
+                               next_history=self._buffers[self._write], stream=stream, current_weight=k,
+                               max_history=self.fast_history, **sigmas)
+        if moved:
+            import torch
+            with torch.cuda.stream(stream):
+                self.fast.tensor[2, :, :, :3].copy_(g["position"])
+        self.last_code = rectify.clamp(slow, self.fast, albedo=g["albedo"], out=target, code=self._code, stream=stream, **self.params)[2]
+
+
 class TemporalPreview:
     """The preview of a resident scene whose camera moves (DeviceScene.temporal_preview): one Progressive, two history
     buffers and the a-trous workspace.  ``frame()`` returns the [H, W, 3] preview of the scene as it now stands.
@@ -393,7 +456,7 @@ class TemporalPreview:
     The modes are parts of this module, chosen once here, and each tells its own contract: ``denoise`` and
     ``scale_sigma_color`` in _fixed_filter, ``variance_guided`` in _moments_accumulation, ``sparse`` and ``fill_weight``
     in _SparseIncrement, ``demand`` in _DemandIncrement, ``despeckle`` in _Despeckle, ``antilag`` in _Antilag, ``motion`` in _Motion, ``exposure`` in
-    _Exposure.
+    _Exposure, ``rectify`` in _Rectify.
 
     Limits: without ``antilag``, history from before a material edit is reprojected all the same and fades at
     1 / max_history per frame (``reset()`` drops all of it), and so is history from before a geometry edit, which
@@ -411,10 +474,11 @@ class TemporalPreview:
     last_motion_code, _previous = _of("_motion", "last_code"), _of("_motion", "previous")
     exposure, exposure_state = _of("_expose", "params"), _of("_expose", "state")
     demand, last_demand = _of("_increment", "demand"), _of("_increment", "last")
+    rectify, fast_history, last_rectify_code = _of("_rectify", "params"), _of("_rectify", "fast_history"), _of("_rectify", "last_code")
 
     def __init__(self, dev, params, samples=4, denoise=True, feature_samples=4, filter_kw=None, scale_sigma_color=None,
                  variance_guided=False, sparse=None, fill_weight=None, antilag=False, motion=None, despeckle=None, exposure=None,
-                 demand=None, **temporal_kw):
+                 demand=None, rectify=None, **temporal_kw):
         if params.tile_world != 1:
             raise ValueError("temporal_preview: reprojection reads whole frames, not shards (tile_world must be 1)")
         if int(samples) < 1 or int(feature_samples) < 1:
@@ -435,7 +499,11 @@ class TemporalPreview:
         demanded = demand_kw(demand, "temporal_preview")
         if demanded is not None and sparse is None:
             raise ValueError("temporal_preview: demand chooses the pixels a sparse frame samples: it needs sparse")
+        rectified = rectify_kw(rectify, "temporal_preview")
+        if rectified is not None and sparse is not None:
+            raise ValueError("temporal_preview: rectify does not go with sparse: a filled pixel's weight would have to enter the fast history too")
         sigmas = {k: temporal_kw[k] for k in ("sigma_normal", "sigma_plane") if k in temporal_kw}
+        self._sigmas = sigmas
         self._increment = (_full_increment if sparse is None else _SparseIncrement(dev, sparse, fill_weight) if demanded is None else
                            _DemandIncrement(dev, sparse, fill_weight, demanded, sigmas))
         self._ask = getattr(self._increment, "ask", _absent)
@@ -450,7 +518,7 @@ class TemporalPreview:
         w, h = dev.resolution
         self._buffers = [_empty("float32", 4 if self.variance_guided else 3, h, w, 4) for _ in range(2)]
         self._variance = _empty("float32", h, w) if self.variance_guided else None
-        self._features = GUIDES if denoise or sparse is not None or clamp is not None else ("normal", "position", "depth")
+        self._features = GUIDES if denoise or sparse is not None or clamp is not None or rectified is not None else ("normal", "position", "depth")
         max_history = float(temporal_params(max_history=temporal_kw.get("max_history")).max_history)
         self._filter = (_no_filter if not denoise else _variance_filter(dev, self.filter_kw, self._variance) if self.variance_guided else
                         _fixed_filter(dev, self.filter_kw, self.scale_sigma_color, max_history))
@@ -458,7 +526,8 @@ class TemporalPreview:
         self._cut = _absent if antilag is False or antilag is None else _Antilag(dev, antilag)
         self._motion = _absent if motion is None else _Motion(dev, motion)
         self._expose = _linear if exposed is None else _Exposure(dev, exposed)
-        self._resets = [part.reset for part in (self._increment, self._cut, self._motion, self._expose) if hasattr(part, "reset")]
+        self._rectify = _absent if rectified is None else _Rectify(dev, *rectified)
+        self._resets = [part.reset for part in (self._increment, self._cut, self._motion, self._expose, self._rectify) if hasattr(part, "reset")]
         self._guides = GuideCache(dev)
         self.reset()
 
@@ -492,13 +561,17 @@ class TemporalPreview:
             self._cut(mean, g, self._frozen, stream)
         self._k += 1
         target = mean if out is None else out
-        self.history = self._accumulate(acc, self._k, mean, g, g["position"] if previous is None else previous, weight, self._variance,
-                                        history=self._frozen, world_to_pixel=world_to_pixel(dev.camera), out=target,
+        position, matrix, rectified = g["position"] if previous is None else previous, world_to_pixel(dev.camera), self._rectify is not _absent
+        # with ``rectify`` the accumulate call writes no picture - the increment stays what it is for the fast history - and
+        # the clamp writes ``target`` from the history it has clamped
+        self.history = self._accumulate(acc, self._k, mean, g, position, weight, self._variance,
+                                        history=self._frozen, world_to_pixel=matrix, out=None if rectified else target,
                                         next_history=self._buffers[self._write], stream=stream, **self.temporal_kw)
         if previous is not None:       # the accumulate call was given Q: plane G1 of the history it wrote gets the CURRENT positions
             import torch
             with torch.cuda.stream(stream):
                 self.history.tensor[2, :, :, :3].copy_(g["position"])
+        self._rectify(froze, self._k, mean, g, position, previous is not None, self.history, target, matrix, self._sigmas, stream)
         self._frames += 1
         return self._expose(self._filter(target, g, self._frames, stream), stream)
 
