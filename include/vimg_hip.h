@@ -384,7 +384,10 @@ int vimg_hip_time_renders(VimgDeviceScene* scene, const VimgRenderParams* params
  * (src/tonemap/reinhard.cpp), 3 ACES (src/tonemap/aces.cpp); then sRGB_gamma_correction
  * (include/color_utils.h:45-68) and the 8-bit quantisation with NaN -> magenta.
  * d_rgb: DEVICE, w*h float triples; d_rgb8: DEVICE, w*h byte triples.  Saves the 12 B/pixel
- * download when only the picture is wanted. */
+ * download when only the picture is wanted.
+ * Known limit: Reinhard's largest luminance is reduced into ONE device word of the process, reset and
+ * read by each call on its own stream.  Calls with tonemapper 2 that run concurrently on different
+ * streams share that word and may read each other's maximum; serialise them. */
 int vimg_hip_post_rgb8(const void* d_rgb, int w, int h, int tonemapper, void* d_rgb8,
                        void* stream);
 

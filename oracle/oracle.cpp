@@ -1844,11 +1844,10 @@ inline float srgb_oetf(float x) {
   if (x < 0.0031308f) return x * 12.92f;
   return 1.055f * F_pow(x, 1.0f / 2.4f) - 0.055f;
 }
-}  // namespace
-extern "C" {
-
-int oracle_post_rgb8(const float* rgb, int w, int h, int tonemapper, uint8_t* out) {
-  if (!rgb || !out || w <= 0 || h <= 0 || tonemapper < 0 || tonemapper > 3) return -1;
+// the chain up to and including the OETF, once for both entry points: `emit(i, c)` takes pixel i's three floats
+template <class Emit>
+int post_chain(const float* rgb, int w, int h, int tonemapper, Emit emit) {
+  if (!rgb || w <= 0 || h <= 0 || tonemapper < 0 || tonemapper > 3) return -1;
   const size_t n = static_cast<size_t>(w) * h;
   float largest_L = 0.0f;
   if (tonemapper == 2)
@@ -1870,7 +1869,16 @@ int oracle_post_rgb8(const float* rgb, int w, int h, int tonemapper, uint8_t* ou
       }
       default: c = aces_pixel(c); break;
     }
-    c = vec3{srgb_oetf(c.x), srgb_oetf(c.y), srgb_oetf(c.z)};
+    emit(i, vec3{srgb_oetf(c.x), srgb_oetf(c.y), srgb_oetf(c.z)});
+  }
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+int oracle_post_rgb8(const float* rgb, int w, int h, int tonemapper, uint8_t* out) {
+  if (!out) return -1;
+  return post_chain(rgb, w, h, tonemapper, [out](size_t i, vec3 c) {
     uint8_t* o = out + 3 * i;
     if (std::isnan(c.x) || std::isnan(c.y) || std::isnan(c.z)) {
       o[0] = 255, o[1] = 0, o[2] = 255;
@@ -1879,8 +1887,14 @@ int oracle_post_rgb8(const float* rgb, int w, int h, int tonemapper, uint8_t* ou
       o[1] = static_cast<uint8_t>(clampi(static_cast<int>(255.999 * c.y), 0, 255));
       o[2] = static_cast<uint8_t>(clampi(static_cast<int>(255.999 * c.z), 0, 255));
     }
-  }
-  return 0;
+  });
+}
+
+int oracle_post_float(const float* rgb, int w, int h, int tonemapper, float* out_float) {
+  if (!out_float) return -1;
+  return post_chain(rgb, w, h, tonemapper, [out_float](size_t i, vec3 c) {
+    out_float[3 * i + 0] = c.x, out_float[3 * i + 1] = c.y, out_float[3 * i + 2] = c.z;
+  });
 }
 
 int oracle_uses_float_libm(void) {

@@ -45,6 +45,8 @@ def load(name="liboracle.so"):
         lib.oracle_heatmap.argtypes = [abi.PScene, abi.PParams, C.c_float, C.c_int, abi.Pf32, abi.Pf32]
         lib.oracle_post_rgb8.restype = C.c_int
         lib.oracle_post_rgb8.argtypes = [abi.Pf32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+        lib.oracle_post_float.restype = C.c_int
+        lib.oracle_post_float.argtypes = [abi.Pf32, C.c_int, C.c_int, C.c_int, abi.Pf32]
         _libs[name] = lib
     return _libs[name]
 
@@ -128,4 +130,15 @@ def post_rgb8(image, tonemapper, lib=None):
     if lib.oracle_post_rgb8(img.ctypes.data_as(abi.Pf32), img.shape[1], img.shape[0], tonemapper,
                             out.ctypes.data_as(C.POINTER(C.c_uint8))):
         raise RuntimeError("oracle_post_rgb8 rejected its arguments")
+    return out
+
+
+def post_float(image, tonemapper, lib=None):
+    """The three floats of every pixel after the OETF, before the quantiser (a NaN kept)."""
+    lib = lib or load()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    out = np.empty(img.shape, dtype=np.float32)
+    if lib.oracle_post_float(img.ctypes.data_as(abi.Pf32), img.shape[1], img.shape[0], tonemapper,
+                             out.ctypes.data_as(abi.Pf32)):
+        raise RuntimeError("oracle_post_float rejected its arguments")
     return out

@@ -49,6 +49,33 @@ def test_an_output_buffer_is_refused_in_one_sentence(no_upload):
             hip._device_tensor(out, "trace_rays", F32, (4, 4), aligned=True, out=True)
 
 
+POST_REFUSED = {
+    "cpu tensor": (lambda: torch.zeros((4, 8, 3)), 1, "post_rgb8 image: the tensor must be on the current CUDA device"),
+    "float64 tensor": (lambda: torch.zeros((4, 8, 3), dtype=torch.float64), 1, "post_rgb8 image: dtype must be float32, not torch.float64"),
+    "float64 numpy": (lambda: np.zeros((4, 8, 3), np.float64), 1, "post_rgb8 image: dtype must be float32, not float64"),
+    "non-contiguous view": (lambda: torch.zeros((8, 4, 3)).transpose(0, 1), 1, "post_rgb8 image: the tensor must be"),
+    "four channels": (lambda: np.zeros((4, 8, 4), np.float32), 1, r"post_rgb8 image: shape must be \(H, W, 3\), not \(4, 8, 4\)"),
+    "four channels, tensor": (lambda: torch.zeros((4, 8, 4)), 1, r"post_rgb8 image: shape must be \(H, W, 3\), not \(4, 8, 4\)"),
+    "no rows": (lambda: np.zeros((0, 8, 3), np.float32), 1, r"post_rgb8 image: shape must be \(H, W, 3\), not \(0, 8, 3\)"),
+    "python list": (lambda: [[[0.0] * 3] * 8] * 4, 1, "post_rgb8 image: shape must be"),
+    "operator 4": (lambda: np.zeros((4, 8, 3), np.float32), 4, "post_rgb8: tonemapper must be 0 .* not 4"),
+    "operator -1": (lambda: np.zeros((4, 8, 3), np.float32), -1, "post_rgb8: tonemapper must be 0 .* not -1"),
+    "operator 1.5": (lambda: np.zeros((4, 8, 3), np.float32), 1.5, "post_rgb8: tonemapper must be 0 .* not 1.5"),
+}
+
+
+@pytest.mark.parametrize("case", list(POST_REFUSED))
+def test_post_rgb8_refuses_before_the_gpu_is_touched(case, no_upload, monkeypatch):
+    """hip.post_rgb8 goes through the same check as every other launch: nothing is copied, CUDA is not initialised
+    and the library is not called (it is not even loaded)."""
+    def no_library():
+        raise AssertionError("the library was called")
+    monkeypatch.setattr(hip, "_lib", no_library)
+    make, tonemapper, words = POST_REFUSED[case]
+    with pytest.raises(ValueError, match=words):
+        hip.post_rgb8(make(), tonemapper)
+
+
 def test_a_numpy_bool_mask_passes_the_host_checks_and_goes_up_as_uint8(monkeypatch):
     sent = []
 

@@ -919,15 +919,22 @@ class Progressive:
 
 
 def post_rgb8(image, tonemapper=1, stream=None):
-    """Tonemap + sRGB + 8-bit quantise a [H, W, 3] float32 CUDA tensor on the GPU
-    (vimg_hip_post_rgb8); returns a [H, W, 3] uint8 CUDA tensor."""
+    """Tonemap (0 clamp, 1 AgX, 2 Reinhard, 3 ACES) + sRGB + 8-bit quantise a [H, W, 3] float32 frame on the GPU
+    (vimg_hip_post_rgb8): a contiguous CUDA tensor on the current device gives a [H, W, 3] uint8 CUDA tensor, a numpy
+    frame is copied up and its bytes come back as numpy."""
     import torch
-    h, w = image.shape[0], image.shape[1]
-    out = torch.empty((h, w, 3), dtype=torch.uint8, device=image.device)
-    with _Launch(stream, made=[out], used=[image]) as sp:
-        _check(_lib().vimg_hip_post_rgb8(C.c_void_p(image.data_ptr()), w, h, tonemapper,
-                                         C.c_void_p(out.data_ptr()), sp))
-    return out
+    if isinstance(tonemapper, bool) or not isinstance(tonemapper, (int, np.integer)) or not 0 <= tonemapper <= 3:
+        raise ValueError(f"post_rgb8: tonemapper must be 0 (clamp), 1 (AgX), 2 (Reinhard) or 3 (ACES), not {tonemapper!r}")
+    shape = getattr(image, "shape", None)
+    if shape is None or len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"post_rgb8 image: shape must be (H, W, 3), not {None if shape is None else tuple(shape)}")
+    h, w = int(shape[0]), int(shape[1])
+    ts = _Tensors(to_host=not isinstance(image, torch.Tensor))
+    frame = ts.take(image, "post_rgb8 image", ("float32",), (h, w, 3))
+    out = ts.output(None, "post_rgb8 out", "uint8", (h, w, 3))
+    with ts.launch(stream) as sp:
+        _check(_lib().vimg_hip_post_rgb8(_ptr(frame), w, h, int(tonemapper), _ptr(out), sp))
+    return ts.result(out)
 
 
 __all__ = ["DeviceScene", "Progressive", "RayHits", "post_rgb8", "HipError", "device_count", "init", "make_params"]
