@@ -75,7 +75,7 @@ typedef struct VimgHipOptions {
   int32_t lds_stack;          /* CU: entries of a lane's traversal stack kept in LDS, the rest in global memory.  AUTO 32 (fewer where the LDS asks for it); a value no launch fits is VIMG_E_INVALID at the render */
   int32_t pool_gbreak;        /* accepted and ignored */
   int32_t cu_waves;           /* CU: reserved; one 16-wave workgroup is a whole compute unit (12 waves at 168 registers measured slower) */
-  int32_t cu_walkers;         /* CU: waves of the 16 that walk (the rest only shade).  AUTO: 9 on trees in LDS, 10 on trees in global memory, all 16 when every pixel of the launch owns a slot (tree in LDS) */
+  int32_t cu_walkers;         /* CU: waves of the 16 that walk (the rest only shade).  AUTO: 8 on trees in LDS, 10 on trees in global memory, all 16 when every pixel of the launch owns a slot (tree in LDS) */
   int32_t cu_flex;            /* CU: bit 0: a walking wave that holds no ray may run a vertex batch; bit 4 (16): no split batches (the two BSDF evaluations of a vertex on the two halves of the wave when a batch has <= 32 slots); bit 5 (32): EARLY rays - a vertex stage queues its shadow ray right after the light sample and its path ray right after the BSDF sample and finishes (evaluations, stores) beside their walks; bits 1, 2: shading / walking at wave priority 1 (measurements).  AUTO 1, + 32 on launches of fewer than three pools' worth of pixels and on trees in global memory */
   int32_t cu_lowwater;        /* CU: partial vertex batches run only while fewer rays than this wait in the walk ring.  AUTO 64 */
   int32_t cu_patience;        /* CU: looks in vain after which a wave takes a partial batch of any size.  AUTO 4 */

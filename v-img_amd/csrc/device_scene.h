@@ -208,7 +208,8 @@ struct RenderArgs {
 struct DeviceStats {
   unsigned long long closest, shadow, internal, leaf, prim, sphere, nan_samples;
   unsigned long long trip_descend, trip_prim, iterations;   // wave-level loop trips (diagnostic)
-  // render_cu_kernel, statistics launches: per stage cycles [0..5], batches [6..10] and their slots [11..15];
+  // render_cu_kernel, statistics launches: per stage cycles [0..5], batches [6..9], waves [10] and the batches' slots [11..14];
+  // shadow rays whose light sample adds exactly zero, which a late build does not queue [15];
   // the walk's passes, rounds, sessions and refills [16..22]; looks for work and the ring counts seen [23..27]
   unsigned long long prof[28];
   unsigned long long wait_cyc[5], wait_n[5];   // render_cu_kernel, statistics launches: cycles slots waited in the rings (vertex 0-3, walk), and how many

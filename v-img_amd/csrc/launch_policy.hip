@@ -110,11 +110,13 @@ LaunchCfg cu_launch_with(const VimgDeviceScene* s, const VimgRenderParams* p, in
   // the build with the overflow path and the global node fetch serves both trees beyond the LDS
   // node cache and stacks deeper than their LDS rows
   c.deep = a.lds_nodes < s->d.num_nodes || a.stack_lds < a.stack_entries;
-  // walking waves (profiles/r3_cu/sweeps.txt): trees in LDS 9 of 16 (config 2 at 512 spp: 8 waves 307,
-  // 9: 304, 10: 325, 11: 337 ms), trees in global memory 10 (stand-ins of configs 4 / 5 at 32 spp:
+  // walking waves: trees in LDS 8 of 16.  It was 9 (profiles/r3_cu/sweeps.txt, config 2 at 512 spp: 8 waves 307,
+  // 9: 304, 10: 325, 11: 337 ms) until the late builds stopped walking shadow rays whose light sample adds zero
+  // (render_cu_kernel.h: ELIDE): 7 % fewer rays for the same shading, and 8: 243.0, 9: 258.1, 10: 267.5 ms
+  // (profiles/r9_nee_elide/); trees in global memory 10 (stand-ins of configs 4 / 5 at 32 spp:
   // 8 waves 2 650 / 3 436, 10: 2 796 / 4 019, 12: 2 649 / 3 762 Mrays/s); when every wave walks, every
   // wave must be allowed to shade too
-  a.cu_walkers = std::min(nw, std::max(1u, opt_or(o.cu_walkers, c.deep ? 10u : 9u)));
+  a.cu_walkers = std::min(nw, std::max(1u, opt_or(o.cu_walkers, c.deep ? 10u : 8u)));
   // finished rays that send a walking wave to its rings (hand-over, then refill): 16 on trees in LDS; on
   // trees in global memory, where a pass waits for memory and a finished ray would wait with it, 2
   // (stand-ins of configs 4 / 5: an eighth of the frame at 128 spp 82.8 / 77.9 against 93.3 / 82.3 ms,

@@ -123,7 +123,8 @@ static_assert(sizeof(CuCtl) == 96, "CuCtl layout");
 struct CuWaveRec {
   unsigned long long cyc[6], nbatch[4], nslots[4];
   uint32_t internal, leaf, prim, sphere;
-  unsigned long long box_pass, box_lanes, leaf_round, leaf_lanes, sessions, refills, refill_rays, pad;
+  unsigned long long box_pass, box_lanes, leaf_round, leaf_lanes, sessions, refills, refill_rays;
+  unsigned long long would_elide;   // shadow rays whose light sample adds exactly zero (cu_vertex: a late build does not queue them)
   unsigned long long looks, q_sum[4];   // looks of the main loop and the ring counts they saw (finisher, Lambertian, Principled, walk)
   unsigned long long w_cyc[4];          // cycles of a walk session: refill + set-up, box loop, leaf rounds, hand-over
   unsigned long long wait_cyc[5], wait_n[5];   // cycles slots spent in the rings (vertex 0-3, walk) and how many
@@ -423,14 +424,19 @@ VD CuKPtr cu_kargs() {
     return got_;                                                                                                        \
   }
 
+// All three components are +0 or -0: one test of the words - +-0 are the only values whose bits below the sign are
+// all clear, so a NaN or a subnormal component is not zero (cu_vertex: ELIDE, and the statistics build's count of it)
+VD bool adds_exactly_zero(const f3& c) { return ((__float_as_uint(c.x) | __float_as_uint(c.y) | __float_as_uint(c.z)) << 1) == 0u; }
+
 // ======================================================================== one vertex batch
 // (FIN: the finisher queue, MTC: material the shading
 // is specialised for, -1 = any).  `n` slots; lane i < n holds its slot id in `slot`.
-template <bool TEX, int NW, bool DIAG, int EARLY, bool FIN, int MTC, uint32_t PLAIN>
-VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan, uint32_t& n_dead) {
+template <bool TEX, int NW, bool DIAG, int EARLY, bool FIN, int MTC, uint32_t PLAIN, bool ELIDE>
+VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan, uint32_t& n_dead, uint32_t& n_elided) {
   const CuKPtr K = cu_kargs();
   CU_STAGE_LOCALS(K);
   constexpr bool finisher_batch = FIN;
+  // (ELIDE: this build does not queue shadow rays whose light sample adds exactly zero, below)
   // A batch of at most 32 slots of a material whose two BSDF evaluations are worth it runs SPLIT: lanes
   // 32-63 shadow lanes 0-31 (same slot, same loads, same draws, same arithmetic) up to the two
   // evaluations of a vertex - towards the light and along the sampled direction, independent of each
@@ -615,6 +621,7 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
   bool has_s = false, has_r = false;
   bool early = false, pushed_r = false;   // EARLY launches: this lane queues its rays before the end of the stage / has queued its path ray
   bool rec_written = false;               // this lane's rays are in the slot's record already (a vertex of the mis integrator)
+  [[maybe_unused]] bool elided = false;   // ELIDE builds: this lane's shadow ray is not queued (its light sample adds exactly zero)
   f3 shadow_d{0.f, 0.f, 1.f}, nee_contrib{0.f, 0.f, 0.f};
   float shadow_max_t = 0.f;
   // (a finisher batch never holds a vertex to shade: the walk sends every hit on a non-emitter to
@@ -825,12 +832,32 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
           prev_pdf = pdf_s;
         }
       }
-      has_s = nee;
+      // A light sample that adds exactly (0, 0, 0) - the one-sided emitter seen from behind, a light below the
+      // surface's horizon, the pdf_l == 0 / NaN case above - needs no occlusion answer: that answer decides between
+      // `result + 0` and `result`.  `result` starts at +0 and is only ever assigned or added to; in round to nearest
+      // a sum is -0 only if both operands are, so `result` is never -0 and `result + (+-0)` has its bits, component by
+      // component: the sample is the reference's whether the ray is walked or not.  The compare is
+      // exact and per component - a NaN compares false, its ray is kept, a NaN sample stays one - and the evaluation
+      // above is never skipped (0 x inf must still come out NaN).  A build that queues its rays LATE knows the
+      // contribution before push_rays and does not queue such a ray (ELIDE: no SC_NEE store, no CF_HAS_S, no join);
+      // the reference traced it, so it is counted (n_elided).  EARLY builds have queued it already; the statistics
+      // build walks it - its node and primitive counts are the reference's - and only counts what a late build saves.
+      if constexpr (ELIDE) {
+        // (owner lanes only are counted - a mirror lane of a split batch has evaluated nothing towards the light)
+        const bool adds_zero = nee && adds_exactly_zero(nee_contrib);
+        has_s = nee && !adds_zero;
+        elided = adds_zero && !mirror;
+      } else {
+        has_s = nee;
+      }
       has_r = sc.valid;
       primary = false;
       if (!has_s && !has_r) finish = true;
     }
   }
+  // counted per wave, from the ballot, where every lane of the wave is back (as n_nan and n_dead are: the flush reads
+  // one lane's copy of a count that must be the wave's)
+  if constexpr (ELIDE && !FIN) n_elided += static_cast<uint32_t>(__popcll(__ballot(elided)));
 
   // ---- finished samples: accumulate, pixel write-back, next pixel, next camera ray
   bool need_pixel = fresh;
@@ -1013,6 +1040,13 @@ VD void cu_vertex(uint32_t n, uint32_t slot, bool& all_pending, uint32_t& n_nan,
       *reinterpret_cast<VIMG_GLOBAL v2u*>(cold + (slot * SC4_MAIN + SC4_RNG)) = v2u{static_cast<uint32_t>(rng.s), static_cast<uint32_t>(rng.s >> 32)};
     }
     if (has_s) cwr(SC_NEE, slot, v4u{fu(nee_contrib.x), fu(nee_contrib.y), fu(nee_contrib.z), 0u});
+    // the statistics build walks every shadow ray and counts here, where the contribution leaves the registers, those
+    // a late build would not have queued (above: ELIDE) - in its wave's record, by the first of the lanes that hold one
+    if constexpr (DIAG && !FIN) {
+      const bool z = has_s && adds_exactly_zero(nee_contrib);
+      const unsigned long long zm = __ballot(z);
+      if (z && lane == static_cast<uint32_t>(__ffsll(static_cast<long long>(zm))) - 1u) wrec->would_elide += static_cast<unsigned long long>(__popcll(zm));
+    }
     if (finisher_batch) cold_acc[slot] = v4u{fu(acc.x), fu(acc.y), fu(acc.z), item};
     if constexpr (TEX) cold_cone[slot] = v4u{fu(cone.cone_width), fu(cone.spread_angle), 0u, 0u};
   }
@@ -1366,6 +1400,12 @@ render_cu_kernel(const CuKArgs ka) {
   // wave-uniform event counts (scalar registers): the two ray counts every stats launch reports
   uint32_t n_closest = 0, n_shadow = 0, n_nan = 0, iter_wave = 0;
   uint32_t n_dead = 0;   // path rays queued early and walked for nothing (their vertex found the path ended): not counted, as the reference never traced them
+  // shadow rays whose light sample adds exactly zero: a late build does not queue them and counts them here, as the
+  // reference traced them (cu_vertex, ELIDE); the statistics build walks them, counts them in n_shadow and keeps this count in its wave's record
+  uint32_t n_elided = 0;
+  // Builds that queue their rays late, but not the statistics build - and not the textured build for trees in global
+  // memory, the one kernel the compare costs anything (16 spilled registers more; the policy launches it early anyway)
+  constexpr bool ELIDE = !DIAG && EARLY == 0 && !(TEX && DEEP);
   unsigned long long t_mark = __builtin_readcyclecounter();
   bool skip_fin = false;   // the last finisher batch of this wave held only slots that wait for another slot's segment
   uint32_t polls = 0;      // looks that found nothing to do
@@ -1430,13 +1470,13 @@ render_cu_kernel(const CuKArgs ka) {
       const bool by_class = opt_classes<PLAIN>(A) == 3u;
       if (opt_flex<PLAIN>(A) & 2u) __builtin_amdgcn_s_setprio(1);
       if (cls == 0u)
-        cu_vertex<TEX, NW, DIAG, EARLY, true, -1, PLAIN>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, true, -1, PLAIN, ELIDE>(n, e, all_pending, n_nan, n_dead, n_elided);
       else if (cls == 1u && by_class)
-        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_LAMBERTIAN), PLAIN>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_LAMBERTIAN), PLAIN, ELIDE>(n, e, all_pending, n_nan, n_dead, n_elided);
       else if ((cls == 2u && by_class) || opt_no_other<PLAIN>)   // (without the fourth ring a batch that is neither 0 nor 1 is 2)
-        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_PRINCIPLED), PLAIN>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, false, int(VIMG_MAT_PRINCIPLED), PLAIN, ELIDE>(n, e, all_pending, n_nan, n_dead, n_elided);
       else if constexpr (!opt_no_other<PLAIN>)
-        cu_vertex<TEX, NW, DIAG, EARLY, false, -1, PLAIN>(n, e, all_pending, n_nan, n_dead);
+        cu_vertex<TEX, NW, DIAG, EARLY, false, -1, PLAIN, ELIDE>(n, e, all_pending, n_nan, n_dead, n_elided);
       if (opt_flex<PLAIN>(A) & 2u) __builtin_amdgcn_s_setprio(0);
       skip_fin = all_pending;
       if (!all_pending) polls = 0, idle_since = 0;   // (a batch of waiting slots only is not progress: the watchdog keeps its time)
@@ -1477,7 +1517,7 @@ render_cu_kernel(const CuKArgs ka) {
     if (full_stats && lane == 0) wrec->cyc[5] += __builtin_readcyclecounter() - t_mark;
     if (stats && lane == 0) {
       atomicAdd(&stats->closest, static_cast<unsigned long long>(n_closest) - static_cast<unsigned long long>(n_dead));   // (modulo 2^64: the sum over the waves is what counts)
-      atomicAdd(&stats->shadow, static_cast<unsigned long long>(n_shadow));
+      atomicAdd(&stats->shadow, static_cast<unsigned long long>(n_shadow) + (DIAG ? 0ull : static_cast<unsigned long long>(n_elided)));
       if (n_nan) atomicAdd(&stats->nan_samples, static_cast<unsigned long long>(n_nan));
       if (full_stats) {
         // (32-bit per-wave event counts: a wave sees 2^32 node visits only beyond ~10^13 per frame)
@@ -1489,6 +1529,7 @@ render_cu_kernel(const CuKArgs ka) {
         for (int k = 0; k < 6; ++k) atomicAdd(&stats->prof[k], wrec->cyc[k]);
         for (int k = 0; k < 4; ++k) atomicAdd(&stats->prof[6 + k], wrec->nbatch[k]), atomicAdd(&stats->prof[11 + k], wrec->nslots[k]);
         atomicAdd(&stats->prof[10], 1ull);
+        atomicAdd(&stats->prof[15], wrec->would_elide);   // (the spare word behind the slots)
         const unsigned long long wd[7] = {wrec->box_pass, wrec->box_lanes, wrec->leaf_round, wrec->leaf_lanes, wrec->sessions,
                                           wrec->refills, wrec->refill_rays};
         for (int k = 0; k < 7; ++k) atomicAdd(&stats->prof[16 + k], wd[k]);

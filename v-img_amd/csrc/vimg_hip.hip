@@ -179,7 +179,10 @@ int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* 
     for (int k = 0; k < 6; ++k)
       std::fprintf(stderr, "[vimg stage] %-18s %14llu cyc %6.2f %%  batches %10llu  slots/batch %7.2f\n", st_names[k],
                    ds.prof[k], 100.0 * double(ds.prof[k]) / double(total ? total : 1), k < 5 ? ds.prof[6 + k] : 0ull,
-                   (k < 5 && ds.prof[6 + k]) ? double(ds.prof[11 + k]) / double(ds.prof[6 + k]) : 0.0);
+                   (k < 4 && ds.prof[6 + k]) ? double(ds.prof[11 + k]) / double(ds.prof[6 + k]) : 0.0);   // (prof[15] is no slot count)
+    // the rays a late build of the kernel does not queue (cu_vertex, ELIDE); this build walked and counted them
+    std::fprintf(stderr, "[vimg walk] would-elide shadow rays %llu of %llu (%.2f %%): their light sample adds exactly zero\n",
+                 ds.prof[15], ds.shadow, 100.0 * double(ds.prof[15]) / double(ds.shadow ? ds.shadow : 1));
     if (ds.prof[16])   // render_cu_kernel: passes of the walk loops and the lanes that took part
       std::fprintf(stderr, "[vimg walk] box passes %llu lanes/pass %.2f   leaf rounds %llu lanes/round %.2f   sessions %llu   refills %llu rays/refill %.2f\n",
                    ds.prof[16], double(ds.prof[17]) / double(ds.prof[16]), ds.prof[18], double(ds.prof[19]) / double(ds.prof[18] ? ds.prof[18] : 1),
