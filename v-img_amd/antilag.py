@@ -75,9 +75,7 @@ def rescale(color, normal, position, depth, history, world_to_pixel, out_scale=N
                                            C.byref(p), C.c_void_p(workspace.data_ptr()),
                                            workspace.numel() * workspace.element_size(),
                                            None if out_scale is False else C.c_void_p(out_scale.data_ptr()), sp))
-    if hist is not history.tensor:          # the history held a numpy array: its rescaled copy, where it came from
-        history = type(history)(hist.cpu().numpy(), history.world_to_pixel)
-    return history, (None if out_scale is False else c.result(out_scale))
+    return c.rewritten(history, hist), (None if out_scale is False else c.result(out_scale))
 
 
 __all__ = ["rescale", "antilag_params", "workspace_bytes", "FLOATS", "FRAMES"]

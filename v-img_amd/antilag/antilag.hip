@@ -192,27 +192,21 @@ int vimg_antilag_rescale(const VimgAntilagFrames* f, const float cur_world_to_pi
   k.sigma_normal = a->sigma_normal;
   k.sigma_plane = a->sigma_plane;
   if (!d_history) return fail(VIMG_E_INVALID, "antilag: null history");
-  if (reinterpret_cast<uintptr_t>(d_history) % 16) return fail(VIMG_E_INVALID, "antilag: the history must be 16-byte aligned");
+  if (misaligned(d_history, 16)) return fail(VIMG_E_INVALID, "antilag: the history must be 16-byte aligned");
   const uint32_t w = f->width, h = f->height;
   const uint64_t need = vimg_antilag_workspace_bytes(w, h);
   if (const int rc = check_workspace(d_workspace, workspace_bytes, need, w, h)) return rc;
-  if (reinterpret_cast<uintptr_t>(d_scale_out) % 4) return fail(VIMG_E_INVALID, "antilag: the scale output must be 4-byte aligned");
+  if (misaligned(d_scale_out, 4)) return fail(VIMG_E_INVALID, "antilag: the scale output must be 4-byte aligned");
   // the history is written while other lanes read the frames, the workspace between the two kernels, the scales last
   const uint64_t frame = uint64_t(12) * w * h, hist = uint64_t(VIMG_ANTILAG_HISTORY_PER_PIXEL) * w * h, plane = uint64_t(4) * w * h;
-  const void* frames[4] = {f->color, f->normal, f->position, f->depth};
-  const char* names[4] = {"color", "normal", "position", "depth"};
-  for (int i = 0; i < 4; ++i)
-    if (overlaps(d_history, hist, frames[i], frame)) return fail(VIMG_E_INVALID, "antilag: the history overlaps the %s frame", names[i]);
-  if (overlaps(d_workspace, need, d_history, hist)) return fail(VIMG_E_INVALID, "antilag: the workspace overlaps the history");
-  for (int i = 0; i < 4; ++i)
-    if (overlaps(d_workspace, need, frames[i], frame)) return fail(VIMG_E_INVALID, "antilag: the workspace overlaps the %s frame", names[i]);
-  if (d_scale_out) {
-    if (overlaps(d_scale_out, plane, d_history, hist)) return fail(VIMG_E_INVALID, "antilag: the scale output overlaps the history");
-    for (int i = 0; i < 4; ++i)
-      if (overlaps(d_scale_out, plane, frames[i], frame))
-        return fail(VIMG_E_INVALID, "antilag: the scale output overlaps the %s frame", names[i]);
-    if (overlaps(d_scale_out, plane, d_workspace, need)) return fail(VIMG_E_INVALID, "antilag: the scale output overlaps the workspace");
-  }
+  const Range reads[] = {{d_history, hist, "history"}, {f->color, frame, "color frame"}, {f->normal, frame, "normal frame"},
+                         {f->position, frame, "position frame"}, {f->depth, frame, "depth frame"}, {d_workspace, need, "workspace"}};
+  if (const Range* r = first_overlap(d_history, hist, std::span(reads).subspan(1, 4)))
+    return fail(VIMG_E_INVALID, "antilag: the history overlaps the %s", r->name);
+  if (const Range* r = first_overlap(d_workspace, need, std::span(reads).first(5)))
+    return fail(VIMG_E_INVALID, "antilag: the workspace overlaps the %s", r->name);
+  if (const Range* r = d_scale_out ? first_overlap(d_scale_out, plane, reads) : nullptr)
+    return fail(VIMG_E_INVALID, "antilag: the scale output overlaps the %s", r->name);
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   float4* history = static_cast<float4*>(d_history);
@@ -224,18 +218,9 @@ int vimg_antilag_rescale(const VimgAntilagFrames* f, const float cur_world_to_pi
   if (const int rc = launched("pair")) return rc;
   const Thresholds t{a->t_low, a->t_high, a->min_matches};
   float* scale = static_cast<float*>(d_scale_out);
-#define VIMG_ANTILAG_SCALE(R) antilag_scale_kernel<R><<<tile_grid(w, h), pixel_block(), 0, s>>>(w, h, pairs, t, history, scale)
-  switch (a->radius) {
-    case 1: VIMG_ANTILAG_SCALE(1); break;
-    case 2: VIMG_ANTILAG_SCALE(2); break;
-    case 3: VIMG_ANTILAG_SCALE(3); break;
-    case 4: VIMG_ANTILAG_SCALE(4); break;
-    case 5: VIMG_ANTILAG_SCALE(5); break;
-    case 6: VIMG_ANTILAG_SCALE(6); break;
-    case 7: VIMG_ANTILAG_SCALE(7); break;
-    default: VIMG_ANTILAG_SCALE(8); break;
-  }
-#undef VIMG_ANTILAG_SCALE
+  with_radius<VIMG_ANTILAG_MAX_RADIUS>(a->radius, [&](auto R) {
+    antilag_scale_kernel<R.value><<<tile_grid(w, h), pixel_block(), 0, s>>>(w, h, pairs, t, history, scale);
+  });
   return launched("scale");
 }
 

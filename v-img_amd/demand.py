@@ -25,14 +25,8 @@ def params(stride=None, phase=None, **floats):
     """An abi.DemandParams: the library's defaults (vimg_demand_defaults; include/vimg_demand.h names them) with the given
     values in place of them: ``stride``, ``phase``, ``min_history``, ``sigma_normal``, ``sigma_plane``.  The library
     checks the ranges; here an integer field only has to fit its uint32."""
-    p = library_params("demand", abi.DemandParams, _lib().vimg_demand_defaults, FLOATS, list(floats.items()),
-                       ("stride", stride, "0 or 2..4"))
-    # library_params checks the one integer field of the other libraries; this one has two
-    if phase is not None:
-        if not 0 <= int(phase) < 2 ** 32:
-            raise ValueError(f"demand: phase must be 0..stride^2 - 1, not {phase}")
-        p.phase = int(phase)
-    return p
+    return library_params("demand", abi.DemandParams, _lib().vimg_demand_defaults, FLOATS, list(floats.items()),
+                          ("stride", stride, "0 or 2..4"), ("phase", phase, "0..stride^2 - 1"))
 
 
 def new_counts(device="cuda"):

@@ -89,18 +89,9 @@ void vimg_demand_defaults(VimgDemandParams* params) {
 int vimg_demand_mask(const VimgDemandFrames* f, const void* d_prev_history, const float prev_world_to_pixel[12],
                      const VimgDemandParams* a, void* d_out_mask, void* d_out_length, void* d_out_counts, void* stream) {
   static_assert(VIMG_DEMAND_HISTORY_PER_PIXEL == 3 * sizeof(float4), "the history is three float4 planes");
-  // frame_lib.h's check_head, in its order and its sentences, for a frames struct that has no colour frame
-  if (!f) return fail(VIMG_E_INVALID, "demand: null frames");
-  if (!a) return fail(VIMG_E_INVALID, "demand: null params");
-  if (f->struct_size < sizeof(VimgDemandFrames))
-    return fail(VIMG_E_INVALID, "demand: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgDemandFrames));
-  if (a->struct_size < sizeof(VimgDemandParams))
-    return fail(VIMG_E_INVALID, "demand: params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(VimgDemandParams));
+  if (const int rc = check_structs(f, a, "params", VIMG_DEMAND_MAX_EXTENT)) return rc;
+  if (const int rc = check_present({{f->normal, "normal"}, {f->position, "position"}, {f->depth, "depth"}})) return rc;
   const uint32_t w = f->width, h = f->height;
-  if (w == 0 || h == 0 || w > VIMG_DEMAND_MAX_EXTENT || h > VIMG_DEMAND_MAX_EXTENT)
-    return fail(VIMG_E_INVALID, "demand: width and height must be 1..%u, not %u x %u", VIMG_DEMAND_MAX_EXTENT, w, h);
-  if (!f->normal || !f->position || !f->depth)
-    return fail(VIMG_E_INVALID, "demand: null %s frame", !f->normal ? "normal" : !f->position ? "position" : "depth");
   if (!d_out_mask) return fail(VIMG_E_INVALID, "demand: null mask");
   if (a->stride == 1 || a->stride > VIMG_DEMAND_MAX_STRIDE)
     return fail(VIMG_E_INVALID, "demand: stride must be 0 or 2..%u, not %u", VIMG_DEMAND_MAX_STRIDE, a->stride);
@@ -111,39 +102,22 @@ int vimg_demand_mask(const VimgDemandFrames* f, const void* d_prev_history, cons
   if (const int rc = check_float("min_history", a->min_history, 0.f, false, false)) return rc;
   if (const int rc = check_float("sigma_normal", a->sigma_normal, 0.f, true, false)) return rc;
   if (const int rc = check_float("sigma_plane", a->sigma_plane, 0.f, true, false)) return rc;
-  // reproject.h's sentences for the previous history and its matrix
   Constants k{};
-  if (d_prev_history) {
-    if (reinterpret_cast<uintptr_t>(d_prev_history) % 16) return fail(VIMG_E_INVALID, "demand: the previous history must be 16-byte aligned");
-    if (!prev_world_to_pixel) return fail(VIMG_E_INVALID, "demand: a previous history needs its world-to-pixel matrix");
-  }
-  if (prev_world_to_pixel)
-    for (int i = 0; i < 12; ++i) {
-      if (!std::isfinite(prev_world_to_pixel[i]))
-        return fail(VIMG_E_INVALID, "demand: world-to-pixel entry %d is not finite (%g)", i, double(prev_world_to_pixel[i]));
-      k.r.m[i] = prev_world_to_pixel[i];
-    }
-  if (d_out_length && reinterpret_cast<uintptr_t>(d_out_length) % 4) return fail(VIMG_E_INVALID, "demand: the output lengths must be 4-byte aligned");
-  if (d_out_counts && reinterpret_cast<uintptr_t>(d_out_counts) % 4) return fail(VIMG_E_INVALID, "demand: the output counts must be 4-byte aligned");
+  if (const int rc = check_previous(d_prev_history, prev_world_to_pixel, k.r)) return rc;
+  if (misaligned(d_out_length, 4)) return fail(VIMG_E_INVALID, "demand: the output lengths must be 4-byte aligned");
+  if (misaligned(d_out_counts, 4)) return fail(VIMG_E_INVALID, "demand: the output counts must be 4-byte aligned");
   // nothing is written where something is read or where something else is written: outputs in the order mask, lengths,
   // counts, each against the history, the guides and the outputs before it
   const uint64_t n = uint64_t(w) * h, frame = 12 * n, hist = uint64_t(VIMG_DEMAND_HISTORY_PER_PIXEL) * n;
-  struct Range {
-    const void* p;
-    uint64_t bytes;
-    const char* name;
-  };
   const Range reads[] = {{d_prev_history, hist, "the previous history"}, {f->normal, frame, "the normal frame"},
                          {f->position, frame, "the position frame"}, {f->depth, frame, "the depth frame"}};
   const Range outs[] = {{d_out_mask, n, "mask"}, {d_out_length, 4 * n, "output lengths"}, {d_out_counts, 4 * COUNTS, "output counts"}};
   for (int o = 0; o < 3; ++o) {
     if (!outs[o].p) continue;
-    for (const Range& r : reads)
-      if (r.p && overlaps(outs[o].p, outs[o].bytes, r.p, r.bytes))
-        return fail(VIMG_E_INVALID, "demand: the %s overlap%s %s", outs[o].name, o == 0 ? "s" : "", r.name);
-    for (int e = 0; e < o; ++e)
-      if (outs[e].p && overlaps(outs[o].p, outs[o].bytes, outs[e].p, outs[e].bytes))
-        return fail(VIMG_E_INVALID, "demand: the %s overlap the %s", outs[o].name, outs[e].name);
+    if (const Range* r = first_overlap(outs[o].p, outs[o].bytes, reads))
+      return fail(VIMG_E_INVALID, "demand: the %s overlap%s %s", outs[o].name, o == 0 ? "s" : "", r->name);
+    if (const Range* e = first_overlap(outs[o].p, outs[o].bytes, std::span(outs).first(o)))
+      return fail(VIMG_E_INVALID, "demand: the %s overlap the %s", outs[o].name, e->name);
   }
 
   if (a->stride) {

@@ -24,15 +24,9 @@ def params(radius=None, rank=None, min_taps=None, **floats):
     """An abi.DespeckleParams: the library's defaults (vimg_despeckle_defaults; include/vimg_despeckle.h names them) with
     the given values in place of them: ``radius``, ``rank``, ``min_taps``, ``gain``, ``sigma_normal``, ``sigma_plane``,
     ``albedo_floor``.  The library checks the ranges; here an integer field only has to fit its uint32."""
-    p = library_params("despeckle", abi.DespeckleParams, _lib().vimg_despeckle_defaults, FLOATS, list(floats.items()),
-                       ("radius", radius, f"1..{abi.DESPECKLE_MAX_RADIUS}"))
-    # library_params checks the one integer field of the other libraries; this one has three
-    for name, v, allowed in (("rank", rank, f"1..{abi.DESPECKLE_MAX_RANK}"), ("min_taps", min_taps, "rank..(2 radius + 1)^2 - 1")):
-        if v is not None:
-            if not 0 <= int(v) < 2 ** 32:
-                raise ValueError(f"despeckle: {name} must be {allowed}, not {v}")
-            setattr(p, name, int(v))
-    return p
+    return library_params("despeckle", abi.DespeckleParams, _lib().vimg_despeckle_defaults, FLOATS, list(floats.items()),
+                          ("radius", radius, f"1..{abi.DESPECKLE_MAX_RADIUS}"), ("rank", rank, f"1..{abi.DESPECKLE_MAX_RANK}"),
+                          ("min_taps", min_taps, "rank..(2 radius + 1)^2 - 1"))
 
 
 def workspace_bytes(width, height):

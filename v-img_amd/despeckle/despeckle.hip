@@ -23,6 +23,7 @@
 #define FRAME_LIB "despeckle"
 #include "../frames/frame_lib.h"
 #include "../frames/guides.h"
+#include "../frames/tile.h"
 
 namespace vimg_despeckle {
 
@@ -63,11 +64,9 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void despeckle_clamp_kernel(
   int x, y;
   const bool inside = pixel_of(w, h, x, y);
   // the workgroup's tile with its apron, row-major; a cell outside the image reads as "not live"
-  constexpr int TW = WAVE_X + 2 * R, TH = ROWS + 2 * R;
-  __shared__ float4 t0[TH * TW], t1[TH * TW];
-  const int ox = int(blockIdx.x * WAVE_X) - R, oy = int(blockIdx.y * ROWS) - R;
-  for (int i = int(threadIdx.y) * WAVE_X + int(threadIdx.x); i < TW * TH; i += WAVE_X * ROWS) {
-    const int gx = ox + i % TW, gy = oy + i / TW;
+  constexpr int TW = tile_width<R>;
+  __shared__ float4 t0[tile_cells<R>], t1[tile_cells<R>];
+  const int lp = stage_tile<R>([&](int i, int gx, int gy) {
     float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
     if (uint32_t(gx) < w && uint32_t(gy) < h) {
       const size_t q = size_t(gy) * w + size_t(gx);
@@ -76,11 +75,9 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void despeckle_clamp_kernel(
     }
     t0[i] = v0;
     t1[i] = v1;
-  }
-  __syncthreads();
+  });
   if (!inside) return;
   const size_t p = size_t(y) * w + size_t(x), t = 3 * p;
-  const int lp = (int(threadIdx.y) + R) * TW + int(threadIdx.x) + R;
   const float4 np = t0[lp], pp = t1[lp];
   const float cr = color[t], cg = color[t + 1], cb = color[t + 2];
   float r = cr, g = cg, b = cb;
@@ -188,16 +185,11 @@ int vimg_despeckle_clamp(const VimgDespeckleFrames* f, const VimgDespeckleParams
   // other lanes read the planes, and pack reads every frame before clamp writes: only the colour frame itself may be
   // the output
   const uint64_t frame = uint64_t(12) * w * h, codes = uint64_t(w) * h;
-  if (d_out_rgb != f->color && overlaps(d_out_rgb, frame, f->color, frame))
-    return fail(VIMG_E_INVALID, "despeckle: the output overlaps the color frame without being it");
-  const void* frames[4] = {f->normal, f->position, f->depth, f->albedo};
-  const char* names[4] = {"normal", "position", "depth", "albedo"};
-  for (int i = 0; i < 4; ++i)
-    if (frames[i] && overlaps(d_out_rgb, frame, frames[i], frame))
-      return fail(VIMG_E_INVALID, "despeckle: the output overlaps the %s frame", names[i]);
-  if (d_out_code && overlaps(d_out_rgb, frame, d_out_code, codes))
-    return fail(VIMG_E_INVALID, "despeckle: the output overlaps the output codes");
-  if (overlaps(d_out_rgb, frame, d_workspace, need)) return fail(VIMG_E_INVALID, "despeckle: the output overlaps the workspace");
+  const Range others[] = {{f->color, frame, "color frame"}, {f->normal, frame, "normal frame"}, {f->position, frame, "position frame"},
+                          {f->depth, frame, "depth frame"}, {f->albedo, frame, "albedo frame"}, {d_out_code, codes, "output codes"},
+                          {d_workspace, need, "workspace"}};
+  if (const Range* r = first_overlap(d_out_rgb, frame, std::span(others).subspan(d_out_rgb == f->color ? 1 : 0)))
+    return fail(VIMG_E_INVALID, "despeckle: the output overlaps the %s%s", r->name, r == others ? " without being it" : "");
   if (d_out_code && overlaps(d_out_code, codes, d_workspace, need))
     return fail(VIMG_E_INVALID, "despeckle: the output codes overlap the workspace");
 
@@ -216,15 +208,10 @@ int vimg_despeckle_clamp(const VimgDespeckleFrames* f, const VimgDespeckleParams
   if (const int rc = launched("pack")) return rc;
   float* out = static_cast<float*>(d_out_rgb);
   uint8_t* code = static_cast<uint8_t*>(d_out_code);
-#define VIMG_DESPECKLE_CLAMP(R)                                                                                              \
-  despeckle_clamp_kernel<R><<<grid, block, 0, s>>>(w, h, a->rank, a->min_taps, a->gain, a->sigma_normal, a->sigma_plane, \
-                                                   a->albedo_floor, color, albedo, g0, g1, out, code)
-  switch (a->radius) {
-    case 1: VIMG_DESPECKLE_CLAMP(1); break;
-    case 2: VIMG_DESPECKLE_CLAMP(2); break;
-    default: VIMG_DESPECKLE_CLAMP(3); break;
-  }
-#undef VIMG_DESPECKLE_CLAMP
+  with_radius<VIMG_DESPECKLE_MAX_RADIUS>(a->radius, [&](auto R) {
+    despeckle_clamp_kernel<R.value><<<grid, block, 0, s>>>(w, h, a->rank, a->min_taps, a->gain, a->sigma_normal, a->sigma_plane,
+                                                           a->albedo_floor, color, albedo, g0, g1, out, code);
+  });
   return launched("clamp");
 }
 

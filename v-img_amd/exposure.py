@@ -24,14 +24,9 @@ def params(low_permille=None, high_permille=None, **floats):
     """An abi.ExposureParams: the library's defaults (vimg_exposure_defaults; include/vimg_exposure.h names them) with the
     given values in place of them: ``low_permille``, ``high_permille``, ``key``, ``min_exposure``, ``max_exposure``,
     ``rate_brighten``, ``rate_darken``.  The library checks the ranges; here an integer field only has to fit its uint32."""
-    p = library_params("exposure", abi.ExposureParams, _lib().vimg_exposure_defaults, FLOATS, list(floats.items()),
-                       ("low_permille", low_permille, "0..high_permille - 1"))
-    # library_params checks the one integer field of the other libraries; this one has two
-    if high_permille is not None:
-        if not 0 <= int(high_permille) < 2 ** 32:
-            raise ValueError(f"exposure: high_permille must be low_permille + 1..1000, not {high_permille}")
-        p.high_permille = int(high_permille)
-    return p
+    return library_params("exposure", abi.ExposureParams, _lib().vimg_exposure_defaults, FLOATS, list(floats.items()),
+                          ("low_permille", low_permille, "0..high_permille - 1"),
+                          ("high_permille", high_permille, "low_permille + 1..1000"))
 
 
 def new_state(device="cuda"):

@@ -151,19 +151,11 @@ void vimg_exposure_defaults(VimgExposureParams* params) {
 }
 
 int vimg_exposure_adapt(const VimgExposureFrames* f, const VimgExposureParams* a, void* d_state, void* d_out_rgb, void* stream) {
-  // frame_lib.h's check_head, in its order and its sentences, for a frames struct that has no normal and position
-  if (!f) return fail(VIMG_E_INVALID, "exposure: null frames");
-  if (!a) return fail(VIMG_E_INVALID, "exposure: null params");
-  if (f->struct_size < sizeof(VimgExposureFrames))
-    return fail(VIMG_E_INVALID, "exposure: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgExposureFrames));
-  if (a->struct_size < sizeof(VimgExposureParams))
-    return fail(VIMG_E_INVALID, "exposure: params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(VimgExposureParams));
+  if (const int rc = check_structs(f, a, "params", VIMG_EXPOSURE_MAX_EXTENT)) return rc;
+  if (const int rc = check_present({{f->color, "color"}})) return rc;
   const uint32_t w = f->width, h = f->height;
-  if (w == 0 || h == 0 || w > VIMG_EXPOSURE_MAX_EXTENT || h > VIMG_EXPOSURE_MAX_EXTENT)
-    return fail(VIMG_E_INVALID, "exposure: width and height must be 1..%u, not %u x %u", VIMG_EXPOSURE_MAX_EXTENT, w, h);
-  if (!f->color) return fail(VIMG_E_INVALID, "exposure: null color frame");
   if (!d_state) return fail(VIMG_E_INVALID, "exposure: null state");
-  if (reinterpret_cast<uintptr_t>(d_state) % 16) return fail(VIMG_E_INVALID, "exposure: the state must be 16-byte aligned");
+  if (misaligned(d_state, 16)) return fail(VIMG_E_INVALID, "exposure: the state must be 16-byte aligned");
   if (a->low_permille >= a->high_permille || a->high_permille > 1000)
     return fail(VIMG_E_INVALID, "exposure: the permilles must be 0 <= low < high <= 1000, not %u and %u", a->low_permille, a->high_permille);
   if (const int rc = check_float("key", a->key, 0.f, true, false)) return rc;
@@ -180,15 +172,12 @@ int vimg_exposure_adapt(const VimgExposureFrames* f, const VimgExposureParams* a
   // a lane of apply touches its own pixel alone, so the colour frame itself may be the output; nothing else may be
   // written where something is read
   const uint64_t frame = uint64_t(12) * w * h;
-  if (d_out_rgb) {
-    if (d_out_rgb != f->color && overlaps(d_out_rgb, frame, f->color, frame))
-      return fail(VIMG_E_INVALID, "exposure: the output overlaps the color frame without being it");
-    if (f->depth && overlaps(d_out_rgb, frame, f->depth, frame)) return fail(VIMG_E_INVALID, "exposure: the output overlaps the depth frame");
-    if (overlaps(d_out_rgb, frame, d_state, VIMG_EXPOSURE_STATE_BYTES)) return fail(VIMG_E_INVALID, "exposure: the output overlaps the state");
-  }
-  if (overlaps(d_state, VIMG_EXPOSURE_STATE_BYTES, f->color, frame)) return fail(VIMG_E_INVALID, "exposure: the state overlaps the color frame");
-  if (f->depth && overlaps(d_state, VIMG_EXPOSURE_STATE_BYTES, f->depth, frame))
-    return fail(VIMG_E_INVALID, "exposure: the state overlaps the depth frame");
+  const Range reads[] = {{f->color, frame, "color frame"}, {f->depth, frame, "depth frame"}, {d_state, VIMG_EXPOSURE_STATE_BYTES, "state"}};
+  if (d_out_rgb)
+    if (const Range* r = first_overlap(d_out_rgb, frame, std::span(reads).subspan(d_out_rgb == f->color ? 1 : 0)))
+      return fail(VIMG_E_INVALID, "exposure: the output overlaps the %s%s", r->name, r == reads ? " without being it" : "");
+  if (const Range* r = first_overlap(d_state, VIMG_EXPOSURE_STATE_BYTES, std::span(reads).first(2)))
+    return fail(VIMG_E_INVALID, "exposure: the state overlaps the %s", r->name);
 
   const uint64_t n = uint64_t(w) * h;
   const uint64_t wanted = (n + BINS - 1) / BINS;

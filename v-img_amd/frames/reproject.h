@@ -1,10 +1,10 @@
-// What the libraries that reproject a history share (libvimg_temporal.so, libvimg_moments.so, libvimg_wtemporal.so;
-// DESIGN.md 4.20): the reprojection of include/vimg_temporal.h's contract, from the projection of a pixel's surface
-// point to the weighted means of its accepted history taps, and the argument checks of a call that takes a previous
-// history, a next one and outputs.  Internal, like frame_lib.h, which a unit includes first: shared source in an
-// anonymous namespace, compiled into every library that includes it, never a dynamic symbol.
+// What the libraries that reproject a history share (libvimg_temporal.so, libvimg_moments.so, libvimg_wtemporal.so,
+// libvimg_demand.so): the reprojection of include/vimg_temporal.h's contract, from the projection of a
+// pixel's surface point to the weighted means of its accepted history taps; the check of a previous history and its
+// matrix; and the argument checks of a call that also takes a next history and outputs.  Internal, like frame_lib.h,
+// which a unit includes first: shared source in an anonymous namespace, compiled into every library that includes it,
+// never a dynamic symbol.
 #pragma once
-#include <span>
 
 namespace vimg_frames {
 namespace {
@@ -88,18 +88,8 @@ struct ExtraOutput {
   int own = -1;
 };
 
-// In this order: the alignment of the next history, of `reads` and of the previous history; the matrix, which is
-// copied to `k`; what the next history must not overlap; what d_out_rgb must not - other lanes gather from prev and
-// read the guides, so of all frames only the colour frame itself may be the output; the same for `extra`, whose own
-// frame is looked at last.  `hist`: the bytes of one history.
-template <class Frames>
-int check_reprojection(const Frames* f, const void* prev, const float* matrix, const void* next, uint64_t hist,
-                       std::span<const ReadFrame> reads, const void* out, const ExtraOutput& extra, Reprojection& k) {
-  const auto misaligned = [](const void* p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; };
-  if (misaligned(next, 16)) return fail(VIMG_E_INVALID, FRAME_LIB ": the next history must be 16-byte aligned");
-  for (const ReadFrame& r : reads)
-    if (r.p && r.align && misaligned(r.p, r.align))
-      return fail(VIMG_E_INVALID, FRAME_LIB ": the %s frame must be %u-byte aligned", r.name, r.align);
+// the history a call reprojects (null: none) and the matrix it is projected with, which is copied to `k`
+int check_previous(const void* prev, const float* matrix, Reprojection& k) {
   if (prev) {
     if (misaligned(prev, 16)) return fail(VIMG_E_INVALID, FRAME_LIB ": the previous history must be 16-byte aligned");
     if (!matrix) return fail(VIMG_E_INVALID, FRAME_LIB ": a previous history needs its world-to-pixel matrix");
@@ -110,34 +100,48 @@ int check_reprojection(const Frames* f, const void* prev, const float* matrix, c
         return fail(VIMG_E_INVALID, FRAME_LIB ": world-to-pixel entry %d is not finite (%g)", i, double(matrix[i]));
       k.m[i] = matrix[i];
     }
+  return VIMG_OK;
+}
+
+// In this order: the alignment of the next history and of `reads`; check_previous; what the next history must not
+// overlap; what d_out_rgb must not - other lanes gather from prev and read the guides, so of all frames only the
+// colour frame itself may be the output; the same for `extra`, whose own frame is looked at last.  `hist`: the bytes
+// of one history.
+template <class Frames>
+int check_reprojection(const Frames* f, const void* prev, const float* matrix, const void* next, uint64_t hist,
+                       std::span<const ReadFrame> reads, const void* out, const ExtraOutput& extra, Reprojection& k) {
+  if (misaligned(next, 16)) return fail(VIMG_E_INVALID, FRAME_LIB ": the next history must be 16-byte aligned");
+  for (const ReadFrame& r : reads)
+    if (r.p && r.align && misaligned(r.p, r.align))
+      return fail(VIMG_E_INVALID, FRAME_LIB ": the %s frame must be %u-byte aligned", r.name, r.align);
+  if (const int rc = check_previous(prev, matrix, k)) return rc;
   const uint64_t frame = uint64_t(12) * f->width * f->height;
   if (prev && overlaps(next, hist, prev, hist))
     return fail(VIMG_E_INVALID, FRAME_LIB ": the next history overlaps the previous one");
-  ReadFrame all[8] = {{f->color, frame, "color"}, {f->normal, frame, "normal"}, {f->position, frame, "position"}, {f->depth, frame, "depth"}};
+  Range all[8] = {{f->color, frame, "color"}, {f->normal, frame, "normal"}, {f->position, frame, "position"}, {f->depth, frame, "depth"}};
   size_t n = 4;
-  for (const ReadFrame& r : reads) all[n++] = r;      // (a null one keeps its place and is passed over below)
-  const auto touches = [&](const void* p, uint64_t bytes, size_t i) { return all[i].p && overlaps(p, bytes, all[i].p, all[i].bytes); };
-  for (size_t i = 0; i < n; ++i)
-    if (touches(next, hist, i)) return fail(VIMG_E_INVALID, FRAME_LIB ": the next history overlaps the %s frame", all[i].name);
+  for (const ReadFrame& r : reads) all[n++] = {r.p, r.bytes, r.name};      // (a null one keeps its place and is passed over)
+  const std::span<const Range> frames(all, n);
+  if (const Range* r = first_overlap(next, hist, frames))
+    return fail(VIMG_E_INVALID, FRAME_LIB ": the next history overlaps the %s frame", r->name);
   if (out) {
     if (prev && overlaps(out, frame, prev, hist)) return fail(VIMG_E_INVALID, FRAME_LIB ": the output overlaps the previous history");
     if (overlaps(out, frame, next, hist)) return fail(VIMG_E_INVALID, FRAME_LIB ": the output overlaps the next history");
-    for (size_t i = 0; i < n; ++i)
-      if (touches(out, frame, i) && !(i == 0 && out == f->color))
-        return fail(VIMG_E_INVALID, i == 0 ? FRAME_LIB ": the output overlaps the %s frame without being it"
-                                           : FRAME_LIB ": the output overlaps the %s frame", all[i].name);
+    if (const Range* r = first_overlap(out, frame, frames.subspan(out == f->color ? 1 : 0)))
+      return fail(VIMG_E_INVALID, r == all ? FRAME_LIB ": the output overlaps the %s frame without being it"
+                                           : FRAME_LIB ": the output overlaps the %s frame", r->name);
   }
   if (extra.p) {
-    const size_t own = extra.own < 0 ? n : size_t(4 + extra.own);
+    Range own{};      // taken out of its place, to be looked at last
+    if (extra.own >= 0) std::swap(own, all[4 + extra.own]);
     if (prev && overlaps(extra.p, extra.bytes, prev, hist))
       return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the previous history", extra.says);
     if (overlaps(extra.p, extra.bytes, next, hist)) return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the next history", extra.says);
-    for (size_t i = 0; i < n; ++i)
-      if (i != own && touches(extra.p, extra.bytes, i))
-        return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the %s frame", extra.says, all[i].name);
+    if (const Range* r = first_overlap(extra.p, extra.bytes, frames))
+      return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the %s frame", extra.says, r->name);
     if (out && overlaps(extra.p, extra.bytes, out, frame)) return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the output", extra.says);
-    if (own < n && extra.p != all[own].p && touches(extra.p, extra.bytes, own))
-      return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the %s frame without being it", extra.says, all[own].name);
+    if (extra.p != own.p && first_overlap(extra.p, extra.bytes, {&own, 1}))
+      return fail(VIMG_E_INVALID, FRAME_LIB ": the %s the %s frame without being it", extra.says, own.name);
   }
   return VIMG_OK;
 }

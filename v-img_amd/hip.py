@@ -206,6 +206,11 @@ class FrameCall(_Tensors):
         prev = self.take(history.tensor, f"{self.what} history", ("float32",), (cls.PLANES, self.h, self.w, 4), aligned=True)
         return prev, (abi.f32 * 12)(*history.world_to_pixel.tolist())
 
+    def rewritten(self, history, t):
+        """The ``history`` a call rewrote in place through ``t``, what ``take`` made of its tensor: ``history`` itself
+        when that is its own CUDA tensor; when it held a numpy array, a new one of its class around ``t``'s copy."""
+        return history if t is history.tensor else type(history)(t.cpu().numpy(), history.world_to_pixel)
+
     def workspace(self, workspace, nbytes):
         """The caller's ``workspace`` as it is, or ``nbytes`` bytes of this call's own when None."""
         import torch
@@ -238,18 +243,19 @@ class FrameHistory:
         return self.tensor[0, :, :, 3]
 
 
-def library_params(what, struct, defaults, floats, given, count=None):
+def library_params(what, struct, defaults, floats, given, *counts):
     """An abi ``struct`` of parameters: the library's defaults (``defaults`` fills them in) with the values of ``given``
     ((name, value) pairs; None keeps the default) in place of them.  ``floats`` are the names ``given`` may hold - a
-    call's keywords with another are refused - and ``count`` = (name, value, "1..12") is the library's one integer
-    field."""
+    call's keywords with another are refused - and each of ``counts`` = (name, value, "1..12") is one of the library's
+    integer fields with the range its sentence names: the library checks that range, here the value only has to fit
+    the field's uint32.  The integer fields are looked at first, in the order given."""
     p = struct()
     defaults(C.byref(p))
-    if count is not None and count[1] is not None:
-        name, v, allowed = count
-        if not 0 <= int(v) < 2 ** 32:
-            raise ValueError(f"{what}: {name} must be {allowed}, not {v}")
-        setattr(p, name, int(v))
+    for name, v, allowed in counts:
+        if v is not None:
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"{what}: {name} must be {allowed}, not {v}")
+            setattr(p, name, int(v))
     for name, v in given:
         if name not in floats:
             raise TypeError(f"{what}: unknown parameters {sorted(n for n, _ in given if n not in floats)}; expected some of {floats}")

@@ -101,12 +101,6 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void motion_previous_kernel(uint32_t
   if (code_out) code_out[q] = uint8_t(code);
 }
 
-struct Span {
-  const char* name;
-  const void* p;
-  uint64_t bytes;
-};
-
 }  // namespace vimg_motion
 
 using namespace vimg_motion;
@@ -117,17 +111,8 @@ int vimg_motion_previous_position(const VimgMotionFrames* f, const VimgMotionGeo
                                   void* stream) {
   static_assert(sizeof(VimgRayHit) == sizeof(float4) && sizeof(VimgRay) == 2 * sizeof(float4) && sizeof(VimgPrim) == sizeof(uint2),
                 "the records the kernel reads as vectors");
-  auto misaligned = [](const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-  if (!f) return fail(VIMG_E_INVALID, "motion: null frames");
-  if (!g) return fail(VIMG_E_INVALID, "motion: null geometry");
-  if (f->struct_size < sizeof(VimgMotionFrames))
-    return fail(VIMG_E_INVALID, "motion: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgMotionFrames));
-  if (g->struct_size < sizeof(VimgMotionGeometry))
-    return fail(VIMG_E_INVALID, "motion: geometry.struct_size %u is below the struct's %zu", g->struct_size,
-                sizeof(VimgMotionGeometry));
-  if (f->width == 0 || f->height == 0 || f->width > VIMG_MOTION_MAX_EXTENT || f->height > VIMG_MOTION_MAX_EXTENT)
-    return fail(VIMG_E_INVALID, "motion: width and height must be 1..%u, not %u x %u", VIMG_MOTION_MAX_EXTENT, f->width, f->height);
-  if (!f->position || !f->hits) return fail(VIMG_E_INVALID, "motion: null %s frame", !f->position ? "position" : "hits");
+  if (const int rc = check_structs(f, g, "geometry", VIMG_MOTION_MAX_EXTENT)) return rc;
+  if (const int rc = check_present({{f->position, "position"}, {f->hits, "hits"}})) return rc;
   if (misaligned(f->position, 4)) return fail(VIMG_E_INVALID, "motion: the position frame must be 4-byte aligned");
   if (misaligned(f->hits, 16)) return fail(VIMG_E_INVALID, "motion: the hits must be 16-byte aligned");
   if (misaligned(f->rays, 16)) return fail(VIMG_E_INVALID, "motion: the rays must be 16-byte aligned");
@@ -151,22 +136,19 @@ int vimg_motion_previous_position(const VimgMotionFrames* f, const VimgMotionGeo
   const uint32_t w = f->width, h = f->height;
   const uint64_t n = uint64_t(w) * h;
   // what the kernel reads: a table that is NULL or empty is never read
-  const Span in[9] = {{"position frame", f->position, 12 * n},
-                      {"hits", f->hits, 16 * n},
-                      {"rays", f->rays, 32 * n},
-                      {"prims table", g->prims, uint64_t(8) * g->num_prims},
-                      {"tri_vertices table", g->tri_vertices, uint64_t(12) * g->num_tris},
-                      {"old_vertices table", g->old_vertices, uint64_t(12) * g->num_vertices},
-                      {"new_vertices table", g->new_vertices, uint64_t(12) * g->num_vertices},
-                      {"old_spheres table", g->old_spheres, uint64_t(16) * g->num_spheres},
-                      {"new_spheres table", g->new_spheres, uint64_t(16) * g->num_spheres}};
-  for (const Span& s : in)
-    if (s.p && s.bytes && overlaps(d_out_previous, 12 * n, s.p, s.bytes))
-      return fail(VIMG_E_INVALID, "motion: the previous-position output overlaps the %s", s.name);
+  const Range in[9] = {{f->position, 12 * n, "position frame"},
+                       {f->hits, 16 * n, "hits"},
+                       {f->rays, 32 * n, "rays"},
+                       {g->prims, uint64_t(8) * g->num_prims, "prims table"},
+                       {g->tri_vertices, uint64_t(12) * g->num_tris, "tri_vertices table"},
+                       {g->old_vertices, uint64_t(12) * g->num_vertices, "old_vertices table"},
+                       {g->new_vertices, uint64_t(12) * g->num_vertices, "new_vertices table"},
+                       {g->old_spheres, uint64_t(16) * g->num_spheres, "old_spheres table"},
+                       {g->new_spheres, uint64_t(16) * g->num_spheres, "new_spheres table"}};
+  if (const Range* r = first_overlap(d_out_previous, 12 * n, in))
+    return fail(VIMG_E_INVALID, "motion: the previous-position output overlaps the %s", r->name);
   if (d_out_code) {
-    for (const Span& s : in)
-      if (s.p && s.bytes && overlaps(d_out_code, n, s.p, s.bytes))
-        return fail(VIMG_E_INVALID, "motion: the code output overlaps the %s", s.name);
+    if (const Range* r = first_overlap(d_out_code, n, in)) return fail(VIMG_E_INVALID, "motion: the code output overlaps the %s", r->name);
     if (overlaps(d_out_code, n, d_out_previous, 12 * n))
       return fail(VIMG_E_INVALID, "motion: the code output overlaps the previous-position output");
   }

@@ -27,14 +27,8 @@ def params(radius=None, min_taps=None, **floats):
     """An abi.RectifyParams: the library's defaults (vimg_rectify_defaults; include/vimg_rectify.h names them) with the
     given values in place of them: ``radius``, ``min_taps``, ``k``, ``cut``, ``sigma_normal``, ``sigma_plane``,
     ``albedo_floor``.  The library checks the ranges; here an integer field only has to fit its uint32."""
-    p = library_params("rectify", abi.RectifyParams, _lib().vimg_rectify_defaults, FLOATS, list(floats.items()),
-                       ("radius", radius, f"1..{abi.RECTIFY_MAX_RADIUS}"))
-    # library_params checks the one integer field of the other libraries; this one has two
-    if min_taps is not None:
-        if not 0 <= int(min_taps) < 2 ** 32:
-            raise ValueError(f"rectify: min_taps must be 1..(2 radius + 1)^2, not {min_taps}")
-        p.min_taps = int(min_taps)
-    return p
+    return library_params("rectify", abi.RectifyParams, _lib().vimg_rectify_defaults, FLOATS, list(floats.items()),
+                          ("radius", radius, f"1..{abi.RECTIFY_MAX_RADIUS}"), ("min_taps", min_taps, "1..(2 radius + 1)^2"))
 
 
 def workspace_bytes(width, height):
@@ -82,9 +76,7 @@ def clamp(slow, fast, albedo=None, out=None, code=False, workspace=None, stream=
                                          None if code is False else C.c_void_p(code.data_ptr()),
                                          None if work is None else C.c_void_p(work.data_ptr()),
                                          0 if work is None else work.numel() * work.element_size(), sp))
-    if s is not slow.tensor:          # the history held a numpy array: its clamped copy, where it came from
-        slow = type(slow)(s.cpu().numpy(), slow.world_to_pixel)
-    return slow, (None if out is False else c.result(out)), (None if code is False else c.result(code))
+    return c.rewritten(slow, s), (None if out is False else c.result(out)), (None if code is False else c.result(code))
 
 
 __all__ = ["clamp", "params", "workspace", "workspace_bytes", "FLOATS", "COUNTS"]

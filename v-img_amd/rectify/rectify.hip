@@ -19,6 +19,7 @@
 #define FRAME_LIB "rectify"
 #include "../frames/frame_lib.h"
 #include "../frames/guides.h"
+#include "../frames/tile.h"
 
 namespace vimg_rectify {
 
@@ -44,11 +45,9 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void rectify_clamp_kernel(
   int x, y;
   const bool inside = pixel_of(w, h, x, y);
   // the workgroup's tile with its apron, row-major; a cell outside the image reads as a miss
-  constexpr int TW = WAVE_X + 2 * R, TH = ROWS + 2 * R;
-  __shared__ float4 t0[TH * TW], t1[TH * TW], t2[TH * TW];
-  const int ox = int(blockIdx.x * WAVE_X) - R, oy = int(blockIdx.y * ROWS) - R;
-  for (int i = int(threadIdx.y) * WAVE_X + int(threadIdx.x); i < TW * TH; i += WAVE_X * ROWS) {
-    const int gx = ox + i % TW, gy = oy + i / TW;
+  constexpr int TW = tile_width<R>;
+  __shared__ float4 t0[tile_cells<R>], t1[tile_cells<R>], t2[tile_cells<R>];
+  const int lp = stage_tile<R>([&](int i, int gx, int gy) {
     float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0, v2 = v0;
     if (uint32_t(gx) < w && uint32_t(gy) < h) {
       const size_t q = size_t(gy) * w + size_t(gx);
@@ -66,11 +65,9 @@ __global__ __launch_bounds__(WAVE_X * ROWS) void rectify_clamp_kernel(
     t0[i] = v0;
     t1[i] = v1;
     t2[i] = v2;
-  }
-  __syncthreads();
+  });
   if (!inside) return;
   const size_t p = size_t(y) * w + size_t(x);
-  const int lp = (int(threadIdx.y) + R) * TW + int(threadIdx.x) + R;
   const float4 np = t0[lp], pp = t1[lp];
   const float4 a = slow_a[p];
   float r = a.x, g = a.y, b = a.z;
@@ -158,21 +155,13 @@ uint64_t vimg_rectify_workspace(uint32_t, uint32_t) { return 0; }
 int vimg_rectify_clamp(const VimgRectifyFrames* f, const VimgRectifyParams* a, void* d_out_rgb, void* d_out_code, void*,
                        uint64_t, void* stream) {
   static_assert(VIMG_RECTIFY_HISTORY_PER_PIXEL == 3 * sizeof(float4), "a history is three float4 planes");
-  // frame_lib.h's check_head, in its order and its sentences, for a frames struct of two histories
-  if (!f) return fail(VIMG_E_INVALID, "rectify: null frames");
-  if (!a) return fail(VIMG_E_INVALID, "rectify: null params");
-  if (f->struct_size < sizeof(VimgRectifyFrames))
-    return fail(VIMG_E_INVALID, "rectify: frames.struct_size %u is below the struct's %zu", f->struct_size, sizeof(VimgRectifyFrames));
-  if (a->struct_size < sizeof(VimgRectifyParams))
-    return fail(VIMG_E_INVALID, "rectify: params.struct_size %u is below the struct's %zu", a->struct_size, sizeof(VimgRectifyParams));
+  if (const int rc = check_structs(f, a, "params", VIMG_RECTIFY_MAX_EXTENT)) return rc;
+  if (const int rc = check_present({{f->slow, "slow"}, {f->fast, "fast"}}, "history")) return rc;
   const uint32_t w = f->width, h = f->height;
-  if (w == 0 || h == 0 || w > VIMG_RECTIFY_MAX_EXTENT || h > VIMG_RECTIFY_MAX_EXTENT)
-    return fail(VIMG_E_INVALID, "rectify: width and height must be 1..%u, not %u x %u", VIMG_RECTIFY_MAX_EXTENT, w, h);
-  if (!f->slow || !f->fast) return fail(VIMG_E_INVALID, "rectify: null %s history", !f->slow ? "slow" : "fast");
-  if (reinterpret_cast<uintptr_t>(f->slow) % 16 || reinterpret_cast<uintptr_t>(f->fast) % 16)
-    return fail(VIMG_E_INVALID, "rectify: the %s history must be 16-byte aligned", reinterpret_cast<uintptr_t>(f->slow) % 16 ? "slow" : "fast");
-  if (f->albedo && reinterpret_cast<uintptr_t>(f->albedo) % 4) return fail(VIMG_E_INVALID, "rectify: the albedo frame must be 4-byte aligned");
-  if (d_out_rgb && reinterpret_cast<uintptr_t>(d_out_rgb) % 4) return fail(VIMG_E_INVALID, "rectify: the output must be 4-byte aligned");
+  if (misaligned(f->slow, 16) || misaligned(f->fast, 16))
+    return fail(VIMG_E_INVALID, "rectify: the %s history must be 16-byte aligned", misaligned(f->slow, 16) ? "slow" : "fast");
+  if (misaligned(f->albedo, 4)) return fail(VIMG_E_INVALID, "rectify: the albedo frame must be 4-byte aligned");
+  if (misaligned(d_out_rgb, 4)) return fail(VIMG_E_INVALID, "rectify: the output must be 4-byte aligned");
   if (a->radius < 1 || a->radius > VIMG_RECTIFY_MAX_RADIUS)
     return fail(VIMG_E_INVALID, "rectify: radius must be 1..%u, not %u", VIMG_RECTIFY_MAX_RADIUS, a->radius);
   const uint32_t window = (2 * a->radius + 1) * (2 * a->radius + 1);
@@ -185,21 +174,13 @@ int vimg_rectify_clamp(const VimgRectifyFrames* f, const VimgRectifyParams* a, v
   // nothing is written where something else is read or written: the slow history against the fast one and the albedo
   // frame, then each output against both histories, the albedo frame and the output before it
   const uint64_t n = uint64_t(w) * h, frame = 12 * n, hist = uint64_t(VIMG_RECTIFY_HISTORY_PER_PIXEL) * n;
-  if (overlaps(f->slow, hist, f->fast, hist)) return fail(VIMG_E_INVALID, "rectify: the slow history overlaps the fast history");
-  if (f->albedo && overlaps(f->slow, hist, f->albedo, frame)) return fail(VIMG_E_INVALID, "rectify: the slow history overlaps the albedo frame");
-  struct Range {
-    const void* p;
-    uint64_t bytes;
-    const char* name;
-  };
   const Range reads[] = {{f->slow, hist, "the slow history"}, {f->fast, hist, "the fast history"}, {f->albedo, frame, "the albedo frame"}};
-  const Range outs[] = {{d_out_rgb, frame, "output"}, {d_out_code, n, "output codes"}};
-  for (int o = 0; o < 2; ++o) {
-    if (!outs[o].p) continue;
-    for (const Range& r : reads)
-      if (r.p && overlaps(outs[o].p, outs[o].bytes, r.p, r.bytes))
-        return fail(VIMG_E_INVALID, "rectify: the %s overlap%s %s", outs[o].name, o == 0 ? "s" : "", r.name);
-  }
+  if (const Range* r = first_overlap(f->slow, hist, std::span(reads).subspan(1)))
+    return fail(VIMG_E_INVALID, "rectify: the slow history overlaps %s", r->name);
+  if (const Range* r = d_out_rgb ? first_overlap(d_out_rgb, frame, reads) : nullptr)
+    return fail(VIMG_E_INVALID, "rectify: the output overlaps %s", r->name);
+  if (const Range* r = d_out_code ? first_overlap(d_out_code, n, reads) : nullptr)
+    return fail(VIMG_E_INVALID, "rectify: the output codes overlap %s", r->name);
   if (d_out_rgb && d_out_code && overlaps(d_out_rgb, frame, d_out_code, n))
     return fail(VIMG_E_INVALID, "rectify: the output overlaps the output codes");
 
@@ -208,17 +189,11 @@ int vimg_rectify_clamp(const VimgRectifyFrames* f, const VimgRectifyParams* a, v
   const dim3 block = pixel_block(), grid = pixel_grid(w, h);
   hipStream_t s = static_cast<hipStream_t>(stream);
   clear_stale_error();
-#define VIMG_RECTIFY_CLAMP(R)                                                                                               \
-  rectify_clamp_kernel<R><<<grid, block, 0, s>>>(w, h, a->min_taps, a->k, a->cut, a->sigma_normal, a->sigma_plane,          \
-                                                 a->albedo_floor, slow, slow + n, slow + 2 * n, fast,                       \
-                                                 static_cast<const float*>(f->albedo), static_cast<float*>(d_out_rgb),      \
-                                                 static_cast<uint8_t*>(d_out_code))
-  switch (a->radius) {
-    case 1: VIMG_RECTIFY_CLAMP(1); break;
-    case 2: VIMG_RECTIFY_CLAMP(2); break;
-    default: VIMG_RECTIFY_CLAMP(3); break;
-  }
-#undef VIMG_RECTIFY_CLAMP
+  with_radius<VIMG_RECTIFY_MAX_RADIUS>(a->radius, [&](auto R) {
+    rectify_clamp_kernel<R.value><<<grid, block, 0, s>>>(w, h, a->min_taps, a->k, a->cut, a->sigma_normal, a->sigma_plane, a->albedo_floor,
+                                                         slow, slow + n, slow + 2 * n, fast, static_cast<const float*>(f->albedo),
+                                                         static_cast<float*>(d_out_rgb), static_cast<uint8_t*>(d_out_code));
+  });
   return launched();
 }
 
