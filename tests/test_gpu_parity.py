@@ -1177,6 +1177,39 @@ def test_a_tree_deeper_than_the_lds_stack():
         assert gst.as_dict() == lst.as_dict(), sched
 
 
+_CORNERS = {}
+
+
+def _corner_frame():
+    """cornell_box_spheres at 20 x 12 (ragged tiles, triangles and spheres), mis, 3 spp: the scene, its parameters and the
+    lane-bound kernel's frame and statistics, rendered once for all the corners."""
+    if not _CORNERS:
+        s = scenes.json_scene("cornell_box_spheres.json", res=(20, 12))
+        p = s.default_params(samples=3, integrator="mis")
+        _CORNERS["ref"] = (s, p) + tuple(_dev_opts(s, scheduler="lane").render_to_host(p))
+    return _CORNERS["ref"]
+
+
+@pytest.mark.parametrize("corner", ["lds_budget_kb=1", "lds_stack=4", "pool_slots=8", "cu_walkers=1", "cu_walkers=16", "lds_leaf=0",
+                                    "pool_segments=2", "VIMG_HIP_LDS_TABLES=0"])
+def test_cu_layout_corners(corner, monkeypatch):
+    """The corners of the workgroup's LDS carve (cu_layout.h), one option at a time: the smallest node budget, a stack
+    mostly in global memory, the smallest pool, one walking wave and sixteen, leaves out of LDS, two segments, and no
+    table staged.  Each must give the lane-bound kernel's image bit for bit and its statistics."""
+    s, p, lane, lst = _corner_frame()
+    name, value = corner.split("=")
+    opts = dict(scheduler="cu")
+    if name.startswith("VIMG_"):
+        monkeypatch.setenv(name, value)   # (read once, at upload)
+    else:
+        opts[name] = int(value)
+    d = _dev_opts(s, **opts)
+    assert d.kernel.startswith("render_cu_kernel<"), d.kernel
+    gpu, gst = d.render_to_host(p)
+    assert np.array_equal(gpu.view(np.uint32), lane.view(np.uint32)), (corner, d.kernel)
+    assert gst.as_dict() == lst.as_dict(), corner
+
+
 def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` with no rendezvous in the environment must start the ranks itself
     (fresh child processes; the driver invokes it exactly like this) and relay one JSON line.

@@ -1,7 +1,10 @@
 // What the host units of libvimg_hip.so share (none of it is exported: include/vimg_hip.h is the ABI).
 //   vimg_hip.hip       init / options / last_error, the render entry points, enqueue_render
 //   scene_upload.hip   validation, baking and upload of a scene, its changes, its release
-//   launch_policy.hip  the configuration of one launch: render_cu_kernel, the lane-bound render_kernel, feature_kernel
+//   launch_plan.hip    the plan of one launch (render_cu_kernel, the lane-bound render_kernel, feature_kernel) from a
+//                      few facts of the scene: host arithmetic only, no runtime call (launch_plan.h; cu_layout.h is the
+//                      workgroup's LDS, shared with the kernel)
+//   launch_policy.hip  its HIP side: the facts of a device scene, the lane launch's occupancy query, plan -> kernel
 //   ray_query.hip      ray queries        precompute.hip   texture pre-pass and post-processing
 //   scene_rebuild.hip  a new tree for a resident scene, its cost       bvh_build.hip    the GPU builders and their cores
 //   scene_relight.hip  new materials, texture contents, emitters and background of a resident scene
@@ -18,6 +21,7 @@
 #include "device_mem.h"
 #include "device_scene.h"
 #include "kernel_tus.h"
+#include "launch_plan.h"
 
 #pragma GCC visibility push(hidden)
 struct VimgDeviceScene {
@@ -97,26 +101,6 @@ extern hipStream_t g_stream;   // vimg_hip.hip (vimg_hip_init)
 extern int g_device;
 // the stream argument of the ABI: NULL = the library's own stream
 inline hipStream_t stream_of(void* stream) { return stream ? static_cast<hipStream_t>(stream) : g_stream; }
-
-inline uint32_t tiles_of(int n) { return (static_cast<uint32_t>(n) + 7u) / 8u; }
-uint32_t local_tiles(const VimgDeviceScene* s, const VimgRenderParams* p);
-// the first-hit feature integrators (feature_kernel.h): one kernel of their own, whatever the scheduler option says
-inline bool is_feature_integrator(uint32_t i) { return i >= VIMG_INTEGRATOR_ALBEDO && i <= VIMG_INTEGRATOR_COVERAGE; }
-inline uint32_t opt_or(int32_t v, uint32_t dflt) { return v == VIMG_OPT_AUTO ? dflt : static_cast<uint32_t>(v); }
-
-struct LaunchCfg {
-  const char* error;   // nullptr, or why no launch can be made of the scene's options (make_launch_cu): VIMG_E_INVALID
-  RenderArgs args;
-  uint32_t grid, lds_bytes;
-  uint32_t table_bytes;   // CU scheduler: the part of lds_bytes that holds the shading tables and the permuted leaf copies (the end of the layout)
-  int sched;     // VIMG_SCHED_CU or VIMG_SCHED_LANE
-  int wps;       // register-budget build (waves per SIMD of __launch_bounds__)
-  bool deep;     // CU scheduler: build whose box loop yields to waiting leaves (tree beyond the LDS node cache)
-  int cu_waves;  // CU scheduler: waves per workgroup (16 or 8)
-  bool feature;  // feature_kernel (integrators ALBEDO .. COVERAGE) in the lane launch's shape: sched is VIMG_SCHED_LANE
-  size_t cold_bytes;   // scene-owned scratch of the launch: cold slot records of every workgroup (0: none) ...
-  size_t ovf_bytes;    // ... and the stack entries beyond stack_lds (0: the stacks fit)
-};
 
 // ---- bvh_build.hip: the cores of vimg_hip_build_ploc / _lbvh.  They take the primitive bounds (n x {min.xyz,
 // max.xyz}) on the device and leave the tree in the reference's layout (include/bvh.h:22-57) there too: nodes
@@ -199,25 +183,12 @@ uint64_t fetch_shard_pixels(const VimgDeviceScene* s, const VimgRenderParams* p)
 int fetch_stats(VimgDeviceScene* s, const VimgRenderParams* p, VimgRenderStats* out);   // (paths = pixels x p->samples)
 
 // ---- launch_policy.hip
+LaunchFacts facts_of(const VimgDeviceScene* s);   // what the planner (launch_plan.h) knows of the scene: filled here and nowhere else
+// the plan of a launch: plan_launch, with the grid of a lane-shaped launch sized by its kernel's occupancy
 LaunchCfg make_launch(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
-// the lane-bound kernel's launch; also the LDS layout (stacks, then the top of the tree) of probes, the heatmap and queries
-LaunchCfg make_launch_lane(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
-// feature_kernel's launch (integrators ALBEDO .. COVERAGE): make_launch_lane's layout, its own persistent grid
-LaunchCfg make_launch_feature(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
-RenderArgs base_args(const VimgDeviceScene* s, const VimgRenderParams* p, int sx, int sy);
-// Splits a pixel's samples into segments handed out as separate work items (sets pool_segments, pool_seg_len;
-// returns the length): about `per_gen` segments per pool generation of the frame, at most `most`
-uint32_t segments_for(const VimgDeviceScene* s, const VimgRenderParams* p, uint64_t items, uint64_t in_flight,
-                      double per_gen, double most, RenderArgs* a);
-// the kernel the policy sizes a launch for, and the build of it that runs (render_cu_kernel: the statistics
-// build for `stats`, the early-ray build for cu_flex bit 5, a PLAIN build where plain_launch_serves says so)
-const void* kernel_of(const VimgDeviceScene* s, const LaunchCfg& c);
+// the build that runs a plan (render_cu_kernel: the statistics build for `stats`, the early-ray build for cu_flex
+// bit 5, a PLAIN build where plain_fold_of names one)
 const void* launched_kernel_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
-// whether the launch, as its arguments stand, runs a PLAIN build (plain_build.h)
-bool plain_launch_serves(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);
-uint32_t plain_fold_of(const VimgDeviceScene* s, const LaunchCfg& c, bool stats);   // the serving build's fold (plain_build.h), 0 = none
-// takes the shading tables out of a launch that will not run a PLAIN build (call once its arguments are complete)
-void drop_unread_tables(const VimgDeviceScene* s, LaunchCfg& c, bool stats);
 
 }  // namespace vimg
 #pragma GCC visibility pop

@@ -4,8 +4,8 @@
 #include "render_cu_kernel.h"
 
 namespace vimg {
-CuKernel vimg_cu_kernel_diag(bool tex, bool deep, int) {
-  if (tex) return deep ? render_cu_kernel<true, true, 16, 4, true, 2> : render_cu_kernel<true, false, 16, 4, true, 2>;
-  return deep ? render_cu_kernel<false, true, 16, 4, true, 2> : render_cu_kernel<false, false, 16, 4, true, 2>;
+CuKernel vimg_cu_kernel_diag(bool tex, bool deep) {
+  if (tex) return deep ? render_cu_kernel<true, true, CU_WAVES, 4, true, 2> : render_cu_kernel<true, false, CU_WAVES, 4, true, 2>;
+  return deep ? render_cu_kernel<false, true, CU_WAVES, 4, true, 2> : render_cu_kernel<false, false, CU_WAVES, 4, true, 2>;
 }
 }  // namespace vimg

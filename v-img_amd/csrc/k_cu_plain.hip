@@ -5,5 +5,5 @@
 #include "render_cu_kernel.h"
 
 namespace vimg {
-CuKernel vimg_cu_kernel_plain() { return render_cu_kernel<false, false, 16, 4, false, 0, PLAIN_FOLD>; }
+CuKernel vimg_cu_kernel_plain() { return render_cu_kernel<false, false, CU_WAVES, 4, false, 0, PLAIN_FOLD>; }
 }  // namespace vimg

@@ -4,5 +4,5 @@
 #include "render_cu_kernel.h"
 
 namespace vimg {
-CuKernel vimg_cu_kernel_plain_early() { return render_cu_kernel<false, false, 16, 4, false, 1, PLAIN_FOLD>; }
+CuKernel vimg_cu_kernel_plain_early() { return render_cu_kernel<false, false, CU_WAVES, 4, false, 1, PLAIN_FOLD>; }
 }  // namespace vimg

@@ -4,5 +4,5 @@
 #include "render_cu_kernel.h"
 
 namespace vimg {
-CuKernel vimg_cu_kernel_plain_other() { return render_cu_kernel<false, false, 16, 4, false, 0, PLAIN_FOLD_OTHER>; }
+CuKernel vimg_cu_kernel_plain_other() { return render_cu_kernel<false, false, CU_WAVES, 4, false, 0, PLAIN_FOLD_OTHER>; }
 }  // namespace vimg

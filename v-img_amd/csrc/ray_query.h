@@ -13,7 +13,7 @@ enum RayQueryKind { QUERY_CLOSEST = 0, QUERY_CLOSEST_INFO = 1, QUERY_OCCLUDED = 
 const void* ray_query_kernel(int kind);
 
 // Enqueues one query launch of `grid` 256-thread workgroups with `lds_bytes` of LDS laid out by `A`
-// (make_launch_lane): rays 32 B each, hits 16 B, info 48 B (or nullptr), flags 1 B.
+// (launch_plan.h: lane_layout): rays 32 B each, hits 16 B, info 48 B (or nullptr), flags 1 B.
 hipError_t enqueue_ray_query(const DScene& d, const RenderArgs& A, int kind, uint32_t grid, uint32_t lds_bytes,
                              const void* rays, uint32_t n, void* hits, void* info, uint8_t* flags, hipStream_t st);
 

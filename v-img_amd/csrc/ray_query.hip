@@ -8,7 +8,7 @@
 //
 // The query kernels call traverse / make_hit_info of render_kernels.h unchanged, so a ray's answer is the
 // render's bits.  Launch shape: a persistent grid (as many 256-thread workgroups as the CU holds at the LDS
-// size of make_launch_lane); each workgroup stages the top of the tree into LDS once and
+// size of lane_layout); each workgroup stages the top of the tree into LDS once and
 // its waves then take whole 64-ray chunks, chunk = global wave + k * waves of the grid.  A lane loads its
 // ray as two 16-byte loads and stores its hit as one (plus three for the record).  The same kernel on a
 // grid of one workgroup per 256 rays is the probe's launch; which of the two runs is the policy of
@@ -139,7 +139,7 @@ int check_query(const char* what, const VimgDeviceScene* s, uint64_t n, const vo
 int ensure_query(VimgDeviceScene* s) {
   if (s->query_ready) return VIMG_OK;
   VimgRenderParams p{VIMG_INTEGRATOR_MIS, 1, 1, 0, 1};
-  const LaunchCfg c = make_launch_lane(s, &p, -1, -1);
+  const LaunchCfg c = lane_layout(facts_of(s), p);
   s->query_args = c.args;
   s->query_lds = c.lds_bytes;
   for (int k = QUERY_CLOSEST; k <= QUERY_OCCLUDED; ++k) {

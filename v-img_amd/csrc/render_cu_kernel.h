@@ -43,6 +43,7 @@
 #pragma once
 #include <type_traits>
 
+#include "cu_layout.h"
 #include "plain_build.h"
 #include "render_kernels.h"
 
@@ -59,11 +60,7 @@ enum : uint32_t {
   SC4_RNG,             // rng lo | rng hi | px + (py << 16) | sample index
   SC4_MAIN             // records of the main line
 };
-// 16-byte records per slot in a cold region: main line + accumulator + cone
-__host__ __device__ constexpr uint32_t cu_cold_records(bool tex) { return SC4_MAIN + 1u + (tex ? 1u : 0u); }
-// rows of a lane's LDS stack: all entries, or the first stack_lds and one more that takes the
-// writes of the entries kept in global memory
-__host__ __device__ constexpr uint32_t cu_stack_rows_of(uint32_t entries, uint32_t in_lds) { return in_lds < entries ? in_lds + 1u : entries; }
+static_assert(SC4_MAIN == CU_COLD_MAIN, "cu_layout.h: cu_cold_records");   // (records per slot in a cold region: cu_cold_records)
 constexpr uint32_t SLOT_IDLE = 0xffffffffu;   // a walking lane that holds no ray
 
 // words of a pixel's between-segments record: agent-scope relaxed atomics (global_load/store sc1)
@@ -103,9 +100,7 @@ constexpr uint32_t CU_RAY_S = 0x8000u;   // walk-ring entry: the SHADOW ray of t
 // with are bound by the service time of their hops, not by queueing - and the full frame paid 7 %
 // for the second set of pops and ballots: 325 against 304 ms.)
 constexpr uint32_t CQ_WALK = 4u, CQ_COUNT = 5u;
-// LDS bytes per slot: hot records, {primitive id, t} of the hit, four vertex rings (capacity P),
-// the walk ring (capacity 2 P: two rays per slot), time of the last hand-over (statistics launches)
-constexpr uint32_t CU_LDS_BYTES = CR_COUNT * 16u + 8u + 4u * 2u + 2u * 2u + 4u;
+static_assert(CR_COUNT == CU_HOT_RECORDS, "cu_layout.h: the LDS bytes of a slot, CU_LDS_BYTES");
 
 // queue state of the workgroup, in LDS
 struct CuCtl {
@@ -117,7 +112,7 @@ struct CuCtl {
   uint32_t t0_lo, t0_hi;   // s_memrealtime at the start of the workgroup (statistics launches)
   uint32_t pad[1];
 };
-static_assert(sizeof(CuCtl) == 96, "CuCtl layout");
+static_assert(sizeof(CuCtl) == CU_CTL_BYTES, "CuCtl layout (cu_layout.h)");
 // per wave, in LDS: what only statistics launches touch (event counts beyond the two ray counts,
 // cycles by stage: 0-3 vertex batches by class, 4 walk, 5 idle; batches and slots by class)
 struct CuWaveRec {
@@ -131,12 +126,9 @@ struct CuWaveRec {
   unsigned long long ray_cyc, ray_n;           // cycles rays spent in a walking lane, from the pop to the hand-over
   unsigned long long pv_cyc[6], pv_n;          // Principled batches: cycles in state loads, hit record + path logic, light sample, BSDF sample, evaluations, stores + hand-over
 };
-static_assert(sizeof(CuWaveRec) == 416, "CuWaveRec layout");
-__host__ __device__ constexpr uint32_t cu_pool_bytes(uint32_t slots, uint32_t waves) {
-  return CU_LDS_BYTES * slots + uint32_t(sizeof(CuCtl)) + waves * uint32_t(sizeof(CuWaveRec));
-}
+static_assert(sizeof(CuWaveRec) == CU_WAVE_REC_BYTES, "CuWaveRec layout (cu_layout.h)");
 // divisor d -> (magic, shift) with n / d == mulhi(n, magic) >> shift for every n < 2^31
-// (Granlund & Montgomery; host side in launch_policy.hip:magic_div)
+// (Granlund & Montgomery; host side in launch_plan.hip:magic_div)
 VD uint32_t cu_mod(uint32_t n, uint32_t d, uint32_t magic, uint32_t shift) { return n - d * (__umulhi(n, magic) >> shift); }
 VD int32_t lds_add_rtn(VIMG_LDS int32_t* p, int32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 VD uint32_t lds_add_rtn(VIMG_LDS uint32_t* p, uint32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -220,14 +212,15 @@ VD void stage_leaf_perm(const DScene& g, const RenderArgs& A, VIMG_LDS v4f* lds_
   for (uint32_t i = threadIdx.x; i < 2u * n; i += blockDim.x) {
     const int k = i < n ? 0 : 1;
     const uint32_t r = i - (k ? n : 0u);
-    gptr<v4f> src = reinterpret_cast<gptr<v4f>>(g.leaf_prims) + r * 3u;
+    constexpr uint32_t rec = CU_LEAF_BYTES / 16u;   // a leaf record in 16-byte words
+    gptr<v4f> src = reinterpret_cast<gptr<v4f>>(g.leaf_prims) + r * rec;
     v4f a = src[0], b = src[1], c = src[2];
     if (__float_as_uint(c.z) == 0u) {   // kind: a triangle
       const f3 p0 = permute(f3{a.x, a.y, a.z}, k), p1 = permute(f3{a.w, b.x, b.y}, k), p2 = permute(f3{b.z, b.w, c.x}, k);
       a = v4f{p0.x, p0.y, p0.z, p1.x}, b = v4f{p1.y, p1.z, p2.x, p2.y}, c.x = p2.z;
     }
     VIMG_LDS v4f* dst = reinterpret_cast<VIMG_LDS v4f*>(reinterpret_cast<VIMG_LDS unsigned char*>(lds_leaf) + A.leaf_perm_off +
-                                                        uint32_t(k) * A.leaf_perm_stride) + r * 3u;
+                                                        uint32_t(k) * A.leaf_perm_stride) + r * rec;
     dst[0] = a, dst[1] = b, dst[2] = c;
   }
 }
@@ -275,20 +268,26 @@ VD CuKPtr cu_kargs() {
   [[maybe_unused]] const bool material_mode = (opt_integrator<PLAIN>(A) == VIMG_INTEGRATOR_MATERIAL);                   \
   [[maybe_unused]] const uint32_t P = A.pool_slots;                                                                     \
   [[maybe_unused]] const bool can_walk = wave < A.cu_walkers;                                                           \
+  /* The carve-out of cu_layout.h.  Behind the stacks every region lies a multiple of the slot count, or a constant,    \
+     behind the one before it: the layout of ONE slot (a constant) says how many bytes, and each pointer is stepped in  \
+     elements of its own type, as the compiler has always seen it */                                                    \
   const uint32_t stack_rows_ = cu_stack_rows_of(A.stack_entries, A.stack_lds);                                          \
-  const uint32_t node_bytes_ = (lds_node_bytes(A.lds_nodes) + 255u) & ~255u;                                            \
+  const uint32_t node_bytes_ = cu_node_plane_bytes(A.lds_nodes);                                                        \
+  constexpr CuLayout one_ = cu_layout(0u, 0u, 0u, 1u, NW, 0u);                                                          \
   [[maybe_unused]] VIMG_LDS uint32_t* stack0 =                                                                          \
       reinterpret_cast<VIMG_LDS uint32_t*>((VIMG_LDS unsigned char*)lds_raw + node_bytes_) +                            \
-      size_t(can_walk ? wave : 0u) * stack_rows_ * 64u + lane;                                                          \
-  VIMG_LDS unsigned char* base_ = (VIMG_LDS unsigned char*)lds_raw + node_bytes_ + A.cu_walkers * stack_rows_ * 256u;   \
+      size_t(can_walk ? wave : 0u) * stack_rows_ * (CU_STACK_ROW_BYTES / 4u) + lane;                                    \
+  VIMG_LDS unsigned char* base_ = (VIMG_LDS unsigned char*)lds_raw + node_bytes_ + A.cu_walkers * stack_rows_ * CU_STACK_ROW_BYTES; \
   [[maybe_unused]] VIMG_LDS v4u* recs = reinterpret_cast<VIMG_LDS v4u*>(base_);                                         \
-  [[maybe_unused]] VIMG_LDS v2u* hitx = reinterpret_cast<VIMG_LDS v2u*>(recs + CR_COUNT * P);                           \
-  [[maybe_unused]] VIMG_LDS uint16_t* ring_v = reinterpret_cast<VIMG_LDS uint16_t*>(hitx + P);                          \
-  [[maybe_unused]] VIMG_LDS uint16_t* ring_w = ring_v + 4u * P;                                                         \
-  [[maybe_unused]] VIMG_LDS uint32_t* tq = reinterpret_cast<VIMG_LDS uint32_t*>(ring_w + 2u * P);                       \
-  [[maybe_unused]] VIMG_LDS CuCtl* G = reinterpret_cast<VIMG_LDS CuCtl*>(tq + P);                                       \
-  [[maybe_unused]] VIMG_LDS CuWaveRec* wrec = reinterpret_cast<VIMG_LDS CuWaveRec*>(G + 1) + wave;                      \
-  [[maybe_unused]] VIMG_LDS v4f* lds_leaf = reinterpret_cast<VIMG_LDS v4f*>(reinterpret_cast<VIMG_LDS CuWaveRec*>(G + 1) + NW); \
+  [[maybe_unused]] VIMG_LDS v2u* hitx = reinterpret_cast<VIMG_LDS v2u*>(recs + (one_.hitx - one_.recs) / 16u * P);      \
+  [[maybe_unused]] VIMG_LDS uint16_t* ring_v = reinterpret_cast<VIMG_LDS uint16_t*>(hitx + (one_.ring_v - one_.hitx) / 8u * P); \
+  [[maybe_unused]] VIMG_LDS uint16_t* ring_w = ring_v + (one_.ring_w - one_.ring_v) / 2u * P;                           \
+  [[maybe_unused]] VIMG_LDS uint32_t* tq = reinterpret_cast<VIMG_LDS uint32_t*>(ring_w + (one_.tq - one_.ring_w) / 2u * P); \
+  [[maybe_unused]] VIMG_LDS CuCtl* G = reinterpret_cast<VIMG_LDS CuCtl*>(tq + (one_.ctl - one_.tq) / 4u * P);           \
+  [[maybe_unused]] VIMG_LDS CuWaveRec* wrec = reinterpret_cast<VIMG_LDS CuWaveRec*>(G + (one_.wave_recs - one_.ctl) / CU_CTL_BYTES) + wave; \
+  [[maybe_unused]] VIMG_LDS v4f* lds_leaf =                                                                             \
+      reinterpret_cast<VIMG_LDS v4f*>(reinterpret_cast<VIMG_LDS CuWaveRec*>(G + (one_.wave_recs - one_.ctl) / CU_CTL_BYTES) + \
+                                      (one_.leaf - one_.wave_recs) / CU_WAVE_REC_BYTES);                                \
   [[maybe_unused]] VIMG_LDS uint32_t* recw = reinterpret_cast<VIMG_LDS uint32_t*>(recs);                                \
   /* the scene as the vertex stages read its shading tables: from LDS for the groups this build folds (PF_TAB_*) */     \
   [[maybe_unused]] const auto& gt = table_view<(PLAIN & PF_TABLES)>(g, A, (const VIMG_LDS unsigned char*)lds_raw);      \

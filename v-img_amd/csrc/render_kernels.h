@@ -15,6 +15,7 @@
 //
 // Every function cites the reference code whose result it must reproduce.
 #pragma once
+#include "cu_layout.h"
 #include "device_math.h"
 #include "device_scene.h"
 #include "material_terms.h"
@@ -1614,7 +1615,6 @@ VD float geometric_term(f3 look_from, f3 point_on_surface, f3 surface_normal) {
 }
 
 // ================================================================================ LDS set-up
-VD uint32_t lds_node_bytes(uint32_t n) { return n * (3 * 16 + 8); }
 // where the node planes and this lane's stack live (pointer arithmetic only)
 VD Lds lds_layout(const RenderArgs& A, VIMG_LDS unsigned char* lds_raw) {
   const uint32_t n = A.lds_nodes;
@@ -1623,12 +1623,12 @@ VD Lds lds_layout(const RenderArgs& A, VIMG_LDS unsigned char* lds_raw) {
   VIMG_LDS v4f* nc = nb + n;
   VIMG_LDS v2u* nm = reinterpret_cast<VIMG_LDS v2u*>(nc + n);
   // stacks start at the next 256-byte boundary: [wave][entry][lane]
-  uint32_t stack_off = (lds_node_bytes(n) + 255u) & ~255u;
+  uint32_t stack_off = cu_node_plane_bytes(n);
   VIMG_LDS uint32_t* stacks = reinterpret_cast<VIMG_LDS uint32_t*>(lds_raw + stack_off);
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   Lds L;
   L.na = na, L.nb = nb, L.nc = nc, L.nm = nm;
-  L.stack = stacks + size_t(wave) * A.stack_entries * 64 + lane;
+  L.stack = stacks + size_t(wave) * A.stack_entries * (CU_STACK_ROW_BYTES / 4u) + lane;
   L.n_nodes = n;
   return L;
 }

@@ -105,7 +105,7 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, const RenderLa
   }
   if (int rc = ensure_pool(s, c)) return rc;
   c.args.full_stats = r.stats ? 1u : 0u;
-  drop_unread_tables(s, c, r.stats);
+  drop_unread_tables(facts_of(s), c, r.stats);
   if (c.args.num_local_tiles == 0 && r.sx < 0) return VIMG_OK;
   // (the work counter only: the error word behind it is sticky until a blocking call or vimg_hip_check reads it)
   HIP_TRY(hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), st));
@@ -118,7 +118,7 @@ int enqueue_render(VimgDeviceScene* s, const VimgRenderParams* p, const RenderLa
   if (c.sched == VIMG_SCHED_CU) {
     CuKArgs ka{s->d, c.args, d_out, stats, s->counter.as<unsigned int>()};
     void* kargs[] = {&ka};
-    HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(uint32_t(c.cu_waves) * 64u), kargs, c.lds_bytes, st));
+    HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(CU_WAVES * 64u), kargs, c.lds_bytes, st));
   } else {
     void* kargs[] = {&s->d, &c.args, &d_out, &stats, &s->counter.p};
     HIP_TRY(hipLaunchKernel(kernel, dim3(c.grid), dim3(256), kargs, c.lds_bytes, st));
@@ -251,7 +251,7 @@ void vimg_hip_options_default(VimgHipOptions* o) {
 int64_t vimg_hip_shard_pixels(const VimgDeviceScene* s, const VimgRenderParams* p) {
   int rc = check_params(s, p);
   if (rc) return rc;
-  return int64_t(local_tiles(s, p)) * 64;
+  return int64_t(local_tiles(facts_of(s), *p)) * 64;
 }
 
 int vimg_hip_render_async(VimgDeviceScene* s, const VimgRenderParams* p, void* d_out, void* stream) {
@@ -290,7 +290,7 @@ int vimg_hip_progressive_create(VimgDeviceScene* s, const VimgRenderParams* p, V
   a->scene = s;
   a->generation = s->generation;
   a->params = q;
-  a->items = uint64_t(local_tiles(s, &q)) * 64u;
+  a->items = uint64_t(local_tiles(facts_of(s), q)) * 64u;
   const size_t bytes = std::max<size_t>(a->items, 1) * 32u;
   for (auto& r : a->rec) {
     if (int rc = r.alloc(bytes)) return rc;
@@ -334,7 +334,7 @@ int vimg_hip_render_heatmap(VimgDeviceScene* s, const VimgRenderParams* p, float
   if (int rc = check_render(s, p, d_out)) return rc;
   if (factor <= 0) factor = 20.f;   // heatmap.cpp:137-139
   hipStream_t st = stream_of(stream);
-  LaunchCfg c = make_launch_lane(s, p, -1, -1);
+  const LaunchCfg c = lane_layout(facts_of(s), *p);
   if (c.args.num_local_tiles == 0) return VIMG_OK;
   if (c.lds_bytes > 48u * 1024u)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(heatmap_kernel),
@@ -424,7 +424,7 @@ int vimg_hip_probe(VimgDeviceScene* s, int kind, int n, const float* in_host, fl
       out_host[i] = 0.f;
       if (p.tile_world == 0 || p.tile_rank >= p.tile_world || is_feature_integrator(p.integrator)) continue;
       const LaunchCfg c = make_launch(s, &p, -1, -1);
-      if (!c.error && c.sched == VIMG_SCHED_CU) out_host[i] = float(plain_fold_of(s, c, false));
+      if (!c.error && c.sched == VIMG_SCHED_CU) out_host[i] = float(plain_fold_of(facts_of(s), c, false));
     }
     return VIMG_OK;
   }
@@ -435,7 +435,7 @@ int vimg_hip_probe(VimgDeviceScene* s, int kind, int n, const float* in_host, fl
   if (int rc = d_out.alloc(size_t(n) * n_out[kind] * sizeof(float))) return rc;
   HIP_TRY(hipMemcpy(d_in.p, in_host, size_t(n) * n_in[kind] * sizeof(float), hipMemcpyHostToDevice));
   VimgRenderParams p{VIMG_INTEGRATOR_MIS, 1, 1, 0, 1};
-  LaunchCfg c = make_launch_lane(s, &p, -1, -1);
+  const LaunchCfg c = lane_layout(facts_of(s), p);
   const uint32_t grid = (uint32_t(n) + 255) / 256;
   if (s->textured)
     hipLaunchKernelGGL(probe_kernel<true>, dim3(grid), dim3(256), c.lds_bytes, g_stream, s->d, c.args,
